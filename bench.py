@@ -20,6 +20,8 @@ collective; ranks only barrier and reduce the elapsed time (MAX = the job's time
 WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, backend nccl = RCCL); under `python -m torch.distributed.run
 --nproc-per-node N bench.py --gpus N` it uses the ranks it was given.  Rank 0 prints ONE JSON line.
 `--dry-run` replaces the GPU work by a sleep (CPU / gloo: exercises launcher, barriers, reductions and the JSON line).
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs) as .npy files: the inputs come from fixed seeds, so
+two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -32,6 +34,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -158,6 +161,39 @@ def extra_config_roofline(label, c, dev, klib, D=128, g=32, n_layers=8, steps=42
             "tokens_per_s_at_median_launch_32_layers": round(B / (med * 1e-6 * 32), 1)}
 
 
+CACHE_MEMBERS = ("k_code", "k_res", "k_scale", "k_mn", "v_code", "v_res", "v_scale", "v_mn")   # the reference's 9-tuple, minus its length
+
+
+def _seeded_sample(x, n, seed):
+    """n elements of x at indices fixed by (seed, x.numel()): the same positions in every run and every build."""
+    idx = torch.randint(0, x.numel(), (n,), generator=torch.Generator().manual_seed(seed))
+    return x.reshape(-1)[idx.to(x.device)]
+
+
+def dump_outputs(d, outs, layers, max_bytes=60 * 2**20):
+    """What a caller of the timed path holds after the last timed step, as DIR/<name>.npy: `attn_output` = every layer's returned
+    attention output stacked (L, B, nh, 1, D) in float32 (a seeded flat sample when it exceeds 3/4 of `max_bytes`), and
+    `cache_<member>` = of every layer's in-place cache, the reference-layout 9-tuple member (codes int32, scales / zeros / residuals
+    fp16) at seeded positions, (L, n) in float64 (exact for both).  Returns {name: shape}."""
+    os.makedirs(d, exist_ok=True)
+    files = {}
+    a = torch.stack(outs)
+    cap = (max_bytes * 3 // 4) // 4
+    files["attn_output"] = (a if a.numel() <= cap else _seeded_sample(a, cap, 0)).float().cpu().numpy()
+    n = min(4096, (max_bytes // 4) // (8 * len(CACHE_MEMBERS) * len(layers)))
+    per = {m: [] for m in CACHE_MEMBERS}
+    for lc in layers:
+        for j, (m, x) in enumerate(zip(CACHE_MEMBERS, lc.as_tuple()[:8])):
+            if x is not None and x.numel():
+                per[m].append(_seeded_sample(x, n, 1 + j).double().cpu())
+    for m, xs in per.items():
+        if xs:
+            files["cache_" + m] = torch.stack(xs).numpy()
+    for name, arr in files.items():
+        np.save(os.path.join(d, name + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in files.items()}
+
+
 def launch_ranks(n_gpus: int, argv, timeout_s: float = 3600.0) -> int:
     """`python bench.py --gpus N` without a launcher: start N ranks of this script (one process per GPU, the same
     environment contract as torch.distributed.run) and wait for them.  Rank 0 inherits stdout (the JSON line)."""
@@ -196,8 +232,9 @@ def launch_ranks(n_gpus: int, argv, timeout_s: float = 3600.0) -> int:
     return rc
 
 
-def dist_setup(n_gpus: int):
-    """Returns (rank, world, local_rank, dist-or-None).  backend nccl (= RCCL) on GPUs, gloo without."""
+def dist_setup(n_gpus: int, gpu: bool = True):
+    """Returns (rank, world, local_rank, dist-or-None).  backend nccl (= RCCL) on GPUs, gloo without -- and gloo when `gpu` is
+    False (--dry-run): its ranks touch no device, so they need none, however many the host has."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -207,7 +244,7 @@ def dist_setup(n_gpus: int):
     if world > 1:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        backend = "nccl" if torch.cuda.is_available() else "gloo"
+        backend = "nccl" if gpu and torch.cuda.is_available() else "gloo"
         if backend == "nccl":
             torch.cuda.set_device(local)
             dist.init_process_group(backend=backend, rank=rank, world_size=world, device_id=torch.device("cuda", local))
@@ -398,11 +435,17 @@ def main():
                                                    "row (one launch, a block per row) | slicesN (one launch, N slices per row)")
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the roofline_config4 / _config4_4bit / _config5_slice objects")
     ap.add_argument("--kgemv-passes", type=int, default=10, help="timed passes over the rotating caches of the single-layer K-GEMV lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned (every layer's "
+                                                          "attention output, a seeded sample of every layer's cache) as DIR/<name>.npy; rank 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU work that --dry-run leaves out")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:     # plain `python bench.py --gpus N`: start the ranks ourselves
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
-    rank, world, local, dist = dist_setup(args.gpus)
+    rank, world, local, dist = dist_setup(args.gpus, gpu=not args.dry_run)
     if args.dry_run:
         return dry_run(args, rank, world, dist)
     assert torch.cuda.is_available(), "bench.py needs a GPU (no CPU fallback exists)"
@@ -439,11 +482,14 @@ def main():
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats(dev)
 
-    def step():
+    def step(keep=None):
         for i in range(L):
-            kivi_attention_decode(qs[i], ks[i], vs[i], layers[i], fused_kernels=not args.unfused)
+            o = kivi_attention_decode(qs[i], ks[i], vs[i], layers[i], fused_kernels=not args.unfused)
+            if keep is not None:
+                keep.append(o)
 
     graphed = None
+    last_out = []                    # what the last timed step returned (graph: the static `outs` it wrote)
     if args.graph:
         # the whole step = ONE graph launch (+ a one-thread kernel that uploads the six lengths, + the K flushes every R steps)
         from kivi_amd.graph import GraphedDecode, MfStepDriver
@@ -456,6 +502,7 @@ def main():
                 drv.enqueue(i, qs[i], ks[i], vs[i], outs[i])
 
         graphed = GraphedDecode(drv, graph_body)
+        last_out = outs
         step = graphed.step          # noqa: F811
         args.no_kernel_events = True   # (event pairs cannot be captured)
 
@@ -489,7 +536,11 @@ def main():
     torch.cuda.synchronize()
     barrier(dist)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
+        step()
+    if args.dump_outputs and graphed is None:
+        step(last_out)
+    else:
         step()
     host_enqueue_s = time.perf_counter() - t0      # how long the host needed to enqueue the timed steps
     torch.cuda.synchronize()
@@ -499,6 +550,7 @@ def main():
     elapsed = max_over_ranks(own, dist, dev)
     per_rank = gather_over_ranks(own, dist, dev)
     matmul.launch_hook = None
+    dumped = dump_outputs(args.dump_outputs, last_out, layers) if args.dump_outputs and rank == 0 else None
     # K flushes (llama_kivi.py:343-356: R residual tokens quantised per channel, in place) that fell into the timed region
     R_ = cfg.residual_length
     k_res0 = T0 % R_
@@ -651,6 +703,8 @@ def main():
             "roofline_single_layer_kgemv": single,
             "roofline_single_layer_kgemv_mf_layout": single_mf,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "from": "the last timed step"}
         default_workload = (B, nh, nh_kv, D, T0, bits, g, R, L) == (32, 32, 32, 128, 4080, 2, 32, 32, 32) and args.form == "auto"
         if world == 1 and default_workload and not args.no_extra_configs and not args.unfused:
             # the other BASELINE.json configurations (driver-visible: these keys ride on the one JSON line); the headline's caches are

@@ -1,6 +1,7 @@
 """CPU, world_size 2 over gloo: the multi-process plumbing of bench.py (barrier + max-over-ranks timing,
 batch-sharded replicas with no data-path collective)."""
 import os
+import socket
 import sys
 
 import pytest
@@ -11,12 +12,19 @@ import torch.multiprocessing as mp
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _free_port():
+    """A port nothing listens on now (not derived from the PID: two tests of one session must not share one)."""
+    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
 def _worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     import bench
-    r, w, local, d = bench.dist_setup(world)       # gloo here (no GPU); nccl (= RCCL) on the GPU box
+    r, w, local, d = bench.dist_setup(world, gpu=False)    # the CPU plumbing: gloo, also on a host with GPUs
     assert (r, w) == (rank, world) and d is not None and d.get_backend() == "gloo"
     bench.barrier(d)
     local_seconds = 1.0 + rank                      # rank 1 is the straggler
@@ -31,14 +39,20 @@ def _worker(rank, world, port, q):
 def test_two_rank_timing_and_aggregate():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 29500 + (os.getpid() % 500)
+    port = _free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=120) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    try:
+        for p in procs:
+            p.start()
+        res = sorted(q.get(timeout=120) for _ in procs)
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+    finally:                                        # a rank left waiting for its peer must not outlive the test
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+                p.join()
     assert [r[1] for r in res] == [2.0, 2.0]                      # MAX over ranks on both
     assert res[0][2] == pytest.approx(2 * 32 * 10 / 2.0)            # aggregate tokens/s over the whole job
 
@@ -71,7 +85,7 @@ def test_bench_main_starts_its_own_ranks(launcher):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--dry-run"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-               "--master-port", str(29700 + os.getpid() % 200)] + cmd[1:]
+               "--master-port", str(_free_port())] + cmd[1:]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
