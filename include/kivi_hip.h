@@ -26,7 +26,7 @@
  *               a layer step:   kivi_decode_layer (hook-state cache: any 2- / 4-bit shape), kivi_mf_decode_layer and its
  *                               hipGraph form kivi_mf_decode_layer_dyn + kivi_mf_step_* (matrix-pipe cache: g = 32, D = 128,
  *                               2-bit with nh / nh_kv in {1, 4, 8} or 4-bit with nh / nh_kv in {1, 4}), with the packers of that
- *                               cache: kivi_kt_pack, kivi_vt_pack, kivi_kt_relayout, kivi_vt_relayout
+ *                               cache: kivi_kt_pack, kivi_vt_pack, kivi_vt_pack_at, kivi_kt_relayout, kivi_vt_relayout
  *   BUILDING BLOCKS (what the layer steps are composed of; exported for tests, tools and callers that keep their own cache
  *               bookkeeping -- same contracts, but no stability promise beyond the ABI version):  kivi_gemv_k_paged,
  *               kivi_decode_scores, kivi_softmax_scaled, kivi_decode_output, kivi_decode_softmax_output, kivi_decode_attend,
@@ -312,6 +312,11 @@ int kivi_kt_pack(const void* k, int64_t k_sb, int64_t k_sh, int64_t k_st, void* 
 int kivi_vt_pack(const void* v, int64_t v_sb, int64_t v_sh, int64_t v_st, void* vt, int64_t vt_sb, int64_t vt_sh,
                  int64_t vt_ss, void* vt_range, int B, int nh_kv, int64_t T, int D, int group_size, int bits,
                  kivi_stream_t stream);
+/* kivi_vt_pack_at: tokens [0, T) of v quantised per token into the VT layout at ANY token_offset (partly filled 32-token blocks are
+ * read, modified and written; other tokens' codes are kept): bit-identical to the V flush of the decode step, range marks included */
+int kivi_vt_pack_at(const void* v, int64_t v_sb, int64_t v_sh, int64_t v_st, void* vt, int64_t vt_sb, int64_t vt_sh,
+                    int64_t vt_ss, void* vt_range, int64_t token_offset, int B, int nh_kv, int64_t T, int D, int group_size,
+                    int bits, kivi_stream_t stream);
 /* (kt_range / vt_range may be null when to_ref != 0: reading a store does not touch its flags) */
 int kivi_kt_relayout(int to_ref, void* kt, int64_t kt_sb, int64_t kt_sh, int64_t kt_ss, void* kt_range, void* code,
                      int64_t code_sb, int64_t code_sh, int64_t code_sr, void* scale, void* mn, int64_t sm_sb, int64_t sm_sh,
@@ -480,6 +485,24 @@ int kivi_mf_decode_layer_dyn(const kivi_mf_layer_desc* layer, const kivi_mf_step
                              int64_t q_sb, int64_t q_sh, int nh, const void* knew, int64_t kn_sb, int64_t kn_sh, const void* vnew,
                              int64_t vn_sb, int64_t vn_sh, const void* mask, int64_t mask_sb, void* out, int64_t out_sb,
                              int64_t out_sh, kivi_stream_t stream);
+/*
+ * kivi_mf_extend_layer: Q >= 1 new tokens of one layer at once over a cache in the KT / VT layouts (same descriptor, same state
+ * array as kivi_mf_decode_layer; the ring window flag is required).  q (B, nh, Q, D), knew / vnew (B, nh_kv, Q, D) fp16 (RoPE
+ * applied; rows addressed as base + b*sb + h*sh + i*st, 16-byte aligned), out (B, nh, Q, D).  Chunk row i sits at position
+ * P0 + i (P0 = state[5]) and attends to the whole cache as it stood before the call (packed K / V, the K residual, the V window) and
+ * to chunk tokens 0..i (causal, always); `mask` (optional) is an additive fp16 mask, row i of batch b at mask + b*mask_sb +
+ * i*mask_sq, P0 + Q keys (mask_sq >= P0 + Q).  Per row the arithmetic of one decode step (llama_kivi.py:314-399): fp32 sums of
+ * q * (scale * code + zero), fp16 scores / sqrt(D) in fp16, + mask, fp32 softmax, fp16 probabilities, fp16(fp16(packed sV) +
+ * fp16(fp16 sV)) (the kernel reads the keys twice: the row's softmax statistics, then the probabilities).  In stream order: the attention launch, the K flushes (the residual filled to R and
+ * packed with kivi_kt_pack, whole R-runs packed straight from knew, the rest copied into the residual), kivi_vt_pack_at of the
+ * values that leave the window, the new window rows.  The resulting cache (9-tuple and range words) is bit-identical to Q
+ * kivi_mf_decode_layer steps fed the same keys and values.  Everything is validated before the first launch; `state` is written
+ * once, at the end.  KIVI_EINVAL for Q < 1, a mask pitch below P0 + Q, a capacity below P0 + Q, inconsistent lengths.
+ */
+int kivi_mf_extend_layer(const kivi_mf_layer_desc* layer, int64_t* state, int Q, const void* q, int64_t q_sb, int64_t q_sh,
+                         int64_t q_st, int nh, const void* knew, int64_t kn_sb, int64_t kn_sh, int64_t kn_st, const void* vnew,
+                         int64_t vn_sb, int64_t vn_sh, int64_t vn_st, const void* mask, int64_t mask_sb, int64_t mask_sq, void* out,
+                         int64_t out_sb, int64_t out_sh, int64_t out_st, kivi_stream_t stream);
 /* geometry class of a step (-1: bad arguments): the super-block counts of both stores and whether the step flushes a value; the
  * launch plan (one launch / S slices / two launches) is a function of the class and of constants of the call (shape, bits, flags) */
 int64_t kivi_mf_step_key(const kivi_mf_step* step, int B, int nh, int nh_kv, int residual_length, int flags);

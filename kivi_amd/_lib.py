@@ -164,6 +164,9 @@ SIGNATURES = {
                                     _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp]),
     "kivi_mf_decode_layer_dyn": (_i32, [ctypes.POINTER(MfLayerDesc), ctypes.POINTER(MfStep), _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64,
                                         _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp]),
+    "kivi_mf_extend_layer": (_i32, [ctypes.POINTER(MfLayerDesc), ctypes.POINTER(_i64), _i32, _vp, _i64, _i64, _i64, _i32, _vp, _i64,
+                                    _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
+    "kivi_vt_pack_at": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _i32, _i64, _i32, _i32, _i32, _vp]),
     "kivi_mf_step_key": (_i64, [ctypes.POINTER(MfStep), _i32, _i32, _i32, _i32, _i32]),
     "kivi_mf_step_advance": (_i32, [ctypes.POINTER(MfStep), _i32, _i64]),
     "kivi_mf_step_upload": (_i32, [ctypes.POINTER(MfStep), _vp, _vp]),

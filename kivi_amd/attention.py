@@ -250,6 +250,16 @@ def kivi_attention_decode(query_states: torch.Tensor, key_states: torch.Tensor, 
     return res
 
 
+def kivi_attention_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layer, attention_mask: Optional[torch.Tensor] = None,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Q >= 1 new tokens for one layer that already holds a cache (multi-turn continuation, a prompt fed in pieces, a block of
+    draft tokens).  q (B, nh, Q, D), k / v (B, nh_kv, Q, D) fp16, RoPE applied.  Chunk row i sits at position P0 + i
+    (P0 = layer.kv_seq_len before the call) and attends to the whole cache as it stood plus chunk tokens 0..i (causal, always);
+    `attention_mask`: optional additive (B, 1, Q, P0 + Q) fp16 mask on top.  Mutates `layer` in place -- afterwards it is
+    bit-identical to Q decode steps fed the same keys and values -- and returns (B, nh, Q, D) fp16."""
+    return layer.extend(q, k, v, attention_mask, out)
+
+
 def _attention_decode(query_states, key_states, value_states, layer: KiviLayerCache, attention_mask, fused_kernels, out):
     cfg = layer.cfg
     B, nh, q_len, D = query_states.shape
@@ -434,10 +444,13 @@ class LlamaAttention_KIVI(nn.Module):
                         f"advanced to {layer.kv_seq_len}. In-place cache tuples are single-use; clone the cache "
                         f"(KiviLayerCache.clone()) to continue one prefix twice.")
             elif _mf_supported(self.kivi, self.head_dim, self.num_heads, self.num_key_value_heads):
-                layer = KiviLayerCacheMF.from_tuple(self.kivi, past_key_value, self._capacity(past_len + 1), self.num_heads)
+                layer = KiviLayerCacheMF.from_tuple(self.kivi, past_key_value, self._capacity(past_len + q_len), self.num_heads)
             else:  # a plain reference-style tuple: adopt it once
-                layer = KiviLayerCache.from_tuple(self.kivi, past_key_value, self._capacity(past_len + 1))
-            attn_output = kivi_attention_decode(q, k, v, layer, attention_mask)
+                layer = KiviLayerCache.from_tuple(self.kivi, past_key_value, self._capacity(past_len + q_len))
+            if q_len > 1:
+                attn_output = kivi_attention_extend(q, k, v, layer, attention_mask)
+            else:
+                attn_output = kivi_attention_decode(q, k, v, layer, attention_mask)
         else:
             layer = make_layer_cache(self.kivi, bsz, self.num_key_value_heads, self.head_dim, self._capacity(q_len),
                                      hidden_states.device, q.dtype, num_heads=self.num_heads)

@@ -308,6 +308,67 @@ class KiviLayerCache:
             self.v_res_start += 1
             self.v_res_len -= 1
 
+    # ------------------------------------------------------------------ multi-token extend (untuned)
+    def extend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
+               attention_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Q >= 1 new tokens over this cache: the contract of KiviLayerCacheMF.extend (chunk row i attends to the cache as it stands
+        plus chunk tokens 0..i; per row the rounding sequence of one decode step) for the shapes the matrix pipe does not cover.
+        The UNTUNED path: composed from torch ops on the GPU (fp32 dequantisation of the packed prefix, fp32 matmuls rounded to
+        fp16 where the hook rounds), then the cache bookkeeping of Q decode steps through append / flush, one token at a time."""
+        import math
+        cfg = self.cfg
+        B, nh, Q, D = query_states.shape
+        assert B == self.B and D == self.D and Q >= 1 and nh % self.nh_kv == 0
+        assert self.kv_seq_len > 0, "extend needs a cache: run the prompt pass first"
+        self.ensure_room(Q)
+        ratio, P0 = nh // self.nh_kv, self.kv_seq_len
+        total = P0 + Q
+
+        def heads(x):
+            return x if ratio == 1 else x.repeat_interleave(ratio, dim=1)
+
+        def deq(code, scale, mn, bits):            # groups along the last dim, fp32 scale * code + zero
+            fpi = 32 // bits
+            sh = torch.arange(fpi, device=code.device, dtype=torch.int32) * bits
+            c = ((code.unsqueeze(-1) >> sh) & (2 ** bits - 1)).reshape(*code.shape[:-1], code.shape[-1] * fpi).float()
+            g = cfg.group_size
+            lead, T = c.shape[:-1], c.shape[-1]
+            return (c.view(*lead, T // g, g) * scale.float().unsqueeze(-1) + mn.float().unsqueeze(-1)).view(*lead, T)
+
+        qf = query_states.float()
+        parts = []
+        kc, ks, km = self.k_quant_reference_layout()
+        if kc is not None:
+            parts.append(torch.matmul(qf, heads(deq(kc, ks, km, cfg.k_bits))).half())                 # (B, nh, Q, Tq)
+        kfull = torch.cat([x for x in (self.k_res_view(), key_states) if x is not None], 2)
+        parts.append(torch.matmul(qf, heads(kfull).float().transpose(2, 3)).half())
+        w = torch.cat(parts, -1) / math.sqrt(D)
+        if attention_mask is not None:
+            if attention_mask.size() != (B, 1, Q, total):
+                raise ValueError(f"Attention mask should be of size {(B, 1, Q, total)}, but is {attention_mask.size()}")
+            w = w + attention_mask
+            w = torch.max(w, torch.tensor(torch.finfo(w.dtype).min, device=w.device, dtype=w.dtype))
+        causal = torch.ones((Q, Q), dtype=torch.bool, device=w.device).triu(1)
+        w = w.float()
+        w[..., P0:] = w[..., P0:].masked_fill(causal, float("-inf"))
+        p = torch.softmax(w, dim=-1).half()
+        vfull = torch.cat([self.v_res_view(), value_states], 2)
+        Tv = self.v_quant_len
+        res = torch.matmul(p[..., Tv:].float(), heads(vfull).float()).half()
+        if Tv:
+            vc, vs, vm = self.v_quant_views()
+            res = torch.matmul(p[..., :Tv].float(), heads(deq(vc, vs, vm, cfg.v_bits))).half() + res
+        for i in range(Q):                         # llama_kivi.py:333-356, :377-399 per token
+            self.append_k(key_states[:, :, i: i + 1])
+            self.maybe_flush_k()
+            self.append_v(value_states[:, :, i: i + 1])
+            self.maybe_flush_v()
+            self.kv_seq_len += 1
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+
     # ------------------------------------------------------------------ import of a plain reference tuple
     @classmethod
     def from_tuple(cls, cfg: KiviConfig, past, max_len: int) -> "KiviLayerCache":

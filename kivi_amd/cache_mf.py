@@ -287,6 +287,44 @@ class KiviLayerCacheMF:
         return out
 
 
+    # ------------------------------------------------------------------ multi-token extend
+    def extend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
+               attention_mask: torch.Tensor = None, out: torch.Tensor = None) -> torch.Tensor:
+        """Q >= 1 new tokens in ONE library call (kivi_mf_extend_layer): q (B, nh, Q, D), k / v (B, nh_kv, Q, D), RoPE applied.
+        Chunk row i attends to the cache as it stands plus chunk tokens 0..i; `attention_mask`: optional additive
+        (B, 1, Q, kv_seq_len + Q) fp16.  The cache afterwards is bit-identical to Q decode steps.  Returns (B, nh, Q, D) fp16."""
+        B, nh, Q, D = query_states.shape
+        assert nh == self.nh and B == self.B and D == self.D and Q >= 1
+        assert key_states.shape == value_states.shape == (B, self.nh_kv, Q, D)
+        assert self.kv_seq_len > 0, "extend needs a cache: run the prompt pass first"
+        self.ensure_room(Q)
+        q, k, v = _rows16(query_states), _rows16(key_states), _rows16(value_states)
+        total = self.kv_seq_len + Q
+        mask_ptr, mask_sb, mask_sq = None, 0, 0
+        if attention_mask is not None:
+            if attention_mask.size() != (B, 1, Q, total):
+                raise ValueError(f"Attention mask should be of size {(B, 1, Q, total)}, but is {attention_mask.size()}")
+            assert attention_mask.dtype == torch.float16
+            if attention_mask.stride(3) != 1 or attention_mask.stride(0) < Q * attention_mask.stride(2):
+                attention_mask = attention_mask.contiguous()
+            mask_ptr, mask_sb, mask_sq = attention_mask.data_ptr(), attention_mask.stride(0), attention_mask.stride(2)
+        if out is None:
+            out = torch.empty((B, nh, Q, D), dtype=torch.float16, device=q.device)
+        else:
+            assert out.shape == (B, nh, Q, D) and out.dtype == torch.float16 and out.stride(3) == 1
+        d, state, key, _, _ = self._desc(nh, q.device)
+        d.flags = self._flags()
+        state[0], state[1], state[2] = self.k_quant_len, self.k_res_len, self.v_quant_len
+        state[3], state[4], state[5] = self.v_res_start, self.v_res_len, self.kv_seq_len
+        rc = _lib.load().kivi_mf_extend_layer(ctypes.byref(d), state, Q, q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), nh,
+                                              k.data_ptr(), k.stride(0), k.stride(1), k.stride(2), v.data_ptr(), v.stride(0),
+                                              v.stride(1), v.stride(2), mask_ptr, mask_sb, mask_sq, out.data_ptr(), out.stride(0),
+                                              out.stride(1), out.stride(2), key[1])
+        _lib.check(rc, "kivi_mf_extend_layer")
+        self.k_quant_len, self.k_res_len, self.v_quant_len = state[0], state[1], state[2]
+        self.v_res_start, self.v_res_len, self.kv_seq_len = state[3], state[4], state[5]
+        return out
+
     # ------------------------------------------------------------------ device-resident lengths (hipGraph capture; kivi_amd/graph.py)
     def host_step(self) -> "_lib.MfStep":
         """The six lengths of the NEXT decode step as a kivi_mf_step (include/kivi_hip.h)."""

@@ -111,9 +111,11 @@ class LlamaForCausalLM_KIVI(nn.Module):
         return self.lm_head(self.model.norm(x)), new
 
     @torch.no_grad()
-    def generate(self, input_ids: torch.LongTensor, max_new_tokens: int) -> torch.LongTensor:
-        """Greedy decoding of equal-length prompts (the recipe of the reference's mem_spd_test.py / example.py)."""
-        logits, pasts = self.forward(input_ids)
+    def generate(self, input_ids: torch.LongTensor, max_new_tokens: int, past_key_values: Optional[List] = None) -> torch.LongTensor:
+        """Greedy decoding of equal-length prompts (the recipe of the reference's mem_spd_test.py / example.py).  With
+        `past_key_values` (the caches of an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one
+        pass (kivi_attention_extend) and decoding continues from there; the caches are advanced in place."""
+        logits, pasts = self.forward(input_ids, past_key_values)
         out = [input_ids]
         tok = logits.argmax(-1)
         for _ in range(max_new_tokens):
