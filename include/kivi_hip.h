@@ -491,13 +491,15 @@ int kivi_mf_decode_layer_dyn(const kivi_mf_layer_desc* layer, const kivi_mf_step
  * applied; rows addressed as base + b*sb + h*sh + i*st, 16-byte aligned), out (B, nh, Q, D).  Chunk row i sits at position
  * P0 + i (P0 = state[5]) and attends to the whole cache as it stood before the call (packed K / V, the K residual, the V window) and
  * to chunk tokens 0..i (causal, always); `mask` (optional) is an additive fp16 mask, row i of batch b at mask + b*mask_sb +
- * i*mask_sq, P0 + Q keys (mask_sq >= P0 + Q).  Per row the arithmetic of one decode step (llama_kivi.py:314-399): fp32 sums of
+ * i*mask_sq, P0 + Q keys (mask_sq >= P0 + Q); mask_sq == 0 broadcasts one key row per batch row to all Q chunk rows (a padding
+ * mask: mask_sb >= P0 + Q, bit-identical to the same row written out Q times; the kernel reads it per row as it reads a full mask).  Per row the arithmetic of one decode step (llama_kivi.py:314-399): fp32 sums of
  * q * (scale * code + zero), fp16 scores / sqrt(D) in fp16, + mask, fp32 softmax, fp16 probabilities, fp16(fp16(packed sV) +
  * fp16(fp16 sV)) (the kernel reads the keys twice: the row's softmax statistics, then the probabilities).  In stream order: the attention launch, the K flushes (the residual filled to R and
  * packed with kivi_kt_pack, whole R-runs packed straight from knew, the rest copied into the residual), kivi_vt_pack_at of the
  * values that leave the window, the new window rows.  The resulting cache (9-tuple and range words) is bit-identical to Q
  * kivi_mf_decode_layer steps fed the same keys and values.  Everything is validated before the first launch; `state` is written
- * once, at the end.  KIVI_EINVAL for Q < 1, a mask pitch below P0 + Q, a capacity below P0 + Q, inconsistent lengths.
+ * once, at the end.  KIVI_EINVAL for Q < 1, a mask pitch below P0 + Q (mask_sb when mask_sq == 0), a capacity below P0 + Q,
+ * inconsistent lengths.
  */
 int kivi_mf_extend_layer(const kivi_mf_layer_desc* layer, int64_t* state, int Q, const void* q, int64_t q_sb, int64_t q_sh,
                          int64_t q_st, int nh, const void* knew, int64_t kn_sb, int64_t kn_sh, int64_t kn_st, const void* vnew,

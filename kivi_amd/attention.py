@@ -255,7 +255,8 @@ def kivi_attention_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, lay
     """Q >= 1 new tokens for one layer that already holds a cache (multi-turn continuation, a prompt fed in pieces, a block of
     draft tokens).  q (B, nh, Q, D), k / v (B, nh_kv, Q, D) fp16, RoPE applied.  Chunk row i sits at position P0 + i
     (P0 = layer.kv_seq_len before the call) and attends to the whole cache as it stood plus chunk tokens 0..i (causal, always);
-    `attention_mask`: optional additive (B, 1, Q, P0 + Q) fp16 mask on top.  Mutates `layer` in place -- afterwards it is
+    `attention_mask`: optional additive (B, 1, Q, P0 + Q) fp16 mask on top (a padding row expanded over the chunk -- dim-2 stride 0 --
+    is read without being built).  Mutates `layer` in place -- afterwards it is
     bit-identical to Q decode steps fed the same keys and values -- and returns (B, nh, Q, D) fp16."""
     return layer.extend(q, k, v, attention_mask, out)
 

@@ -292,7 +292,8 @@ class KiviLayerCacheMF:
                attention_mask: torch.Tensor = None, out: torch.Tensor = None) -> torch.Tensor:
         """Q >= 1 new tokens in ONE library call (kivi_mf_extend_layer): q (B, nh, Q, D), k / v (B, nh_kv, Q, D), RoPE applied.
         Chunk row i attends to the cache as it stands plus chunk tokens 0..i; `attention_mask`: optional additive
-        (B, 1, Q, kv_seq_len + Q) fp16.  The cache afterwards is bit-identical to Q decode steps.  Returns (B, nh, Q, D) fp16."""
+        (B, 1, Q, kv_seq_len + Q) fp16 (a view with dim-2 stride 0 -- a padding row expanded over the chunk -- is read as it is,
+        without being built).  The cache afterwards is bit-identical to Q decode steps.  Returns (B, nh, Q, D) fp16."""
         B, nh, Q, D = query_states.shape
         assert nh == self.nh and B == self.B and D == self.D and Q >= 1
         assert key_states.shape == value_states.shape == (B, self.nh_kv, Q, D)
@@ -305,7 +306,11 @@ class KiviLayerCacheMF:
             if attention_mask.size() != (B, 1, Q, total):
                 raise ValueError(f"Attention mask should be of size {(B, 1, Q, total)}, but is {attention_mask.size()}")
             assert attention_mask.dtype == torch.float16
-            if attention_mask.stride(3) != 1 or attention_mask.stride(0) < Q * attention_mask.stride(2):
+            if attention_mask.stride(2) == 0:    # one key row per batch row, expanded over the chunk: passed as mask_sq = 0
+                if attention_mask.stride(3) != 1 or attention_mask.stride(0) < total:
+                    row = torch.empty((B, 1, 1, total), dtype=torch.float16, device=q.device)
+                    attention_mask = row.copy_(attention_mask[:, :, :1]).expand(B, 1, Q, total)
+            elif attention_mask.stride(3) != 1 or attention_mask.stride(0) < Q * attention_mask.stride(2):
                 attention_mask = attention_mask.contiguous()
             mask_ptr, mask_sb, mask_sq = attention_mask.data_ptr(), attention_mask.stride(0), attention_mask.stride(2)
         if out is None:

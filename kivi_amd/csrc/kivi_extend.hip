@@ -441,8 +441,10 @@ extern "C" int kivi_mf_extend_layer(const kivi_mf_layer_desc* L, int64_t* st, in
                  (long long)L->cap, (long long)kv, Q);
     KIVI_REQUIRE((L->flags & KIVI_GQA_WINDOW_RING) != 0 && L->v_window_rows >= R + 1 && wstart < L->v_window_rows, KIVI_EINVAL,
                  "kivi_mf_extend_layer: needs the ring window of >= R + 1 rows");
-    KIVI_REQUIRE(mask == nullptr || (mask_sq >= kv + Q && mask_sb >= (int64_t)Q * mask_sq), KIVI_EINVAL,
-                 "kivi_mf_extend_layer: mask rows of %lld halves cannot hold %lld keys", (long long)mask_sq, (long long)(kv + Q));
+    // mask_sq == 0: one key row per batch row, shared by all Q chunk rows (a padding mask; causality is applied below regardless)
+    KIVI_REQUIRE(mask == nullptr || (mask_sq == 0 ? mask_sb >= kv + Q : mask_sq >= kv + Q && mask_sb >= (int64_t)Q * mask_sq), KIVI_EINVAL,
+                 "kivi_mf_extend_layer: mask rows of %lld halves cannot hold %lld keys", (long long)(mask_sq ? mask_sq : mask_sb),
+                 (long long)(kv + Q));
     const int sbw = L->bits == 4 ? KIVI_MF4_SB_WORDS : KIVI_MF_SB_WORDS;
     KIVI_REQUIRE((uintptr_t)L->kt % 16 == 0 && (uintptr_t)L->vt % 16 == 0 && L->kt_sb % 4 == 0 && L->kt_sh % 4 == 0 && L->kt_ss % 4 == 0 &&
                      L->vt_sb % 4 == 0 && L->vt_sh % 4 == 0 && L->vt_ss % 4 == 0 && L->kt_ss >= sbw && L->vt_ss >= sbw &&

@@ -68,9 +68,9 @@ class DecoderLayer_KIVI(nn.Module):
         self.input_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
         self.post_attention_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
 
-    def forward(self, x, past, attention_mask=None):
-        a, _, past = self.self_attn(self.input_layernorm(x), attention_mask=attention_mask, past_key_value=past,
-                                    use_cache=True)
+    def forward(self, x, past, attention_mask=None, position_ids=None):
+        a, _, past = self.self_attn(self.input_layernorm(x), attention_mask=attention_mask, position_ids=position_ids,
+                                    past_key_value=past, use_cache=True)
         x = x + a
         return x + self.mlp(self.post_attention_layernorm(x)), past
 
@@ -83,9 +83,53 @@ class _Body(nn.Module):
         self.norm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
 
 
+_MIN16 = torch.finfo(torch.float16).min
+
+
+def left_pad(seqs, pad_token_id: int = 0, device=None):
+    """A list of token id sequences -> (ids (B, T), mask (B, T)) left-padded to the longest one (HF's tokenizer with
+    padding_side="left"): mask is 1 on real tokens, 0 on the `pad_token_id` fillers."""
+    seqs = [torch.as_tensor(s, dtype=torch.long).flatten() for s in seqs]
+    T = max(len(s) for s in seqs)
+    ids = torch.full((len(seqs), T), pad_token_id, dtype=torch.long)
+    mask = torch.zeros((len(seqs), T), dtype=torch.long)
+    for i, s in enumerate(seqs):
+        if len(s):
+            ids[i, T - len(s):] = s
+            mask[i, T - len(s):] = 1
+    return ids.to(device), mask.to(device)
+
+
+def padding_position_ids(mask: torch.Tensor, q_len: int) -> torch.LongTensor:
+    """HF's prepare_inputs_for_generation: positions cumsum(mask) - 1, pads at 1; the last `q_len` columns."""
+    m = mask.long()
+    pos = m.cumsum(-1) - 1
+    return pos.masked_fill_(m == 0, 1)[:, -q_len:]
+
+
+def padding_key_row(mask: torch.Tensor, length: Optional[int] = None) -> torch.Tensor:
+    """(B, 1, 1, length) additive fp16 key row of a 2D padding mask: 0 on real tokens, finfo(fp16).min on pads (columns past
+    the mask: 0).  Decode steps read views of it; an extend reads it expanded over the chunk."""
+    B, L = mask.shape
+    row = torch.zeros((B, 1, 1, length or L), dtype=torch.float16, device=mask.device)
+    row[..., :L].masked_fill_((mask == 0)[:, None, None, :], _MIN16)
+    return row
+
+
+def padding_prompt_mask(mask: torch.Tensor) -> torch.Tensor:
+    """HF's 4D causal + padding additive mask of a prompt pass (_prepare_4d_causal_attention_mask): (B, 1, T, T) fp16."""
+    B, T = mask.shape
+    causal = torch.full((T, T), _MIN16, dtype=torch.float16, device=mask.device).triu(1)
+    return causal[None, None].repeat(B, 1, 1, 1).masked_fill_((mask == 0)[:, None, None, :], _MIN16)
+
+
 class LlamaForCausalLM_KIVI(nn.Module):
     """`past_key_values` is a list with one entry per layer: None before the prompt pass, afterwards the 9-tuple of
-    models/llama_kivi.py:454-455 (here the lazy KiviCacheTuple over the in-place cache)."""
+    models/llama_kivi.py:454-455 (here the lazy KiviCacheTuple over the in-place cache).
+
+    Prompts of different lengths are left-padded (`left_pad`) and described by HF's 2D mask (1 = real token): `padding_mask`
+    of forward(), `attention_mask` of generate() / generate_graphed() / decode_graphed().  Pads are ordinary cache tokens
+    that every query masks; a mask without a pad takes the unmasked path unchanged."""
 
     def __init__(self, config, attention_cls=LlamaAttention_KIVI):
         super().__init__()
@@ -97,30 +141,89 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     @torch.no_grad()
     def forward(self, input_ids: torch.LongTensor, past_key_values: Optional[List] = None, attention_mask=None,
-                last_token_only: bool = True):
+                last_token_only: bool = True, padding_mask: Optional[torch.Tensor] = None):
         """logits (B, 1 or T, vocab), new past_key_values.  `attention_mask`: the reference's additive (B, 1, 1, kv_len)
-        fp16 mask for decode steps (llama_kivi.py:364-372); the prompt pass is causal over equal-length prompts."""
+        fp16 mask for decode steps (llama_kivi.py:364-372); with it the prompt pass is causal over equal-length prompts.
+        `padding_mask`: HF's 2D mask (B, past + T) of 0 / 1 (1 = real token) over the history and `input_ids` -- positions
+        and the additive masks of every pass are derived from it (not together with `attention_mask`)."""
+        if padding_mask is None:
+            return self._forward(input_ids, past_key_values, attention_mask, None, last_token_only, False)
+        if attention_mask is not None:
+            raise ValueError("pass either the 4D additive attention_mask or the 2D padding_mask, not both")
+        past_len = self._past_len(past_key_values)
+        if not self._padded(padding_mask, input_ids.shape[0], past_len + input_ids.shape[1], past_len):
+            return self._forward(input_ids, past_key_values, None, None, last_token_only, False)
+        T = input_ids.shape[1]
+        if past_len == 0:
+            mask = padding_prompt_mask(padding_mask)
+        else:
+            mask = padding_key_row(padding_mask).expand(-1, -1, T, -1)
+        return self._forward(input_ids, past_key_values, mask, padding_position_ids(padding_mask, T), last_token_only, True)
+
+    def _forward(self, input_ids, past_key_values, attention_mask, position_ids, last_token_only, mask_prompt):
         pasts = past_key_values or [None] * len(self.model.layers)
         x = self.model.embed_tokens(input_ids)
         new = []
         for layer, past in zip(self.model.layers, pasts):
-            x, p = layer(x, past, attention_mask if past is not None else None)
+            x, p = layer(x, past, attention_mask if past is not None or mask_prompt else None, position_ids)
             new.append(p)
         if last_token_only:
             x = x[:, -1:]
         return self.lm_head(self.model.norm(x)), new
 
+    @staticmethod
+    def _past_len(past_key_values) -> int:
+        return int(past_key_values[0][-1]) if past_key_values and past_key_values[0] is not None else 0
+
+    def _padded(self, mask: torch.Tensor, B: int, length: int, past_len: int) -> bool:
+        """Validate a 2D padding mask; True when it holds a pad (False: the caller takes the unmasked path, no mask is built)."""
+        if mask.dim() != 2 or tuple(mask.shape) != (B, length):
+            raise ValueError(f"the 2D attention / padding mask should be of size {(B, length)} (history + new tokens), "
+                             f"but is {tuple(mask.shape)}")
+        if bool((mask != 0).all()):
+            return False
+        if past_len == 0 and not all(layer.self_attn._prefill_uses_mask for layer in self.model.layers):
+            raise ValueError(f"{type(self.model.layers[0].self_attn).__name__}: the prompt pass of this attention class ignores "
+                             f"masks (llama_kivi.py:420-423), so padded prompts cannot be run; use the eager class")
+        return True
+
     @torch.no_grad()
-    def generate(self, input_ids: torch.LongTensor, max_new_tokens: int, past_key_values: Optional[List] = None) -> torch.LongTensor:
-        """Greedy decoding of equal-length prompts (the recipe of the reference's mem_spd_test.py / example.py).  With
-        `past_key_values` (the caches of an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one
-        pass (kivi_attention_extend) and decoding continues from there; the caches are advanced in place."""
-        logits, pasts = self.forward(input_ids, past_key_values)
+    def generate(self, input_ids: torch.LongTensor, max_new_tokens: int, past_key_values: Optional[List] = None,
+                 attention_mask: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
+                 pad_token_id: Optional[int] = None) -> torch.LongTensor:
+        """Greedy decoding (the recipe of the reference's mem_spd_test.py / example.py).  With `past_key_values` (the caches of
+        an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one pass (kivi_attention_extend) and
+        decoding continues from there; the caches are advanced in place.  `attention_mask`: HF's 2D mask (B, past + T) of
+        left-padded prompts (1 = real token; with `past_key_values` it covers the history and the new turn).  A row that has
+        produced `eos_token_id` emits `pad_token_id` from then on; the loop stops when every row has finished."""
+        if eos_token_id is not None and pad_token_id is None:
+            raise ValueError("eos_token_id needs a pad_token_id for the rows that have finished")
+        B, T = input_ids.shape
+        past_len = self._past_len(past_key_values)
+        pos = row = None
+        if attention_mask is not None and self._padded(attention_mask, B, past_len + T, past_len):
+            # one additive key row per request; every decode step reads a view one column longer (new tokens are real)
+            row = padding_key_row(attention_mask, past_len + T + max_new_tokens)
+            mask = padding_prompt_mask(attention_mask) if past_len == 0 else row[..., : past_len + T].expand(-1, -1, T, -1)
+            logits, pasts = self._forward(input_ids, past_key_values, mask, padding_position_ids(attention_mask, T), True, True)
+            pos = attention_mask.long().sum(-1, keepdim=True)          # (B, 1): position of the next token
+        else:
+            logits, pasts = self.forward(input_ids, past_key_values)
         out = [input_ids]
         tok = logits.argmax(-1)
-        for _ in range(max_new_tokens):
+        live = None if eos_token_id is None else torch.ones((B, 1), dtype=torch.bool, device=tok.device)
+        for s in range(max_new_tokens):
+            if live is not None:
+                tok = torch.where(live, tok, torch.full_like(tok, pad_token_id))
+                live = live & (tok != eos_token_id)
             out.append(tok)
-            logits, pasts = self.forward(tok, pasts)
+            if live is not None and not bool(live.any()):
+                break
+            if row is None:
+                logits, pasts = self.forward(tok, pasts)
+            else:
+                logits, pasts = self._forward(tok, pasts, row[..., : past_len + T + s + 1], pos, True, True)
+                pos = pos + 1
             tok = logits.argmax(-1)
         return torch.cat(out, dim=1)
 
@@ -132,16 +235,20 @@ class LlamaForCausalLM_KIVI(nn.Module):
     # kivi_decode_layer call per layer (its lengths change every step).  Same kernels, same results as forward().
     # Round 4: when every layer's cache is in the matrix-pipe layout the attention launches read their lengths from device
     # memory (kivi_amd/graph.py), so the WHOLE step -- dense parts and attention of all layers -- is ONE graph (whole=True).
-    def _build_graphs(self, B: int, device, whole: bool = False):
+    # Padded batches (padded=True): cos / sin hold one position per row, and `mask` is a static additive (B, 1, 1, pitch) fp16
+    # buffer, pitch >= the cache capacity, that the attention of every step reads (its new column is 0: new tokens are real).
+    def _build_graphs(self, B: int, device, whole: bool = False, padded: bool = False):
         cfg = self.config
         nh, nkv = cfg.num_attention_heads, cfg.num_key_value_heads
         D, H = self.model.layers[0].self_attn.head_dim, cfg.hidden_size
         dt = self.lm_head.weight.dtype
+        rows = B if padded else 1
         g = SimpleNamespace(B=B, tok=torch.zeros((B, 1), dtype=torch.long, device=device),
-                            cos=torch.zeros((1, 1, 1, D), dtype=dt, device=device),
-                            sin=torch.zeros((1, 1, 1, D), dtype=dt, device=device),
+                            cos=torch.zeros((rows, 1, 1, D), dtype=dt, device=device),
+                            sin=torch.zeros((rows, 1, 1, D), dtype=dt, device=device),
                             x=[torch.zeros((B, 1, H), dtype=dt, device=device) for _ in range(len(self.model.layers) + 1)],
-                            attn=torch.zeros((B, nh, 1, D), dtype=dt, device=device), qkv=[], pre=[], post=[], whole=whole)
+                            attn=torch.zeros((B, nh, 1, D), dtype=dt, device=device), qkv=[], pre=[], post=[], whole=whole,
+                            padded=padded, mask=None, pos=None)
 
         def rot(t):
             return torch.cat((-t[..., D // 2:], t[..., : D // 2]), dim=-1)
@@ -191,25 +298,61 @@ class LlamaForCausalLM_KIVI(nn.Module):
         g.tok.zero_()
         return g
 
-    def prepare_graphs(self, batch: int, device, whole: bool = False) -> None:
+    def prepare_graphs(self, batch: int, device, whole: bool = False, padded: bool = False) -> None:
         """Capture the decode graphs for this batch size now (otherwise on the first graphed step)."""
         g = getattr(self, "_graphs", None)
-        if g is None or g.B != batch or g.whole != whole:
-            self._graphs = self._build_graphs(batch, device, whole)
+        if g is None or g.B != batch or g.whole != whole or g.padded != padded:
+            self._graphs = self._build_graphs(batch, device, whole, padded)
+
+    @staticmethod
+    def _mask_room(g, caches, whole: bool) -> bool:
+        """Room for one more token in every cache and a mask buffer as wide as their capacity (the whole-step graph: the tokens
+        the stores can hold, so that the buffer moves only when the stores do).  True when the buffer was reallocated."""
+        from .cache_mf import SB
+        for c in caches:
+            c.ensure_room(1)
+        need = caches[0].n_sb * SB if whole else ((caches[0].cap + 7) // 8) * 8
+        if g.mask is not None and g.mask.shape[3] >= need:
+            return False
+        new = torch.zeros((g.B, 1, 1, need), dtype=torch.float16, device=g.tok.device)
+        if g.mask is not None:
+            new[..., : g.mask.shape[3]].copy_(g.mask)
+        g.mask = new
+        return True
+
+    def _rope_rows(self, g) -> None:
+        """cos / sin of the per-row positions g.pos (B,), as LlamaAttention_KIVI._rope computes them; then the positions advance."""
+        inv_freq = self.model.layers[0].self_attn.inv_freq
+        freqs = g.pos[:, None].float() * inv_freq[None, :].float()
+        emb = torch.cat((freqs, freqs), dim=-1)
+        g.cos.copy_(emb.cos().view(g.B, 1, 1, -1))
+        g.sin.copy_(emb.sin().view(g.B, 1, 1, -1))
+        g.pos += 1
 
     @torch.no_grad()
-    def decode_graphed(self, tok: torch.LongTensor, past_key_values: List, position: int, steps: int) -> torch.LongTensor:
+    def decode_graphed(self, tok: torch.LongTensor, past_key_values: List, position: int, steps: int,
+                       attention_mask: Optional[torch.Tensor] = None) -> torch.LongTensor:
         """`steps` greedy decode steps from token `tok` (B, 1) at position `position` with the dense part replayed from
         hipGraphs; the caches in `past_key_values` are advanced in place.  Returns the (B, steps) tokens fed to the model
-        (tok first); the token following them is left in the graph's token buffer (`self._graphs.tok`)."""
+        (tok first); the token following them is left in the graph's token buffer (`self._graphs.tok`).
+        `attention_mask`: HF's 2D mask (B, kv_len + 1) over the cached tokens and `tok` (1 = real token); with a pad in it
+        every row takes its own position from the mask (`position` is not used) and the pads are masked in every step."""
         from .attention import kivi_attention_decode
         from .cache_mf import KiviLayerCacheMF
         caches = [p.layer for p in past_key_values]
         whole = all(isinstance(c, KiviLayerCacheMF) for c in caches)
-        self.prepare_graphs(tok.shape[0], tok.device, whole)
+        B, kv0 = tok.shape[0], caches[0].kv_seq_len
+        padded = attention_mask is not None and self._padded(attention_mask, B, kv0 + 1, kv0)
+        self.prepare_graphs(B, tok.device, whole, padded)
         g = self._graphs
         attn0 = self.model.layers[0].self_attn
         g.tok.copy_(tok)
+        if padded:
+            if self._mask_room(g, caches, whole):
+                self._graphed = None             # a graph captured over the old buffer is stale
+            g.mask.zero_()
+            g.mask[..., : kv0 + 1].masked_fill_((attention_mask == 0)[:, None, None, :], _MIN16)
+            g.pos = attention_mask.long().sum(-1) - 1                    # (B,): position of `tok`
         out = []
         if whole:
             from .graph import GraphedDecode, MfStepDriver
@@ -227,40 +370,55 @@ class LlamaForCausalLM_KIVI(nn.Module):
                 def body():
                     for i in range(len(self.model.layers)):
                         g.pre_fn(i)
-                        drv.enqueue(i, *g.qkv[i], g.attn)
+                        drv.enqueue(i, *g.qkv[i], g.attn, g.mask)
                         g.post_fn(i)
 
                 gd = GraphedDecode(drv, body)
                 self._graphed = (g, drv, gd)
             for _ in range(steps):
                 out.append(g.tok.clone())
-                freqs = position * attn0.inv_freq.float()
-                emb = torch.cat((freqs, freqs), dim=-1)
-                g.cos.copy_(emb.cos().view(1, 1, 1, -1))
-                g.sin.copy_(emb.sin().view(1, 1, 1, -1))
+                if padded:
+                    self._rope_rows(g)
+                    if self._mask_room(g, caches, whole):     # the stores grew: so did the buffer, capture again
+                        gd.graph, gd.warm = None, False
+                else:
+                    freqs = position * attn0.inv_freq.float()
+                    emb = torch.cat((freqs, freqs), dim=-1)
+                    g.cos.copy_(emb.cos().view(1, 1, 1, -1))
+                    g.sin.copy_(emb.sin().view(1, 1, 1, -1))
                 gd.step()
                 position += 1
             self._last_graph_stats = (gd.eager, gd.captures, gd.replays)
             return torch.cat(out, dim=1)
         for _ in range(steps):
             out.append(g.tok.clone())
-            freqs = position * attn0.inv_freq.float()
-            emb = torch.cat((freqs, freqs), dim=-1)
-            g.cos.copy_(emb.cos().view(1, 1, 1, -1))
-            g.sin.copy_(emb.sin().view(1, 1, 1, -1))
+            mask = None
+            if padded:
+                self._rope_rows(g)
+                self._mask_room(g, caches, whole)
+                mask = g.mask[..., : caches[0].kv_seq_len + 1]
+            else:
+                freqs = position * attn0.inv_freq.float()
+                emb = torch.cat((freqs, freqs), dim=-1)
+                g.cos.copy_(emb.cos().view(1, 1, 1, -1))
+                g.sin.copy_(emb.sin().view(1, 1, 1, -1))
             for i in range(len(self.model.layers)):
                 g.pre[i].replay()
                 q, k, v = g.qkv[i]
-                kivi_attention_decode(q, k, v, caches[i], out=g.attn)
+                kivi_attention_decode(q, k, v, caches[i], attention_mask=mask, out=g.attn)
                 g.post[i].replay()
             position += 1
         return torch.cat(out, dim=1)
 
     @torch.no_grad()
-    def generate_graphed(self, input_ids: torch.LongTensor, max_new_tokens: int) -> torch.LongTensor:
-        """generate() with the dense part of every decode step replayed from hipGraphs (see _build_graphs)."""
-        logits, pasts = self.forward(input_ids)
-        new = self.decode_graphed(logits.argmax(-1), pasts, input_ids.shape[1], max_new_tokens)
+    def generate_graphed(self, input_ids: torch.LongTensor, max_new_tokens: int,
+                         attention_mask: Optional[torch.Tensor] = None) -> torch.LongTensor:
+        """generate() with the dense part of every decode step replayed from hipGraphs (see _build_graphs).
+        `attention_mask`: HF's 2D (B, T) mask of left-padded prompts (1 = real token)."""
+        logits, pasts = self.forward(input_ids, padding_mask=attention_mask)
+        if attention_mask is not None:
+            attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, :1])], dim=1)
+        new = self.decode_graphed(logits.argmax(-1), pasts, input_ids.shape[1], max_new_tokens, attention_mask)
         self._graphed = None        # the caches of this request die with it: so does the graph captured over them
         return torch.cat([input_ids, new], dim=1)
 
