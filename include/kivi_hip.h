@@ -27,6 +27,7 @@
  *                               hipGraph form kivi_mf_decode_layer_dyn + kivi_mf_step_* (matrix-pipe cache: g = 32, D = 128,
  *                               2-bit with nh / nh_kv in {1, 4, 8} or 4-bit with nh / nh_kv in {1, 4}), with the packers of that
  *                               cache: kivi_kt_pack, kivi_vt_pack, kivi_vt_pack_at, kivi_kt_relayout, kivi_vt_relayout
+ *               beam search:    kivi_cache_reorder (in-place row reorder of either cache layout, from a fork point on)
  *   BUILDING BLOCKS (what the layer steps are composed of; exported for tests, tools and callers that keep their own cache
  *               bookkeeping -- same contracts, but no stability promise beyond the ABI version):  kivi_gemv_k_paged,
  *               kivi_decode_scores, kivi_softmax_scaled, kivi_decode_output, kivi_decode_softmax_output, kivi_decode_attend,
@@ -505,6 +506,29 @@ int kivi_mf_extend_layer(const kivi_mf_layer_desc* layer, int64_t* state, int Q,
                          int64_t q_st, int nh, const void* knew, int64_t kn_sb, int64_t kn_sh, int64_t kn_st, const void* vnew,
                          int64_t vn_sb, int64_t vn_sh, int64_t vn_st, const void* mask, int64_t mask_sb, int64_t mask_sq, void* out,
                          int64_t out_sb, int64_t out_sh, int64_t out_st, kivi_stream_t stream);
+/*
+ * kivi_cache_reorder: row[b] <- row[idx[b]] IN PLACE, for every byte range the slabs name (beam search: HF's
+ * _reorder_cache, models/llama_kivi.py:951-957, without the copy of the whole cache).  Rows come in groups of `group`
+ * consecutive rows and idx[b] must lie in b's group (beam search: group = num_beams; an arbitrary reorder: group = B).  `idx`: B
+ * int32 (idx_bytes 4) or int64 (8) indices in DEVICE memory, read on the device (never copied to the host); an index outside its
+ * group leaves the row as it is.  A slab is one store of one layer, restricted to what has to move: byte (i0, i1, i2, j) of row b is
+ * base + b*row_stride + i0*stride[0] + i1*stride[1] + i2*stride[2] + j, j < run, i_k < n[k].  Slabs and their pieces must not
+ * overlap.  Base, strides and run are multiples of 16 bytes (16-byte moves) or of 4 (word moves).  One launch: a workgroup loads a
+ * chunk of every row its group sources into LDS, then writes the rows whose index differs from their own; identity rows nobody
+ * sources are not touched.  KIVI_EINVAL (before anything is enqueued) for group < 1 or > KIVI_REORDER_MAX_GROUP, B not a multiple of
+ * group, a null or misaligned idx, more than KIVI_REORDER_MAX_SLABS slabs, negative counts, a null base or 4-byte misalignment.
+ */
+#define KIVI_REORDER_MAX_SLABS 32
+#define KIVI_REORDER_MAX_GROUP 1024
+typedef struct kivi_reorder_slab {
+    void* base;
+    int64_t row_stride;
+    int64_t n[3];
+    int64_t stride[3];
+    int64_t run;
+} kivi_reorder_slab;
+int kivi_cache_reorder(const kivi_reorder_slab* slabs, int n_slabs, int B, int group, const void* idx, int idx_bytes,
+                       kivi_stream_t stream);
 /* geometry class of a step (-1: bad arguments): the super-block counts of both stores and whether the step flushes a value; the
  * launch plan (one launch / S slices / two launches) is a function of the class and of constants of the call (shape, bits, flags) */
 int64_t kivi_mf_step_key(const kivi_mf_step* step, int B, int nh, int nh_kv, int residual_length, int flags);

@@ -119,6 +119,15 @@ class MfLayerDesc(ctypes.Structure):
     ]
 
 
+REORDER_MAX_SLABS = 32    # include/kivi_hip.h: KIVI_REORDER_MAX_SLABS
+REORDER_MAX_GROUP = 1024
+
+
+class ReorderSlab(ctypes.Structure):
+    """kivi_reorder_slab (include/kivi_hip.h): byte (i0, i1, i2, j) of row b at base + b*row_stride + sum(i_k*stride[k]) + j."""
+    _fields_ = [("base", _vp), ("row_stride", _i64), ("n", _i64 * 3), ("stride", _i64 * 3), ("run", _i64)]
+
+
 # name -> (restype, argtypes); must list every symbol include/kivi_hip.h declares
 SIGNATURES = {
     "kivi_abi_version": (_i32, []),
@@ -167,6 +176,7 @@ SIGNATURES = {
     "kivi_mf_extend_layer": (_i32, [ctypes.POINTER(MfLayerDesc), ctypes.POINTER(_i64), _i32, _vp, _i64, _i64, _i64, _i32, _vp, _i64,
                                     _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "kivi_vt_pack_at": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _i32, _i64, _i32, _i32, _i32, _vp]),
+    "kivi_cache_reorder": (_i32, [ctypes.POINTER(ReorderSlab), _i32, _i32, _i32, _vp, _i32, _vp]),
     "kivi_mf_step_key": (_i64, [ctypes.POINTER(MfStep), _i32, _i32, _i32, _i32, _i32]),
     "kivi_mf_step_advance": (_i32, [ctypes.POINTER(MfStep), _i32, _i64]),
     "kivi_mf_step_upload": (_i32, [ctypes.POINTER(MfStep), _vp, _vp]),

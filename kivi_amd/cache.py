@@ -171,6 +171,65 @@ class KiviLayerCache:
             other.__dict__.pop(name, None)
         return other
 
+    # ------------------------------------------------------------------ beam search
+    def reorder_(self, idx, group: Optional[int] = None, from_token: int = 0, check: bool = True) -> "KiviLayerCache":
+        """row[b] <- row[idx[b]] in place (one kivi_cache_reorder launch): `idx` (B,) int32 / int64, idx[b] in b's group of `group`
+        consecutive rows (default: B, an arbitrary reorder).  Only what was written from token `from_token` on moves -- rows of a
+        group must be identical before it (beams forked at that length); 0 moves the rows up to the lengths in use.  Buffers,
+        lengths and the native descriptors stay valid.  `check=False` skips the host-side check of the index values (a device
+        read): the kernel leaves a row whose index lies outside its group as it is."""
+        from . import reorder
+        group = self.B if group is None else int(group)
+        if not 0 <= int(from_token) <= self.kv_seq_len:
+            raise ValueError(f"from_token={from_token} lies beyond the cache length {self.kv_seq_len}")
+        idx = reorder.check_idx(idx, self.B, group, self.k_res.device, check)
+        reorder.run(self._reorder_slabs(int(from_token)), self.B, group, idx)
+        return self
+
+    def _reorder_slabs(self, from_token: int):
+        from .reorder import _span, slab
+        g, P, kf, h = self.cfg.group_size, self.page_tokens, 32 // self.cfg.k_bits, self.nh_kv
+        out = []
+        a, kq = from_token // g * g, self.k_quant_len           # the first K group that holds a token >= from_token
+        for p in range(a // P, (kq + P - 1) // P) if a < kq else ():
+            lo, hi = max(a, p * P) - p * P, min(kq, (p + 1) * P) - p * P
+            for x, per in ((self.k_code, kf), (self.k_scale, g), (self.k_mn, g)):
+                es = x.element_size()
+                b0, b1 = _span(lo // per * es, -(-hi // per) * es, x.shape[4] * es)
+                out.append(slab(x, p * x.stride(2) * es + b0, [(h, x.stride(1) * es), (self.D, x.stride(3) * es)], b1 - b0))
+        if self.k_res_len:
+            out.append(slab(self.k_res, 0, [(h, self.k_res.stride(1) * 2)], self.k_res_len * self.D * 2))
+        if from_token < self.v_quant_len:
+            for x in (self.v_code, self.v_scale, self.v_mn):
+                es, rowb = x.element_size(), x.shape[3] * x.element_size()
+                b0, b1 = _span(from_token * rowb, self.v_quant_len * rowb, x.shape[2] * rowb)
+                out.append(slab(x, b0, [(h, x.stride(1) * es)], b1 - b0))
+        if self.v_res_len:
+            rowb = self.D * 2
+            b0, b1 = _span(self.v_res_start * rowb, (self.v_res_start + self.v_res_len) * rowb, self.v_res.shape[2] * rowb)
+            out.append(slab(self.v_res, b0, [(h, self.v_res.stride(1) * 2)], b1 - b0))
+        return out
+
+    def index_select(self, idx) -> "KiviLayerCache":
+        """A new cache of len(idx) rows, row i a bit-identical copy of row idx[i] (whole rows): the fork of B requests into
+        B * num_beams beams."""
+        import copy
+        idx = torch.as_tensor(idx, device=self.k_res.device).long().flatten()
+        if idx.numel() == 0 or not bool(((idx >= 0) & (idx < self.B)).all()):
+            raise ValueError(f"index_select: indices must lie in [0, {self.B})")
+        other = copy.copy(self)
+        for name in ("k_code", "k_scale", "k_mn"):
+            src = getattr(self, name)
+            dst = self._paged((idx.numel(),) + tuple(src.shape[1:]), src.dtype, src.device)
+            dst.copy_(src.index_select(0, idx))
+            setattr(other, name, dst)
+        for name in ("k_res", "v_code", "v_scale", "v_mn", "v_res"):
+            setattr(other, name, getattr(self, name).index_select(0, idx))
+        other.B = idx.numel()
+        for name in ("_native", "_scores", "_probs"):
+            other.__dict__.pop(name, None)
+        return other
+
     # ------------------------------------------------------------------ the 9-tuple
     def k_quant_reference_layout(self):
         """(K_code_T, K_scale_T, K_mn_T) in the reference layout (B, nh_kv, D, Tq/...): gathers the pages (a copy)."""

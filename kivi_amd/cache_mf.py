@@ -134,6 +134,74 @@ class KiviLayerCacheMF:
         other._native = None
         return other
 
+    # ------------------------------------------------------------------ beam search
+    def reorder_(self, idx, group: int = None, from_token: int = 0, check: bool = True) -> "KiviLayerCacheMF":
+        """row[b] <- row[idx[b]] in place: the contract of KiviLayerCache.reorder_ (the range words always move)."""
+        from . import reorder
+        group = self.B if group is None else int(group)
+        if not 0 <= int(from_token) <= self.kv_seq_len:
+            raise ValueError(f"from_token={from_token} lies beyond the cache length {self.kv_seq_len}")
+        idx = reorder.check_idx(idx, self.B, group, self.k_res.device, check)
+        reorder.run(self._reorder_slabs(int(from_token)), self.B, group, idx)
+        return self
+
+    def _reorder_slabs(self, from_token: int):
+        """Super-blocks of 16 blocks of 32 tokens (kivi_mfma_layout.h): codes of block j at words [j BW, (j + 1) BW); V scales /
+        zero points of block j at halves j * 128 of their regions; K scales / zero points of group j at halves
+        (j >> 3) * 1024 + (c, kb) * 64 + (j & 7) * 8 (16 pieces of 16 bytes per block).  Whole super-blocks move as one run."""
+        from .reorder import slab
+        h = self.nh_kv
+        W = mfma.sb_words(self.cfg.k_bits)
+        S0, BW = (W - 2048) * 4, (W - 2048) // 16 * 4          # byte offset of the scale region, bytes of codes per block
+        out = []
+        for st, n_tok, is_k in ((self.kt, self.k_quant_len, True), (self.vt, self.v_quant_len, False)):
+            ss, sh = st.stride(2) * 4, st.stride(1) * 4
+            j0, j1 = from_token // 32, -(-n_tok // 32)           # blocks [j0, j1): K groups / V tokens from from_token on
+            s = j0 // 16
+            while s * 16 < j1 and j0 < j1:
+                lo, hi = max(j0, 16 * s) - 16 * s, min(j1, 16 * s + 16) - 16 * s
+                if lo == 0 and hi == 16:
+                    e = s
+                    while (e + 2) * 16 <= j1:
+                        e += 1
+                    out.append(slab(st, s * ss, [(e - s + 1, ss), (h, sh)], W * 4))
+                    s = e + 1
+                    continue
+                out.append(slab(st, s * ss + lo * BW, [(h, sh)], (hi - lo) * BW))
+                if is_k:
+                    for half in (0, 1):
+                        glo, ghi = max(lo, 8 * half), min(hi, 8 * half + 8)
+                        if glo < ghi:
+                            out.append(slab(st, s * ss + S0 + (half * 1024 + (glo & 7) * 8) * 2, [(h, sh), (2, 4096), (16, 128)],
+                                            (ghi - glo) * 16))
+                else:
+                    out.append(slab(st, s * ss + S0 + lo * 256, [(h, sh), (2, 4096)], (hi - lo) * 256))
+                s += 1
+            out.append(slab(mfma.range_flags(st), 0, [], h * 4))
+        if self.k_res_len:
+            out.append(slab(self.k_res, 0, [(h, self.k_res.stride(1) * 2)], self.k_res_len * self.D * 2))
+        out.append(slab(self.v_res, 0, [(h, self.v_res.stride(1) * 2)], self.v_res.shape[2] * self.D * 2))
+        return out
+
+    def index_select(self, idx) -> "KiviLayerCacheMF":
+        """A new cache of len(idx) rows, row i a bit-identical copy of row idx[i] (whole rows, range words included)."""
+        import copy
+        idx = torch.as_tensor(idx, device=self.k_res.device).long().flatten()
+        if idx.numel() == 0 or not bool(((idx >= 0) & (idx < self.B)).all()):
+            raise ValueError(f"index_select: indices must lie in [0, {self.B})")
+        other = copy.copy(self)
+        for name in ("kt", "vt"):
+            src = getattr(self, name)
+            dst = mfma.alloc_store(idx.numel(), self.nh_kv, self.n_sb, src.device, self.cfg.k_bits)
+            dst.copy_(src.index_select(0, idx))
+            mfma.range_flags(dst).copy_(mfma.range_flags(src).index_select(0, idx))
+            setattr(other, name, dst)
+        for name in ("k_res", "v_res"):
+            setattr(other, name, getattr(self, name).index_select(0, idx))
+        other.B = idx.numel()
+        other._native = None
+        return other
+
     # ------------------------------------------------------------------ the 9-tuple
     def k_quant_reference_layout(self):
         if self.k_quant_len == 0:

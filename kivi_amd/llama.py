@@ -187,17 +187,45 @@ class LlamaForCausalLM_KIVI(nn.Module):
                              f"masks (llama_kivi.py:420-423), so padded prompts cannot be run; use the eager class")
         return True
 
+    @staticmethod
+    def _reorder_cache(past_key_values, beam_idx: torch.Tensor):
+        """The reference's hook for HF's beam search (models/llama_kivi.py:951-957): row b of every layer's cache <- row
+        beam_idx[b], here IN PLACE (kivi_cache_reorder, whole rows) instead of an index_select copy of every member.  Returns
+        fresh 9-tuples of the same caches (plain 9-tuples, which have no in-place cache, are index_selected as the reference does)."""
+        out = []
+        for p in past_key_values:
+            layer = getattr(p, "layer", None)
+            if layer is None:
+                out.append(tuple(x.index_select(0, beam_idx.to(x.device)) if torch.is_tensor(x) else x for x in p))
+            else:
+                out.append(layer.reorder_(beam_idx).as_tuple())
+        return tuple(out)
+
     @torch.no_grad()
     def generate(self, input_ids: torch.LongTensor, max_new_tokens: int, past_key_values: Optional[List] = None,
                  attention_mask: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
-                 pad_token_id: Optional[int] = None) -> torch.LongTensor:
+                 pad_token_id: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0,
+                 early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False):
         """Greedy decoding (the recipe of the reference's mem_spd_test.py / example.py).  With `past_key_values` (the caches of
         an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one pass (kivi_attention_extend) and
         decoding continues from there; the caches are advanced in place.  `attention_mask`: HF's 2D mask (B, past + T) of
         left-padded prompts (1 = real token; with `past_key_values` it covers the history and the new turn).  A row that has
-        produced `eos_token_id` emits `pad_token_id` from then on; the loop stops when every row has finished."""
+        produced `eos_token_id` emits `pad_token_id` from then on; the loop stops when every row has finished.
+
+        `num_beams > 1`: HF's beam search (kivi_amd/beam.py; `length_penalty`, `early_stopping` True / False / "never",
+        `num_return_sequences` as in transformers).  The prompt pass runs on the B requests, the caches are then forked to
+        B * num_beams rows, and every step reorders them in place from the fork point on.  With
+        `past_key_values` the caller's caches are forked and left UNCHANGED (the new turn runs on a copy).  Returns
+        (B * num_return_sequences, T + generated) sequences, and their sequences_scores when `return_scores`."""
         if eos_token_id is not None and pad_token_id is None:
             raise ValueError("eos_token_id needs a pad_token_id for the rows that have finished")
+        if num_beams < 1 or num_return_sequences < 1 or num_return_sequences > num_beams:
+            raise ValueError(f"num_return_sequences ({num_return_sequences}) must lie in [1, num_beams ({num_beams})]")
+        if num_beams > 1:
+            return self._generate_beams(input_ids, max_new_tokens, past_key_values, attention_mask, eos_token_id, pad_token_id,
+                                        num_beams, length_penalty, early_stopping, num_return_sequences, return_scores)
+        if return_scores:
+            raise ValueError("return_scores: sequences_scores exist for beam search (num_beams > 1) only")
         B, T = input_ids.shape
         past_len = self._past_len(past_key_values)
         pos = row = None
@@ -226,6 +254,44 @@ class LlamaForCausalLM_KIVI(nn.Module):
                 pos = pos + 1
             tok = logits.argmax(-1)
         return torch.cat(out, dim=1)
+
+    def _generate_beams(self, input_ids, max_new_tokens, past_key_values, attention_mask, eos_token_id, pad_token_id, nb,
+                        length_penalty, early_stopping, num_return_sequences, return_scores):
+        from .beam import beam_search
+        B, T = input_ids.shape
+        past_len = self._past_len(past_key_values)
+        if past_key_values is not None:              # the caller's caches stay as they are
+            past_key_values = [p.layer.clone().as_tuple() for p in past_key_values]
+        pos = row = None
+        if attention_mask is not None and self._padded(attention_mask, B, past_len + T, past_len):
+            row = padding_key_row(attention_mask, past_len + T + max_new_tokens)
+            mask = padding_prompt_mask(attention_mask) if past_len == 0 else row[..., : past_len + T].expand(-1, -1, T, -1)
+            logits, pasts = self._forward(input_ids, past_key_values, mask, padding_position_ids(attention_mask, T), True, True)
+            pos = attention_mask.long().sum(-1, keepdim=True).repeat_interleave(nb, dim=0)
+            row = row.repeat_interleave(nb, dim=0)
+        else:
+            logits, pasts = self.forward(input_ids, past_key_values)
+        # the fork: every request's rows repeated over its beams; rows of a group agree on every byte before `fork`
+        fork = past_len + T
+        caches = [p.layer.index_select(torch.arange(B, device=input_ids.device).repeat_interleave(nb)) for p in pasts]
+        s = 0
+
+        def step(tok, beam_idx):
+            nonlocal s, pos
+            for c in caches:
+                c.reorder_(beam_idx, group=nb, from_token=fork, check=False)
+            pasts = [c.as_tuple() for c in caches]
+            if row is None:
+                logits, _ = self.forward(tok, pasts)
+            else:
+                logits, _ = self._forward(tok, pasts, row[..., : fork + s + 1], pos, True, True)
+                pos = pos + 1
+            s += 1
+            return logits[:, -1].float()
+
+        seqs, scores = beam_search(step, input_ids, logits[:, -1].float(), nb, max_new_tokens, eos_token_id, pad_token_id,
+                                   length_penalty, early_stopping, num_return_sequences)
+        return (seqs, scores) if return_scores else seqs
 
     # ------------------------------------------------------------------ hipGraph decode
     # The dense part of a decode step is ~30 small launches per layer; in eager mode the host needs longer to enqueue
@@ -412,9 +478,12 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     @torch.no_grad()
     def generate_graphed(self, input_ids: torch.LongTensor, max_new_tokens: int,
-                         attention_mask: Optional[torch.Tensor] = None) -> torch.LongTensor:
+                         attention_mask: Optional[torch.Tensor] = None, num_beams: int = 1) -> torch.LongTensor:
         """generate() with the dense part of every decode step replayed from hipGraphs (see _build_graphs).
-        `attention_mask`: HF's 2D (B, T) mask of left-padded prompts (1 = real token)."""
+        `attention_mask`: HF's 2D (B, T) mask of left-padded prompts (1 = real token).  Greedy only: `num_beams > 1` is refused
+        (a graphed beam step is open; use generate())."""
+        if num_beams != 1:
+            raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
         logits, pasts = self.forward(input_ids, padding_mask=attention_mask)
         if attention_mask is not None:
             attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, :1])], dim=1)
