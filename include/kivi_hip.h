@@ -28,6 +28,8 @@
  *                               2-bit with nh / nh_kv in {1, 4, 8} or 4-bit with nh / nh_kv in {1, 4}), with the packers of that
  *                               cache: kivi_kt_pack, kivi_vt_pack, kivi_vt_pack_at, kivi_kt_relayout, kivi_vt_relayout
  *               beam search:    kivi_cache_reorder (in-place row reorder of either cache layout, from a fork point on)
+ *               sampling:       kivi_sample (temperature / top-k / top-p / min-p draw of one token per row, Philox RNG state on
+ *                               the device)
  *   BUILDING BLOCKS (what the layer steps are composed of; exported for tests, tools and callers that keep their own cache
  *               bookkeeping -- same contracts, but no stability promise beyond the ABI version):  kivi_gemv_k_paged,
  *               kivi_decode_scores, kivi_softmax_scaled, kivi_decode_output, kivi_decode_softmax_output, kivi_decode_attend,
@@ -529,6 +531,27 @@ typedef struct kivi_reorder_slab {
 } kivi_reorder_slab;
 int kivi_cache_reorder(const kivi_reorder_slab* slabs, int n_slabs, int B, int group, const void* idx, int idx_bytes,
                        kivi_stream_t stream);
+/*
+ * kivi_sample: one token per row drawn from (B, V) logits the way transformers' do_sample path does:
+ * s = float(logit) / temperature; keep s >= the top_k-th largest s (ties kept; top_k = 0 or >= V: off); renormalise over those and
+ * keep a token when the probability mass strictly above it is < top_p (whole tie classes; 1: off); keep p >= min_p * p_max (0: off);
+ * then the first token in vocabulary order whose inclusive running sum of kept probabilities exceeds u * (kept mass).
+ * Probabilities are integer weights floor(exp(s - max) * 2^40), so every sum is exact and the token is reproducible bit for bit.
+ *   logits      row b at logits + b * row_stride (elements); fp16 (logits_bits 16) or fp32 (32); any V-long row, e.g. the
+ *               (B, 1, V) output of lm_head read in place
+ *   rng_state   two int64 in device memory, {seed, n}.  u = (x0 >> 8) * 2^-24 with x0 the first word of Philox4x32-10 at
+ *               key (seed low 32 bits, seed high 32 bits), counter (b, 0, n low 32 bits, n high 32 bits).  A second one-thread
+ *               launch of the same call adds 1 to n after the draw: a captured graph replays without host writes.
+ *   out_tokens  int64, token of row b at out_tokens[b * out_stride]
+ * -inf logits are legal and never drawn; a row that is all -inf or holds NaN / +inf gets some token in [0, V).
+ * KIVI_EINVAL (nothing enqueued) for logits_bits not 16 / 32, B outside [1, KIVI_SAMPLE_MAX_B], V outside [1, KIVI_SAMPLE_MAX_V],
+ * row_stride < V or out_stride < 1 (B > 1), temperature not finite and > 0, top_k < 0, top_p outside (0, 1], min_p outside [0, 1),
+ * a null pointer; KIVI_EALIGN for logits not aligned to its element, rng_state or out_tokens not 8-byte aligned.
+ */
+#define KIVI_SAMPLE_MAX_B 65535
+#define KIVI_SAMPLE_MAX_V (1 << 20)
+int kivi_sample(const void* logits, int logits_bits, int64_t row_stride, int B, int V, float temperature, int top_k, float top_p,
+                float min_p, int64_t* rng_state, int64_t* out_tokens, int64_t out_stride, kivi_stream_t stream);
 /* geometry class of a step (-1: bad arguments): the super-block counts of both stores and whether the step flushes a value; the
  * launch plan (one launch / S slices / two launches) is a function of the class and of constants of the call (shape, bits, flags) */
 int64_t kivi_mf_step_key(const kivi_mf_step* step, int B, int nh, int nh_kv, int residual_length, int flags);

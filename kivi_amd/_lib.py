@@ -121,6 +121,8 @@ class MfLayerDesc(ctypes.Structure):
 
 REORDER_MAX_SLABS = 32    # include/kivi_hip.h: KIVI_REORDER_MAX_SLABS
 REORDER_MAX_GROUP = 1024
+SAMPLE_MAX_B = 65535      # include/kivi_hip.h: KIVI_SAMPLE_MAX_B, KIVI_SAMPLE_MAX_V
+SAMPLE_MAX_V = 1 << 20
 
 
 class ReorderSlab(ctypes.Structure):
@@ -177,6 +179,7 @@ SIGNATURES = {
                                     _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "kivi_vt_pack_at": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _i32, _i64, _i32, _i32, _i32, _vp]),
     "kivi_cache_reorder": (_i32, [ctypes.POINTER(ReorderSlab), _i32, _i32, _i32, _vp, _i32, _vp]),
+    "kivi_sample": (_i32, [_vp, _i32, _i64, _i32, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float, _vp, _vp, _i64, _vp]),
     "kivi_mf_step_key": (_i64, [ctypes.POINTER(MfStep), _i32, _i32, _i32, _i32, _i32]),
     "kivi_mf_step_advance": (_i32, [ctypes.POINTER(MfStep), _i32, _i64]),
     "kivi_mf_step_upload": (_i32, [ctypes.POINTER(MfStep), _vp, _vp]),

@@ -1,0 +1,282 @@
+// Fused temperature / top-k / top-p / min-p sampler (include/kivi_hip.h, kivi_sample).
+//
+// One workgroup of 1024 threads per row.  Every filter of the contract keeps the tokens whose score s = float(logit) / temperature
+// is >= some threshold (whole tie classes), so the kernel never sorts: it finds each threshold as an exact key of the
+// order-preserving uint32 image of s by radix select (11 + 11 + 10-bit digits, LDS histograms), then draws by inverse CDF in
+// vocabulary order.  Probabilities are carried as integer weights w = floor(exp(s - max) * 2^40): every sum is an integer sum, so
+// histograms may use LDS integer atomics and the result does not depend on the order of the additions -- the same row, seed and
+// draw index give the same token on every run, eager or replayed from a graph.
+//
+//   pass 0        max key (block reduction)
+//   top-k         3 passes: count histograms, the k-th largest key t_k (ties: keep s >= that value)
+//   top-p         3 passes over the top-k survivors: weight histograms; the first pass's total is Z_k; t_p = the lowest key whose
+//                 strictly-higher mass is < top_p * Z_k
+//   draw          1 pass: per bucket (BS consecutive tokens, one wave each) the kept weight; a block scan over the <= 1024 buckets
+//                 finds the bucket where the running sum crosses u * S; wave 0 scans that bucket's tokens.
+// The row is read from memory in every pass (an L2 hit after the first); nothing is staged, so any V up to KIVI_SAMPLE_MAX_V works.
+// A second, one-thread launch advances the draw counter n of the RNG state after the sampler has read it.
+#include "kivi_common.h"
+
+namespace {
+
+constexpr int kThreads = 1024;
+constexpr int kWaves = kThreads / KIVI_WAVE;
+constexpr int kBins = 2048;
+constexpr float kWScale = 1099511627776.0f;            // 2^40
+
+__device__ __forceinline__ uint32_t key_of(float s) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, s);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float float_of(uint32_t k) {
+    return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+__device__ __forceinline__ uint64_t weight_of(float e) { return e > 0.0f ? (uint64_t)(e * kWScale) : 0; }
+
+__device__ __forceinline__ uint64_t shfl_down64(uint64_t v, int d) {
+    const uint32_t lo = __shfl_down((uint32_t)v, d), hi = __shfl_down((uint32_t)(v >> 32), d);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t shfl_up64(uint64_t v, int d) {
+    const uint32_t lo = __shfl_up((uint32_t)v, d), hi = __shfl_up((uint32_t)(v >> 32), d);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int l) {
+    const uint32_t lo = __shfl((uint32_t)v, l), hi = __shfl((uint32_t)(v >> 32), l);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v, int lane) {
+#pragma unroll
+    for (int d = 1; d < KIVI_WAVE; d <<= 1) {
+        const uint64_t o = shfl_up64(v, d);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants), first output word.
+__device__ __forceinline__ uint32_t philox_x0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) {
+            k0 += 0x9E3779B9u;
+            k1 += 0xBB67AE85u;
+        }
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0;
+        c1 = (uint32_t)p1;
+        c2 = n2;
+        c3 = (uint32_t)p0;
+    }
+    return c0;
+}
+
+struct Shared {
+    uint64_t hist[kBins];       // radix histograms; the draw's bucket sums reuse the first 1024
+    uint64_t wsum[kWaves];
+    uint64_t sel_above, sel_base, sel_rem;
+    uint32_t wmax[kWaves];
+    uint32_t sel_bin, sel_bucket, token;
+};
+
+template <typename T>
+struct Row {
+    const T* p;
+    float temp;
+    bool div;
+    __device__ __forceinline__ float s(int e) const {
+        const float x = (float)p[e];
+        return (div ? x / temp : x) + 0.0f;          // + 0: -0 and +0 are one tie class (one key)
+    }
+};
+
+// One radix digit over the tokens of this wave's segment: histogram (counts, or weights when MASS) of the keys >= lo whose bits
+// above `shift + nbits` equal those of `prefix`, then wave 0 picks the lowest non-empty bin whose strictly-higher total is < the
+// remaining target (for counts: the bin that holds the k-th largest; for weights: the bin that holds the top-p boundary class).
+template <bool MASS, typename T>
+__device__ void radix_digit(Shared& sh, const Row<T>& row, int e0, int e1, float m, uint32_t lo, uint32_t& prefix, int shift,
+                            int nbits, uint64_t& rem, double frac) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int nb = 1 << nbits;
+    for (int i = tid; i < nb; i += kThreads) sh.hist[i] = 0;
+    __syncthreads();
+    const int hs = shift + nbits;
+    for (int e = e0 + lane; e < e1; e += KIVI_WAVE) {
+        const float s = row.s(e);
+        const uint32_t k = key_of(s);
+        if (k < lo || (hs < 32 && (k >> hs) != (prefix >> hs))) continue;
+        const uint64_t v = MASS ? weight_of(expf(s - m)) : 1;
+        if (v) atomicAdd(reinterpret_cast<unsigned long long*>(&sh.hist[(k >> shift) & (nb - 1)]), (unsigned long long)v);
+    }
+    __syncthreads();
+    if (tid < KIVI_WAVE) {
+        const int per = nb / KIVI_WAVE;
+        uint64_t tot = 0;
+        for (int i = 0; i < per; ++i) tot += sh.hist[lane * per + i];
+        uint64_t suf = tot;
+#pragma unroll
+        for (int d = 1; d < KIVI_WAVE; d <<= 1) {
+            const uint64_t o = shfl_down64(suf, d);
+            if (lane + d < KIVI_WAVE) suf += o;
+        }
+        const uint64_t total = shfl64(suf, 0);
+        uint64_t R = rem;
+        if (frac >= 0.0) {                            // first top-p digit: the total is Z_k, the target ceil(top_p * Z_k)
+            const double x = frac * (double)total;
+            R = (uint64_t)x;
+            if ((double)R < x) ++R;
+        }
+        uint64_t above = suf - tot, best_above = 0;
+        int best = 1 << 30;
+        for (int i = per - 1; i >= 0; --i) {
+            const uint64_t h = sh.hist[lane * per + i];
+            if (h && above < R) {
+                best = lane * per + i;
+                best_above = above;
+            }
+            above += h;
+        }
+        int lowest = best;
+#pragma unroll
+        for (int d = 1; d < KIVI_WAVE; d <<= 1) lowest = min(lowest, __shfl_xor(lowest, d));
+        if (lowest == (1 << 30)) {                    // nothing of positive weight (a row outside the contract): any bin
+            if (lane == 0) {
+                sh.sel_bin = 0;
+                sh.sel_above = 0;
+                sh.sel_rem = R;
+            }
+        } else if (best == lowest) {
+            sh.sel_bin = (uint32_t)best;
+            sh.sel_above = best_above;
+            sh.sel_rem = R;
+        }
+    }
+    __syncthreads();
+    prefix |= sh.sel_bin << shift;
+    rem = sh.sel_rem - sh.sel_above;
+    __syncthreads();
+}
+
+template <bool MASS, typename T>
+__device__ uint32_t radix_select(Shared& sh, const Row<T>& row, int e0, int e1, float m, uint32_t lo, uint64_t rem, double frac) {
+    uint32_t prefix = 0;
+    radix_digit<MASS>(sh, row, e0, e1, m, lo, prefix, 21, 11, rem, frac);
+    radix_digit<MASS>(sh, row, e0, e1, m, lo, prefix, 10, 11, rem, -1.0);
+    radix_digit<MASS>(sh, row, e0, e1, m, lo, prefix, 0, 10, rem, -1.0);
+    return prefix;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void sample_kernel(const T* __restrict__ logits, int64_t row_stride, int V, int BS, float temp,
+                                                          int top_k, float top_p, float min_p, const int64_t* __restrict__ state,
+                                                          int64_t* __restrict__ out, int64_t out_stride) {
+    __shared__ Shared sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const Row<T> row{logits + (int64_t)blockIdx.x * row_stride, temp, temp != 1.0f};
+    const int nbk = (V + BS - 1) / BS, bpw = (nbk + kWaves - 1) / kWaves;
+    const int bk0 = min(nbk, wave * bpw), bk1 = min(nbk, (wave + 1) * bpw);
+    const int e0 = min(V, bk0 * BS), e1 = min(V, bk1 * BS);
+
+    // max key
+    uint32_t mk = 0;
+    for (int e = e0 + lane; e < e1; e += KIVI_WAVE) mk = max(mk, key_of(row.s(e)));
+#pragma unroll
+    for (int d = 1; d < KIVI_WAVE; d <<= 1) mk = max(mk, (uint32_t)__shfl_xor(mk, d));
+    if (lane == 0) sh.wmax[wave] = mk;
+    __syncthreads();
+    mk = 0;
+    for (int w = 0; w < kWaves; ++w) mk = max(mk, sh.wmax[w]);
+    const float m = float_of(mk);
+
+    // thresholds (keys): top-k, then top-p over the top-k survivors
+    uint32_t tk = 0, tp = 0;
+    const int k = min(top_k, V);
+    if (k > 0 && k < V) tk = radix_select<false>(sh, row, e0, e1, m, 0, (uint64_t)k, -1.0);
+    if (top_p < 1.0f) tp = radix_select<true>(sh, row, e0, e1, m, tk, 0, (double)top_p);
+    const uint32_t thr = max(tk, tp);
+    auto kept_weight = [&](int e) -> uint64_t {
+        const float s = row.s(e);
+        const float p = expf(s - m);
+        return (key_of(s) >= thr && p >= min_p) ? weight_of(p) : 0;
+    };
+
+    // draw: bucket sums (bucket b = tokens [b * BS, (b + 1) * BS), owned by one wave), block scan, crossing bucket, crossing token
+    for (int b = bk0; b < bk1; ++b) {
+        uint64_t acc = 0;
+        for (int e = b * BS + lane; e < min(V, (b + 1) * BS); e += KIVI_WAVE) acc += kept_weight(e);
+#pragma unroll
+        for (int d = 1; d < KIVI_WAVE; d <<= 1) acc += shfl_down64(acc, d);
+        if (lane == 0) sh.hist[b] = acc;
+    }
+    if (tid == 0) sh.token = 0;                       // a row with no positive weight (outside the contract) gets token 0
+    __syncthreads();
+    const uint64_t v = tid < nbk ? sh.hist[tid] : 0;
+    uint64_t incl = wave_incl_scan64(v, lane);
+    if (lane == 63) sh.wsum[wave] = incl;
+    __syncthreads();
+    uint64_t S = 0;
+    for (int w = 0; w < kWaves; ++w) {
+        if (w < wave) incl += sh.wsum[w];
+        S += sh.wsum[w];
+    }
+    const int64_t n = state[1];
+    const uint64_t seed = (uint64_t)state[0];
+    const uint32_t u24 = philox_x0(blockIdx.x, 0, (uint32_t)n, (uint32_t)((uint64_t)n >> 32), (uint32_t)seed, (uint32_t)(seed >> 32)) >> 8;
+    // floor(S * u24 / 2^24), exactly (S < 2^61)
+    const uint64_t target = (S >> 24) * u24 + (((S & 0xFFFFFFu) * u24) >> 24);
+    if (S > 0 && tid < nbk && incl - v <= target && target < incl) {
+        sh.sel_bucket = (uint32_t)tid;
+        sh.sel_base = incl - v;
+    }
+    __syncthreads();
+    if (S > 0 && tid < KIVI_WAVE) {
+        const int b = (int)sh.sel_bucket;
+        uint64_t base = sh.sel_base;
+        for (int j = b * BS; j < min(V, (b + 1) * BS); j += KIVI_WAVE) {
+            const int e = j + lane;
+            const uint64_t w = e < V ? kept_weight(e) : 0;
+            const uint64_t c = wave_incl_scan64(w, lane);
+            if (base + c - w <= target && target < base + c) sh.token = (uint32_t)e;
+            base += shfl64(c, 63);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) out[(int64_t)blockIdx.x * out_stride] = (int64_t)sh.token;
+}
+
+__global__ void advance_kernel(int64_t* state) { state[1] += 1; }
+
+}  // namespace
+
+extern "C" int kivi_sample(const void* logits, int logits_bits, int64_t row_stride, int B, int V, float temperature, int top_k,
+                           float top_p, float min_p, int64_t* rng_state, int64_t* out_tokens, int64_t out_stride,
+                           kivi_stream_t stream) {
+    KIVI_REQUIRE(logits_bits == 16 || logits_bits == 32, KIVI_EINVAL, "kivi_sample: logits_bits=%d (16: fp16, 32: fp32)", logits_bits);
+    KIVI_REQUIRE(B >= 1 && B <= KIVI_SAMPLE_MAX_B, KIVI_EINVAL, "kivi_sample: B=%d (1 <= B <= %d)", B, KIVI_SAMPLE_MAX_B);
+    KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "kivi_sample: V=%d (1 <= V <= %d)", V, KIVI_SAMPLE_MAX_V);
+    KIVI_REQUIRE(row_stride >= V || B == 1, KIVI_EINVAL, "kivi_sample: row_stride=%lld below V=%d", (long long)row_stride, V);
+    KIVI_REQUIRE(out_stride >= 1 || B == 1, KIVI_EINVAL, "kivi_sample: out_stride=%lld", (long long)out_stride);
+    KIVI_REQUIRE(temperature > 0.0f && __builtin_isfinite(temperature), KIVI_EINVAL, "kivi_sample: temperature=%g (finite, > 0)",
+                 (double)temperature);
+    KIVI_REQUIRE(top_k >= 0, KIVI_EINVAL, "kivi_sample: top_k=%d (0 = off)", top_k);
+    KIVI_REQUIRE(top_p > 0.0f && top_p <= 1.0f, KIVI_EINVAL, "kivi_sample: top_p=%g (0 < top_p <= 1; 1 = off)", (double)top_p);
+    KIVI_REQUIRE(min_p >= 0.0f && min_p < 1.0f, KIVI_EINVAL, "kivi_sample: min_p=%g (0 <= min_p < 1; 0 = off)", (double)min_p);
+    KIVI_REQUIRE(logits && rng_state && out_tokens, KIVI_EINVAL, "kivi_sample: null pointer");
+    const int esz = logits_bits / 8;
+    KIVI_REQUIRE((uintptr_t)logits % esz == 0 && (uintptr_t)rng_state % 8 == 0 && (uintptr_t)out_tokens % 8 == 0, KIVI_EALIGN,
+                 "kivi_sample: misaligned logits (%d-byte elements), rng_state or out_tokens (8 bytes)", esz);
+    int BS = KIVI_WAVE;                              // bucket of the draw: a power of two, at most 1024 buckets per row
+    while ((int64_t)BS * 1024 < V) BS <<= 1;
+    const hipStream_t s = (hipStream_t)stream;
+    if (logits_bits == 16)
+        KIVI_LAUNCH(sample_kernel<f16>, dim3(B), dim3(kThreads), s, (const f16*)logits, row_stride, V, BS, temperature, top_k, top_p,
+                    min_p, (const int64_t*)rng_state, out_tokens, out_stride);
+    else
+        KIVI_LAUNCH(sample_kernel<float>, dim3(B), dim3(kThreads), s, (const float*)logits, row_stride, V, BS, temperature, top_k,
+                    top_p, min_p, (const int64_t*)rng_state, out_tokens, out_stride);
+    int rc = kivi_launch_status("kivi_sample");
+    if (rc) return rc;
+    KIVI_LAUNCH(advance_kernel, dim3(1), dim3(1), s, rng_state);
+    return kivi_launch_status("kivi_sample (advance)");
+}

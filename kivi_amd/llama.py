@@ -2,8 +2,8 @@
 
 Counterpart of the reference's LlamaForCausalLM_KIVI / MistralForCausalLM_KIVI wrappers (models/llama_kivi.py:564-1000,
 models/mistral_kivi.py:673-1100) reduced to what decoding needs: token embedding, pre-norm decoder blocks
-(RMSNorm, LlamaAttention_KIVI, SwiGLU MLP), final norm, lm_head, greedy generate.  Parameter names follow the Hugging
-Face checkpoints (model.embed_tokens, model.layers.N.self_attn.q_proj, ..., lm_head), so `load_state_dict` /
+(RMSNorm, LlamaAttention_KIVI, SwiGLU MLP), final norm, lm_head, generate (greedy, sampling, beam search).  Parameter names
+follow the Hugging Face checkpoints (model.embed_tokens, model.layers.N.self_attn.q_proj, ..., lm_head), so `load_state_dict` /
 `from_pretrained` take an unmodified Llama-2 / Llama-3 / Mistral checkpoint directory; everything outside the attention
 block is plain torch (rocBLAS / hipBLASLt GEMMs).  The reference patches k_bits / v_bits / group_size /
 residual_length onto the HF config (README.md:72-75); the same four fields are read here.
@@ -205,18 +205,26 @@ class LlamaForCausalLM_KIVI(nn.Module):
     def generate(self, input_ids: torch.LongTensor, max_new_tokens: int, past_key_values: Optional[List] = None,
                  attention_mask: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0,
-                 early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False):
-        """Greedy decoding (the recipe of the reference's mem_spd_test.py / example.py).  With `past_key_values` (the caches of
-        an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one pass (kivi_attention_extend) and
-        decoding continues from there; the caches are advanced in place.  `attention_mask`: HF's 2D mask (B, past + T) of
-        left-padded prompts (1 = real token; with `past_key_values` it covers the history and the new turn).  A row that has
-        produced `eos_token_id` emits `pad_token_id` from then on; the loop stops when every row has finished.
+                 early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False, do_sample: bool = False,
+                 temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
+                 seed: Optional[int] = None):
+        """Greedy decoding (the recipe of the reference's mem_spd_test.py / example.py), or sampling with `do_sample=True`.
+        With `past_key_values` (the caches of an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one
+        pass (kivi_attention_extend) and decoding continues from there; the caches are advanced in place.  `attention_mask`:
+        HF's 2D mask (B, past + T) of left-padded prompts (1 = real token; with `past_key_values` it covers the history and the
+        new turn).  A row that has produced `eos_token_id` emits `pad_token_id` from then on; the loop stops when every row has
+        finished.
 
         `num_beams > 1`: HF's beam search (kivi_amd/beam.py; `length_penalty`, `early_stopping` True / False / "never",
         `num_return_sequences` as in transformers).  The prompt pass runs on the B requests, the caches are then forked to
         B * num_beams rows, and every step reorders them in place from the fork point on.  With
         `past_key_values` the caller's caches are forked and left UNCHANGED (the new turn runs on a copy).  Returns
-        (B * num_return_sequences, T + generated) sequences, and their sequences_scores when `return_scores`."""
+        (B * num_return_sequences, T + generated) sequences, and their sequences_scores when `return_scores`.
+
+        `do_sample=True`: transformers' sampling path with HF's parameters and defaults (`temperature`, `top_k`, `top_p`, `min_p`),
+        drawn by the fused HIP sampler (kivi_amd/sampling.py).  `seed`: the Philox seed of the call (None: one
+        drawn from torch's default CPU generator); token i of the call is draw i of every row.  Not with beams."""
+        sampler = self._sampler(input_ids.device, do_sample, num_beams, temperature, top_k, top_p, min_p, seed)
         if eos_token_id is not None and pad_token_id is None:
             raise ValueError("eos_token_id needs a pad_token_id for the rows that have finished")
         if num_beams < 1 or num_return_sequences < 1 or num_return_sequences > num_beams:
@@ -238,7 +246,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
         else:
             logits, pasts = self.forward(input_ids, past_key_values)
         out = [input_ids]
-        tok = logits.argmax(-1)
+        pick = (lambda lg: lg.argmax(-1)) if sampler is None else sampler
+        tok = pick(logits)
         live = None if eos_token_id is None else torch.ones((B, 1), dtype=torch.bool, device=tok.device)
         for s in range(max_new_tokens):
             if live is not None:
@@ -252,8 +261,18 @@ class LlamaForCausalLM_KIVI(nn.Module):
             else:
                 logits, pasts = self._forward(tok, pasts, row[..., : past_len + T + s + 1], pos, True, True)
                 pos = pos + 1
-            tok = logits.argmax(-1)
+            tok = pick(logits)
         return torch.cat(out, dim=1)
+
+    @staticmethod
+    def _sampler(device, do_sample, num_beams, temperature, top_k, top_p, min_p, seed):
+        """The Sampler of a do_sample call (None when greedy); every argument is checked before anything runs on a device."""
+        if not do_sample:
+            return None
+        if num_beams != 1:
+            raise ValueError(f"beam sampling (do_sample=True with num_beams={num_beams}) is not supported")
+        from .sampling import Sampler
+        return Sampler(temperature, top_k, top_p, min_p, seed, device)
 
     def _generate_beams(self, input_ids, max_new_tokens, past_key_values, attention_mask, eos_token_id, pad_token_id, nb,
                         length_penalty, early_stopping, num_return_sequences, return_scores):
@@ -303,7 +322,9 @@ class LlamaForCausalLM_KIVI(nn.Module):
     # memory (kivi_amd/graph.py), so the WHOLE step -- dense parts and attention of all layers -- is ONE graph (whole=True).
     # Padded batches (padded=True): cos / sin hold one position per row, and `mask` is a static additive (B, 1, 1, pitch) fp16
     # buffer, pitch >= the cache capacity, that the attention of every step reads (its new column is 0: new tokens are real).
-    def _build_graphs(self, B: int, device, whole: bool = False, padded: bool = False):
+    # Sampling (sampler=): the last layer's post() draws into g.tok with the sampler instead of argmax; the captured call holds the
+    # sampler's parameters and state buffer, so the graphs are keyed by Sampler.key() and captured again for another sampler.
+    def _build_graphs(self, B: int, device, whole: bool = False, padded: bool = False, sampler=None):
         cfg = self.config
         nh, nkv = cfg.num_attention_heads, cfg.num_key_value_heads
         D, H = self.model.layers[0].self_attn.head_dim, cfg.hidden_size
@@ -314,7 +335,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
                             sin=torch.zeros((rows, 1, 1, D), dtype=dt, device=device),
                             x=[torch.zeros((B, 1, H), dtype=dt, device=device) for _ in range(len(self.model.layers) + 1)],
                             attn=torch.zeros((B, nh, 1, D), dtype=dt, device=device), qkv=[], pre=[], post=[], whole=whole,
-                            padded=padded, mask=None, pos=None)
+                            padded=padded, mask=None, pos=None, sampler=sampler,
+                            sample_key=None if sampler is None else sampler.key(), warmup=False)
 
         def rot(t):
             return torch.cat((-t[..., D // 2:], t[..., : D // 2]), dim=-1)
@@ -337,7 +359,11 @@ class LlamaForCausalLM_KIVI(nn.Module):
             x = g.x[i] + layer.self_attn.o_proj(g.attn.transpose(1, 2).reshape(B, 1, nh * D))
             g.x[i + 1].copy_(x + layer.mlp(layer.post_attention_layernorm(x)))
             if i == len(self.model.layers) - 1:
-                g.tok.copy_(self.lm_head(self.model.norm(g.x[i + 1])).argmax(-1))
+                logits = self.lm_head(self.model.norm(g.x[i + 1]))
+                if g.sampler is None or g.warmup:       # (the warm-up must not consume a draw)
+                    g.tok.copy_(logits.argmax(-1))
+                else:
+                    g.sampler(logits, out=g.tok)
 
         for _ in self.model.layers:
             g.qkv.append((torch.zeros((B, nh, 1, D), dtype=dt, device=device),
@@ -348,11 +374,13 @@ class LlamaForCausalLM_KIVI(nn.Module):
             return g
         side = torch.cuda.Stream(device)
         side.wait_stream(torch.cuda.current_stream(device))
+        g.warmup = True
         with torch.cuda.stream(side):          # warm-up outside capture (library workspaces, autotuning)
             for i in range(len(self.model.layers)):
                 pre(i)
                 post(i)
         torch.cuda.current_stream(device).wait_stream(side)
+        g.warmup = False
         pool = None
         for i in range(len(self.model.layers)):
             for fn, dst in ((pre, g.pre), (post, g.post)):
@@ -364,11 +392,12 @@ class LlamaForCausalLM_KIVI(nn.Module):
         g.tok.zero_()
         return g
 
-    def prepare_graphs(self, batch: int, device, whole: bool = False, padded: bool = False) -> None:
+    def prepare_graphs(self, batch: int, device, whole: bool = False, padded: bool = False, sampler=None) -> None:
         """Capture the decode graphs for this batch size now (otherwise on the first graphed step)."""
         g = getattr(self, "_graphs", None)
-        if g is None or g.B != batch or g.whole != whole or g.padded != padded:
-            self._graphs = self._build_graphs(batch, device, whole, padded)
+        key = None if sampler is None else sampler.key()
+        if g is None or g.B != batch or g.whole != whole or g.padded != padded or g.sample_key != key:
+            self._graphs = self._build_graphs(batch, device, whole, padded, sampler)
 
     @staticmethod
     def _mask_room(g, caches, whole: bool) -> bool:
@@ -397,19 +426,20 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     @torch.no_grad()
     def decode_graphed(self, tok: torch.LongTensor, past_key_values: List, position: int, steps: int,
-                       attention_mask: Optional[torch.Tensor] = None) -> torch.LongTensor:
-        """`steps` greedy decode steps from token `tok` (B, 1) at position `position` with the dense part replayed from
+                       attention_mask: Optional[torch.Tensor] = None, sampler=None) -> torch.LongTensor:
+        """`steps` decode steps from token `tok` (B, 1) at position `position` with the dense part replayed from
         hipGraphs; the caches in `past_key_values` are advanced in place.  Returns the (B, steps) tokens fed to the model
         (tok first); the token following them is left in the graph's token buffer (`self._graphs.tok`).
         `attention_mask`: HF's 2D mask (B, kv_len + 1) over the cached tokens and `tok` (1 = real token); with a pad in it
-        every row takes its own position from the mask (`position` is not used) and the pads are masked in every step."""
+        every row takes its own position from the mask (`position` is not used) and the pads are masked in every step.
+        `sampler`: a kivi_amd.sampling.Sampler that draws each next token (one draw per step, inside the graph); None: greedy."""
         from .attention import kivi_attention_decode
         from .cache_mf import KiviLayerCacheMF
         caches = [p.layer for p in past_key_values]
         whole = all(isinstance(c, KiviLayerCacheMF) for c in caches)
         B, kv0 = tok.shape[0], caches[0].kv_seq_len
         padded = attention_mask is not None and self._padded(attention_mask, B, kv0 + 1, kv0)
-        self.prepare_graphs(B, tok.device, whole, padded)
+        self.prepare_graphs(B, tok.device, whole, padded, sampler)
         g = self._graphs
         attn0 = self.model.layers[0].self_attn
         g.tok.copy_(tok)
@@ -478,16 +508,21 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     @torch.no_grad()
     def generate_graphed(self, input_ids: torch.LongTensor, max_new_tokens: int,
-                         attention_mask: Optional[torch.Tensor] = None, num_beams: int = 1) -> torch.LongTensor:
+                         attention_mask: Optional[torch.Tensor] = None, num_beams: int = 1, do_sample: bool = False,
+                         temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
+                         seed: Optional[int] = None) -> torch.LongTensor:
         """generate() with the dense part of every decode step replayed from hipGraphs (see _build_graphs).
-        `attention_mask`: HF's 2D (B, T) mask of left-padded prompts (1 = real token).  Greedy only: `num_beams > 1` is refused
-        (a graphed beam step is open; use generate())."""
-        if num_beams != 1:
+        `attention_mask`: HF's 2D (B, T) mask of left-padded prompts (1 = real token).  Greedy, or sampling with `do_sample=True`
+        and the parameters of generate() (the draw inside the graph; the same tokens as generate() with the same seed).  Beams
+        are refused (a graphed beam step is open; use generate())."""
+        if num_beams != 1 and not do_sample:
             raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
+        sampler = self._sampler(input_ids.device, do_sample, num_beams, temperature, top_k, top_p, min_p, seed)
         logits, pasts = self.forward(input_ids, padding_mask=attention_mask)
         if attention_mask is not None:
             attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, :1])], dim=1)
-        new = self.decode_graphed(logits.argmax(-1), pasts, input_ids.shape[1], max_new_tokens, attention_mask)
+        tok = logits.argmax(-1) if sampler is None else sampler(logits)
+        new = self.decode_graphed(tok, pasts, input_ids.shape[1], max_new_tokens, attention_mask, sampler)
         self._graphed = None        # the caches of this request die with it: so does the graph captured over them
         return torch.cat([input_ids, new], dim=1)
 
