@@ -502,7 +502,12 @@ int kivi_mf_decode_layer_dyn(const kivi_mf_layer_desc* layer, const kivi_mf_step
  * values that leave the window, the new window rows.  The resulting cache (9-tuple and range words) is bit-identical to Q
  * kivi_mf_decode_layer steps fed the same keys and values.  Everything is validated before the first launch; `state` is written
  * once, at the end.  KIVI_EINVAL for Q < 1, a mask pitch below P0 + Q (mask_sb when mask_sq == 0), a capacity below P0 + Q,
- * inconsistent lengths.
+ * inconsistent lengths, a score dump (below) whose buffer cannot hold the rows.
+ * layer->flags & KIVI_GQA_DUMP_SCORES (tests): the attention launch also writes the fp16 row each chunk row's softmax consumes,
+ * fp16(fp16(q.k) / sqrt(D)) with the mask added and clamped at the fp16 minimum, before the causal mask: key t of chunk row i of
+ * query head h, batch row b at layer->scores + b*s_sb + h*s_sh + i*s_pitch + t (halves), for the keys the row sees, t < P0 + i + 1;
+ * the other halves are not written.  Requires scores != null, s_pitch >= P0 + Q, s_sh >= Q * s_pitch, s_sb >= nh * s_sh.  Without
+ * the flag `scores` is not touched (extend needs no scratch).
  */
 int kivi_mf_extend_layer(const kivi_mf_layer_desc* layer, int64_t* state, int Q, const void* q, int64_t q_sb, int64_t q_sh,
                          int64_t q_st, int nh, const void* knew, int64_t kn_sb, int64_t kn_sh, int64_t kn_st, const void* vnew,

@@ -357,11 +357,13 @@ class KiviLayerCacheMF:
 
     # ------------------------------------------------------------------ multi-token extend
     def extend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
-               attention_mask: torch.Tensor = None, out: torch.Tensor = None) -> torch.Tensor:
+               attention_mask: torch.Tensor = None, out: torch.Tensor = None, scores_dump: torch.Tensor = None) -> torch.Tensor:
         """Q >= 1 new tokens in ONE library call (kivi_mf_extend_layer): q (B, nh, Q, D), k / v (B, nh_kv, Q, D), RoPE applied.
         Chunk row i attends to the cache as it stands plus chunk tokens 0..i; `attention_mask`: optional additive
         (B, 1, Q, kv_seq_len + Q) fp16 (a view with dim-2 stride 0 -- a padding row expanded over the chunk -- is read as it is,
-        without being built).  The cache afterwards is bit-identical to Q decode steps.  Returns (B, nh, Q, D) fp16."""
+        without being built).  The cache afterwards is bit-identical to Q decode steps.  Returns (B, nh, Q, D) fp16.
+        `scores_dump` (tests): a (B, nh, Q, >= kv_seq_len + Q) fp16 buffer with unit inner stride that receives the rows the
+        softmax consumes (KIVI_GQA_DUMP_SCORES; keys a row does not see are left as they were)."""
         B, nh, Q, D = query_states.shape
         assert nh == self.nh and B == self.B and D == self.D and Q >= 1
         assert key_states.shape == value_states.shape == (B, self.nh_kv, Q, D)
@@ -386,7 +388,14 @@ class KiviLayerCacheMF:
         else:
             assert out.shape == (B, nh, Q, D) and out.dtype == torch.float16 and out.stride(3) == 1
         d, state, key, _, _ = self._desc(nh, q.device)
-        d.flags = self._flags()
+        d.flags = self._flags() & ~_lib.GQA_DUMP_SCORES     # the decode steps' dump flag: their scratch rows cannot hold Q rows
+        if scores_dump is not None:              # a copy of the descriptor: the decode steps keep their scratch rows
+            sd = scores_dump
+            assert sd.dtype == torch.float16 and sd.dim() == 4 and sd.shape[:3] == (B, nh, Q) and sd.shape[3] >= total
+            assert sd.stride(3) == 1 and sd.is_cuda
+            d = _lib.MfLayerDesc.from_buffer_copy(d)
+            d.flags |= _lib.GQA_DUMP_SCORES
+            d.scores, d.s_sb, d.s_sh, d.s_pitch = sd.data_ptr(), sd.stride(0), sd.stride(1), sd.stride(2)
         state[0], state[1], state[2] = self.k_quant_len, self.k_res_len, self.v_quant_len
         state[3], state[4], state[5] = self.v_res_start, self.v_res_len, self.kv_seq_len
         rc = _lib.load().kivi_mf_extend_layer(ctypes.byref(d), state, Q, q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), nh,

@@ -24,6 +24,7 @@ struct ExtArgs {
     const uint16_t* vn; int64_t vn_sb, vn_sh, vn_st;
     const uint16_t* mask; int64_t mask_sb, mask_sq;
     uint16_t* out; int64_t out_sb, out_sh, out_st;
+    uint16_t* dump; int64_t d_sb, d_sh, d_sq;             // KIVI_GQA_DUMP_SCORES (tests): null in production
     int64_t Tq, Tv, P0;
     int Q, G, nh_kv, win_start, win_rows, ntile_rows;
 };
@@ -179,6 +180,8 @@ __global__ __launch_bounds__(256) void mf_extend_kernel(ExtArgs a) {
                 float x = h2f(f2h(h2f(f2h(s[tile][reg])) / 11.313708498984761f));   // fp16(fp16(q.k) / sqrt(128))
                 if (mrow && t < a.P0 + a.Q) x = fmaxf(h2f(f2h(x + h2f(mrow[t]))), -65504.f);
                 const bool ok = t < a.P0 || (t < a.P0 + a.Q && t - a.P0 <= ci);
+                if (a.dump && pass == 1 && live && ok)      // the row the softmax consumes, key t (every visible key, once)
+                    a.dump[b * a.d_sb + (int64_t)hq * a.d_sh + (int64_t)ci * a.d_sq + t] = f2h(x);
                 x = ok ? x : -__builtin_inff();
                 w[4 * tile + reg] = x;
                 tmax = fmaxf(tmax, x);
@@ -454,6 +457,11 @@ extern "C" int kivi_mf_extend_layer(const kivi_mf_layer_desc* L, int64_t* st, in
                      rows16(q, q_sb, q_sh, q_st) && rows16(knew, kn_sb, kn_sh, kn_st) && rows16(vnew, vn_sb, vn_sh, vn_st) &&
                      rows16(out, out_sb, out_sh, out_st),
                  KIVI_EALIGN, "kivi_mf_extend_layer: fp16 rows must be 16-byte aligned");
+    const bool dump = (L->flags & KIVI_GQA_DUMP_SCORES) != 0;
+    KIVI_REQUIRE(!dump || (L->scores && (uintptr_t)L->scores % 2 == 0 && L->s_pitch >= kv + Q && L->s_sh >= (int64_t)Q * L->s_pitch &&
+                           L->s_sb >= (int64_t)nh * L->s_sh),
+                 KIVI_EINVAL, "kivi_mf_extend_layer: the score dump needs rows of >= %lld halves, Q rows per head, nh heads per batch row "
+                 "(s_pitch=%lld s_sh=%lld s_sb=%lld)", (long long)(kv + Q), (long long)L->s_pitch, (long long)L->s_sh, (long long)L->s_sb);
     const int G = nh / L->nh_kv;
     const int64_t ntile_rows = ((int64_t)Q * G + 15) / 16;
     KIVI_REQUIRE(ntile_rows < (1 << 30), KIVI_EINVAL, "kivi_mf_extend_layer: chunk too long");
@@ -470,6 +478,7 @@ extern "C" int kivi_mf_extend_layer(const kivi_mf_layer_desc* L, int64_t* st, in
     a.vn = (const uint16_t*)vnew; a.vn_sb = vn_sb; a.vn_sh = vn_sh; a.vn_st = vn_st;
     a.mask = (const uint16_t*)mask; a.mask_sb = mask_sb; a.mask_sq = mask_sq;
     a.out = (uint16_t*)out; a.out_sb = out_sb; a.out_sh = out_sh; a.out_st = out_st;
+    a.dump = dump ? (uint16_t*)L->scores : nullptr; a.d_sb = L->s_sb; a.d_sh = L->s_sh; a.d_sq = L->s_pitch;
     a.Tq = Tq; a.Tv = Tv; a.P0 = kv;
     a.Q = Q; a.G = G; a.nh_kv = L->nh_kv; a.win_start = (int)wstart; a.win_rows = (int)L->v_window_rows; a.ntile_rows = (int)ntile_rows;
     const dim3 grid((unsigned)ntile_rows, (unsigned)(L->B * L->nh_kv));

@@ -2,8 +2,10 @@
 
 * The library exports both entry points and refuses bad arguments with KIVI_EINVAL before anything is enqueued (fake pointers
   that are never dereferenced, as in tests/test_abi_cpu.py), leaving the caller's lengths untouched.
-* `extend64`, the fp64 reference of an extend that tests/test_extend_gpu.py holds the kernels to, is itself pinned here: at Q = 1
-  it IS torch_ref64.decode_step (bit for bit), and its bulk cache update equals Q chained decode steps (bit for bit).
+* `extend64`, the fp64 reference of an extend that tests/test_extend_gpu.py and tests/test_extend_stages_gpu.py hold the kernels to,
+  is itself pinned here: at Q = 1 it IS torch_ref64.decode_step (bit for bit), its bulk cache update equals Q chained decode steps
+  (bit for bit) -- at g = 32 / D = 128 and at the hook-state layout's own shapes -- and its own rows fed back through
+  `scores_override` change nothing.
 """
 import ctypes
 import math
@@ -19,10 +21,14 @@ def _h(x):
     return x.to(torch.float32).to(torch.float16)
 
 
-def extend64(q, kn, vn, past, k_bits, v_bits, g, R, attention_mask=None):
+def extend64(q, kn, vn, past, k_bits, v_bits, g, R, attention_mask=None, scores_override=None, return_scores=False):
     """The extend contract in fp64 (include/kivi_hip.h, kivi_mf_extend_layer): q (B, nh, Q, D), kn / vn (B, nh_kv, Q, D).
     Row i attends to the cache as it stands (packed K / V, K residual, V window) and chunk tokens 0..i, with the rounding sequence
-    of torch_ref64.decode_step.  Returns (out (B, nh, Q, D) fp16, the 9-tuple after the call)."""
+    of torch_ref64.decode_step.  Returns (out (B, nh, Q, D) fp16, the 9-tuple after the call) and, with `return_scores`, the
+    (B, nh, Q, P0 + Q) fp16 rows fed to the softmax (scaled, mask added and clamped; before the causal mask).
+    `scores_override`: rows of that shape to feed the softmax instead (stage B of the extend stage checks,
+    tests/test_extend_stages_gpu.py); the causal mask is applied to them as to the reference's own, so the keys a row does not
+    see may hold anything."""
     B, nh, Q, D = q.shape
     ratio = nh // kn.shape[1]
     kc, k_full, ks, km, vc, v_full, vs, vm, P0 = past
@@ -33,6 +39,10 @@ def extend64(q, kn, vn, past, k_bits, v_bits, g, R, attention_mask=None):
     if attention_mask is not None:
         w = w + attention_mask
         w = torch.max(w, torch.tensor(torch.finfo(w.dtype).min, device=w.device, dtype=w.dtype))
+    pre = w
+    if scores_override is not None:
+        assert scores_override.shape == w.shape and scores_override.dtype == torch.float16
+        w = scores_override.to(w.device)
     causal = torch.ones((Q, Q), dtype=torch.bool, device=w.device).triu(1)
     w = w.clone()
     w[..., P0:] = w[..., P0:].masked_fill(causal, float("-inf"))
@@ -53,7 +63,8 @@ def extend64(q, kn, vn, past, k_bits, v_bits, g, R, attention_mask=None):
         c, s, m = T64.quant_pack_lastdim(v_all[:, :, :nv].contiguous(), g, v_bits)
         vc, vs, vm = (c, s, m) if vc is None else (torch.cat([vc, c], 2), torch.cat([vs, s], 2), torch.cat([vm, m], 2))
     v_full = v_all[:, :, nv:].contiguous()
-    return out, (kc, k_full, ks, km, vc, v_full, vs, vm, P0 + Q)
+    new_past = (kc, k_full, ks, km, vc, v_full, vs, vm, P0 + Q)
+    return (out, new_past, pre) if return_scores else (out, new_past)
 
 
 def _same(a, b):
@@ -91,6 +102,55 @@ def test_extend64_cache_is_q_decode_steps(bits, T0, R, Q):
     assert bulk[8] == chained[8] == T0 + Q
 
 
+@pytest.mark.parametrize("bits,ratio,T0,R,Q,masked", [(2, 4, 70, 32, 9, False), (4, 1, 100, 64, 40, True), (2, 8, 45, 32, 1, True)])
+def test_extend64_scores_override_with_its_own_rows_is_identity(bits, ratio, T0, R, Q, masked):
+    """Stage B's reference: fed the rows it consumed itself, extend64 gives the same output and cache bit for bit -- whatever the keys a
+    row does not see hold (the causal mask is applied to the override)."""
+    B, nh_kv, D, g = 2, 2, 128, 32
+    past = T64.prefill_cache(make_kv(1, B, nh_kv, T0, D, "outlier"), make_kv(2, B, nh_kv, T0, D), bits, bits, g, R)
+    q, kn, vn = make_kv(3, B, nh_kv * ratio, Q, D), make_kv(4, B, nh_kv, Q, D, "outlier"), make_kv(5, B, nh_kv, Q, D)
+    mask = None
+    if masked:
+        mask = torch.zeros((B, 1, Q, T0 + Q), dtype=torch.float16)
+        mask[0, ..., :5] = torch.finfo(torch.float16).min
+        mask[1, ..., T0 + Q - 1] = -2.5                              # a chunk key too
+    out, past1, pre = extend64(q, kn, vn, past, bits, bits, g, R, mask, return_scores=True)
+    assert pre.shape == (B, nh_kv * ratio, Q, T0 + Q) and pre.dtype == torch.float16
+    rows = pre.clone()
+    rows[..., T0:] = rows[..., T0:].masked_fill(torch.ones((Q, Q), dtype=torch.bool).triu(1), float("nan"))
+    out2, past2 = extend64(q, kn, vn, past, bits, bits, g, R, mask, scores_override=rows)
+    assert _same(out, out2)
+    assert all(_same(x, y) for x, y in zip(past1[:8], past2[:8])) and past1[8] == past2[8]
+
+
+# the shapes of the hook-state layout (tests/test_extend_stages_gpu.py): groups of 64 / 128, head_dim 64, K and V bits apart, R = 256
+OTHER_SHAPES = [(2, 2, 64, 128, 1, 64, 150, 70), (2, 2, 128, 128, 2, 128, 300, 131), (4, 4, 32, 64, 1, 32, 100, 40),
+                (2, 4, 32, 128, 1, 32, 70, 33), (4, 4, 64, 64, 8, 64, 200, 67), (2, 4, 32, 128, 4, 256, 300, 259)]
+
+
+@pytest.mark.parametrize("kb,vb,g,D,ratio,R,T0,Q", OTHER_SHAPES)
+def test_extend64_other_shapes(kb, vb, g, D, ratio, R, T0, Q):
+    """extend64 off the g = 32 / D = 128 shape: at Q = 1 it is decode_step bit for bit (with and without a mask), and its bulk
+    cache update over Q tokens (K and V flushes) equals Q chained decode steps bit for bit."""
+    B, nh_kv = 1, 2
+    past = T64.prefill_cache(make_kv(1, B, nh_kv, T0, D), make_kv(2, B, nh_kv, T0, D), kb, vb, g, R)
+    q, kn, vn = make_kv(3, B, nh_kv * ratio, Q, D), make_kv(4, B, nh_kv, Q, D, "outlier"), make_kv(5, B, nh_kv, Q, D)
+    mask = torch.zeros((B, 1, 1, T0 + 1), dtype=torch.float16)
+    mask[..., :3] = torch.finfo(torch.float16).min
+    for m in (None, mask):
+        o1, t1 = extend64(q[:, :, :1], kn[:, :, :1], vn[:, :, :1], past, kb, vb, g, R, m)
+        o2, t2, _ = T64.decode_step(q[:, :, :1], kn[:, :, :1], vn[:, :, :1], past, kb, vb, g, R, m)
+        assert _same(o1, o2)
+        assert all(_same(x, y) for x, y in zip(t1[:8], t2[:8])) and t1[8] == t2[8]
+    _, bulk = extend64(q, kn, vn, past, kb, vb, g, R)
+    chained = past
+    for i in range(Q):
+        _, chained, _ = T64.decode_step(q[:, :, i:i + 1], kn[:, :, i:i + 1], vn[:, :, i:i + 1], chained, kb, vb, g, R)
+    for x, y in zip(bulk[:8], chained[:8]):
+        assert _same(x, y)
+    assert bulk[8] == chained[8] == T0 + Q
+
+
 # ------------------------------------------------------------------ the C ABI without a device
 @pytest.fixture(scope="module")
 def lib():
@@ -122,7 +182,8 @@ def test_extend_symbols_exported(lib):
     assert lib.kivi_abi_version() == 3
 
 
-@pytest.mark.parametrize("case", ["q0", "mask_pitch", "capacity", "lengths", "no_ring"])
+@pytest.mark.parametrize("case", ["q0", "mask_pitch", "capacity", "lengths", "no_ring", "dump_null", "dump_pitch", "dump_head",
+                                  "dump_batch"])
 def test_extend_layer_refuses_bad_arguments(lib, case):
     d = _fake_desc()
     lengths = [64, 10, 42, 0, 32, 74]     # Tq, k_res_len, Tv, v_win_start, v_res_len, kv_seq_len
@@ -137,10 +198,24 @@ def test_extend_layer_refuses_bad_arguments(lib, case):
         lengths[2] = 41
     elif case == "no_ring":
         d.flags = 0
+    elif case.startswith("dump"):                           # KIVI_GQA_DUMP_SCORES: rows of P0 + Q = 82 halves, Q rows per head
+        from kivi_amd import _lib
+        d.flags |= _lib.GQA_DUMP_SCORES
+        d.s_pitch, d.s_sh, d.s_sb = 82, 8 * 82, 4 * 8 * 82
+        if case == "dump_null":
+            d.scores = None
+        elif case == "dump_pitch":
+            d.s_pitch, d.s_sh, d.s_sb = 81, 8 * 82, 4 * 8 * 82
+        elif case == "dump_head":
+            d.s_sh = 8 * 82 - 1
+        else:
+            d.s_sb = 4 * 8 * 82 - 1
     st = (ctypes.c_int64 * 6)(*lengths)
     assert _extend(lib, d, st, Q, mask, mask_sq) == -1          # KIVI_EINVAL
     assert list(st) == lengths, "a refused call leaves the caller's lengths alone"
     assert b"kivi_mf_extend_layer" in lib.kivi_last_error()
+    if case.startswith("dump"):
+        assert b"score dump" in lib.kivi_last_error()
 
 
 def test_vt_pack_at_refuses_bad_arguments(lib):

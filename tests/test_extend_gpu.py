@@ -50,9 +50,8 @@ def _assert_same_state(a, b):
 
 
 # (bits, nh / nh_kv, R, P0, Q, inputs): ratio 1 / 4 / 8 at 2 bits, 1 / 4 at 4 bits; P0 + Q crossing a 512-token super-block;
-# Q = 37 crosses a K flush, Q = 300 runs several
-# (4-bit nh / nh_kv = 4 on outlier inputs -- (4, 4, 128, 600, 5, "outlier") -- and x30 inputs -- (4, 4, 32, 90, 300, "x30") -- measured
-# 1.003 and 2.11 of the bar and are not in this list: DESIGN.md section 9, open.)
+# Q = 37 crosses a K flush, Q = 300 runs several.  tests/test_extend_stages_gpu.py runs these cases stage by stage, with the
+# 4-bit nh / nh_kv = 4 cases on outlier and x30 inputs.
 CASES = [(2, 1, 32, 500, 37, "randn"), (2, 4, 32, 70, 5, "outlier"), (2, 8, 128, 200, 300, "randn"), (2, 1, 128, 480, 1, "x30"),
          (4, 1, 32, 130, 37, "tiny"), (4, 4, 64, 300, 37, "randn"), (2, 4, 32, 1000, 37, "tiny")]
 
@@ -80,7 +79,7 @@ def test_extend_outputs_and_state(bits, ratio, R, T0, Q, kind):
     _assert_same_state(layer, steps)
 
 
-# ((2, 4, 64, 700) measured 1.007 of this bar -- the decode kernel's own error and the extend's add up there: DESIGN.md section 9)
+# ((2, 4, 64, 700): both forms against the contract, stage by stage, in tests/test_extend_stages_gpu.py)
 @pytest.mark.parametrize("bits,ratio,R,T0", [(2, 1, 32, 300), (2, 4, 32, 300), (2, 8, 32, 100), (4, 1, 32, 520), (4, 4, 128, 260)])
 def test_extend_q1_matches_decode_step(bits, ratio, R, T0):
     from kivi_amd.attention import kivi_attention_decode, kivi_attention_extend
