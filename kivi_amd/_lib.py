@@ -257,3 +257,42 @@ def require_gpu(t: torch.Tensor, name: str) -> None:
 
 def ptr(t: torch.Tensor) -> ctypes.c_void_p:
     return ctypes.c_void_p(t.data_ptr())
+
+
+# --------------------------------------------------------------------------- tensors -> arguments of a layer step
+def unit_rows(x: torch.Tensor) -> torch.Tensor:
+    """`x` if its inner stride is 1 (what every kernel that reads rows needs), a contiguous copy otherwise."""
+    return x if x.stride(3) == 1 else x.contiguous()
+
+
+def rows16(x: torch.Tensor) -> torch.Tensor:
+    """16-byte loads of whole rows: unit inner stride, 16-byte aligned rows (a copy otherwise)."""
+    ok = x.stride(3) == 1 and x.data_ptr() % 16 == 0 and x.stride(0) % 8 == 0 and x.stride(1) % 8 == 0
+    return x if ok else x.contiguous()
+
+
+def check_mask_size(attention_mask: torch.Tensor, size: tuple) -> None:
+    """The reference's complaint about an additive mask of the wrong shape (llama_kivi.py:364-368)."""
+    if attention_mask.size() != size:
+        raise ValueError(f"Attention mask should be of size {size}, but is {attention_mask.size()}")
+
+
+def mask_arg(attention_mask, B: int, kv_len: int, wider: bool = False):
+    """(pointer, batch stride) of a decode step's additive (B, 1, 1, kv_len) fp16 mask; (None, 0) without one.  `wider`: a static
+    buffer whose rows are longer than the step's row (graph replays) passes."""
+    if attention_mask is None:
+        return None, 0
+    if wider:
+        assert attention_mask.shape[3] >= kv_len
+    else:
+        check_mask_size(attention_mask, (B, 1, 1, kv_len))
+    assert attention_mask.dtype == torch.float16 and attention_mask.stride(3) == 1
+    return attention_mask.data_ptr(), attention_mask.stride(0)
+
+
+def out_arg(out, shape: tuple, device) -> torch.Tensor:
+    """The fp16 result buffer of a layer step: the caller's (checked) or a new one."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float16, device=device)
+    assert out.shape == shape and out.dtype == torch.float16 and out.stride(3) == 1
+    return out

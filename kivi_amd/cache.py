@@ -23,14 +23,19 @@ Cache policy (llama_kivi.py:343-356, 386-399, 425-452):
 """
 from __future__ import annotations
 
+import copy
+import ctypes
 import math
+import warnings
 from dataclasses import dataclass
 from typing import Optional
 
 import torch
+import torch.nn.functional as F
 
-from . import _tuning
-from .quant import new_pack
+from . import _lib, _tuning, reorder
+from ._lib import KiviUnsupported, check_mask_size, mask_arg, out_arg, unit_rows
+from .quant import fused, matmul, new_pack
 
 PAGE_TOKENS = 2048   # = the tile of the default qK^T kernels (64 lanes x 2 words x 16 codes; 4-bit: 4 words x 8)
 
@@ -75,15 +80,151 @@ class KiviConfig:
         assert self.residual_length % self.group_size == 0  # llama_kivi.py:344
 
 
-class KiviLayerCache:
+_FUSION_ENV = _tuning.knob("KIVI_DECODE_FUSION")   # tuning sessions: "attend" (2 launches), "softmax" (3), "separate" (4)
+
+
+def _fusion_level() -> int:
+    """How much of the decode step goes into the sV launch: 2 = everything after the packed qK^T (kivi_decode_attend),
+    1 = softmax + output, 0 = output only (softmax as its own launch).  Level 2 covers every tuned shape: for short
+    MHA rows the block that owns a row does the row's softmax before it starts streaming; for grouped queries / long
+    rows the library splits rows over blocks and adds a row-statistics launch (kivi_gemv_v.hip, v_run)."""
+    if _FUSION_ENV:
+        return {"attend": 2, "softmax": 1, "separate": 0}[_FUSION_ENV]
+    return 2
+
+
+_HOOK = None
+
+
+def _hook():
+    """kivi_amd.attention (which imports this module): KIVI_NATIVE_STEP lives there as `_NATIVE_STEP`, and tests switch it between
+    two steps, so it is read at every step."""
+    global _HOOK
+    if _HOOK is None:
+        from . import attention
+        _HOOK = attention
+    return _HOOK
+
+
+class KiviPerformanceWarning(UserWarning):
+    """A decode step left the fused kernels for a slower composition (results unchanged)."""
+
+
+class KiviCacheBase:
+    """What the two layouts of a layer's cache (KiviLayerCache here, KiviLayerCacheMF in cache_mf.py) share: the geometry, the six
+    lengths of the state machine, the scratch of a decode step, and everything that follows from them alone.  A layout adds its
+    buffers (`reserve`, `_own_buffers`, `_reorder_slabs`, `prefill`), the readers of the reference layout
+    (`k_quant_reference_layout`, `v_quant_views`, `v_res_view`) and its steps (`decode_step`, `extend`)."""
+
+    def __init__(self, cfg: KiviConfig, batch: int, num_kv_heads: int, head_dim: int, max_len: int, dtype):
+        assert dtype == torch.float16, "the reference extension is fp16 only (gemv_cuda.cu:526-529)"
+        self.cfg = cfg
+        R = cfg.residual_length
+        self.B, self.nh_kv, self.D = batch, num_kv_heads, head_dim
+        self.cap = ((max_len + R - 1) // R) * R
+        self.k_quant_len = 0   # tokens in the packed K prefix (multiple of R)
+        self.k_res_len = 0     # tokens in the fp16 K residual (< R between steps)
+        self.v_quant_len = 0   # tokens in the packed V prefix
+        self.v_res_start = 0
+        self.v_res_len = 0     # tokens in the fp16 V window (<= R between steps)
+        self.kv_seq_len = 0
+        self._native = None    # (descriptor, int64[6] state array, key, entry point, scratch) of the layout's one-call step
+        self._scores = self._probs = None     # (B, nh, 1, pitch) fp16 scratch rows of the multi-launch forms (hook-state layout)
+        # fusion levels this cache has left for good (hook-state layout: KiviLayerCache._drop_fusion)
+        self._attend_unfusable = self._softmax_unfusable = self._fused_unsupported = False
+
+    def _invalidate(self) -> None:
+        """Forget the native descriptor and the scratch rows: they point into / are sized for buffers that have just been replaced."""
+        self._native = self._scores = self._probs = None
+
+    # ------------------------------------------------------------------ the six lengths <-> the int64[6] state array of the library
+    def _store_state(self, state) -> None:
+        state[0], state[1], state[2], state[3], state[4], state[5] = (
+            self.k_quant_len, self.k_res_len, self.v_quant_len, self.v_res_start, self.v_res_len, self.kv_seq_len)
+
+    def _load_state(self, state) -> None:
+        self.k_quant_len, self.k_res_len, self.v_quant_len, self.v_res_start, self.v_res_len, self.kv_seq_len = (
+            state[0], state[1], state[2], state[3], state[4], state[5])
+
+    # ------------------------------------------------------------------ capacity, copies
+    def ensure_room(self, tokens: int = 1) -> None:
+        """Make room for `tokens` more tokens, doubling the capacity when it runs out (amortised O(1) copies)."""
+        need = self.kv_seq_len + tokens
+        if need > self.cap:
+            self.reserve(max(need, 2 * self.cap))
+
+    def clone(self):
+        """Independent copy of the cache (what holding on to an old reference tuple gives for free): use it to continue one
+        prefix twice (beam / contrastive / assisted decoding)."""
+        other = copy.copy(self)
+        other._own_buffers(None)
+        other._invalidate()
+        return other
+
+    def index_select(self, idx):
+        """A new cache of len(idx) rows, row i a bit-identical copy of row idx[i] (whole rows): the fork of B requests into
+        B * num_beams beams."""
+        idx = torch.as_tensor(idx, device=self.k_res.device).long().flatten()
+        if idx.numel() == 0 or not bool(((idx >= 0) & (idx < self.B)).all()):
+            raise ValueError(f"index_select: indices must lie in [0, {self.B})")
+        other = copy.copy(self)
+        other.B = idx.numel()
+        other._own_buffers(idx)
+        other._invalidate()
+        return other
+
+    # ------------------------------------------------------------------ beam search (DESIGN.md section 11)
+    def reorder_(self, idx, group: Optional[int] = None, from_token: int = 0, check: bool = True):
+        """row[b] <- row[idx[b]] in place (one kivi_cache_reorder launch): `idx` (B,) int32 / int64, idx[b] in b's group of `group`
+        consecutive rows (default: B, an arbitrary reorder).  Only what was written from token `from_token` on moves -- rows of a
+        group must be identical before it (beams forked at that length); 0 moves the rows up to the lengths in use.  Buffers,
+        lengths and the native descriptors stay valid.  `check=False` skips the host-side check of the index values (a device
+        read): the kernel leaves a row whose index lies outside its group as it is."""
+        group = self.B if group is None else int(group)
+        if not 0 <= int(from_token) <= self.kv_seq_len:
+            raise ValueError(f"from_token={from_token} lies beyond the cache length {self.kv_seq_len}")
+        idx = reorder.check_idx(idx, self.B, group, self.k_res.device, check)
+        reorder.run(self._reorder_slabs(int(from_token)), self.B, group, idx)
+        return self
+
+    # ------------------------------------------------------------------ the 9-tuple
+    def k_res_view(self) -> Optional[torch.Tensor]:
+        return self.k_res[:, :, : self.k_res_len] if self.k_res_len else None
+
+    def _tuple_members(self):
+        kc, ks, km = self.k_quant_reference_layout()
+        vc, vs, vm = self.v_quant_views()
+        return (kc, self.k_res_view(), ks, km, vc, self.v_res_view(), vs, vm)
+
+    def as_tuple(self) -> KiviCacheTuple:
+        return KiviCacheTuple(self)
+
+    def nbytes(self) -> int:
+        """Resident cache bytes = what the reference's 9-tuple tensors would hold for the same state."""
+        c = self.cfg
+        per_k = self.D * self.k_quant_len * c.k_bits // 8 + 2 * self.D * (self.k_quant_len // c.group_size) * 2
+        per_v = self.v_quant_len * self.D * c.v_bits // 8 + 2 * self.v_quant_len * (self.D // c.group_size) * 2
+        res = (self.k_res_len + self.v_res_len) * self.D * 2
+        return self.B * self.nh_kv * (per_k + per_v + res)
+
+    def _adopt_residuals(self, past) -> None:
+        """The fp16 members and the lengths of a plain reference 9-tuple (the packed members: the layout's from_tuple)."""
+        kfull, vfull = past[1], past[5]
+        if kfull is not None:
+            self.k_res_len = kfull.shape[2]
+            self.k_res[:, :, : self.k_res_len].copy_(kfull)
+        self.v_res_len = vfull.shape[2]
+        self.v_res[:, :, : self.v_res_len].copy_(vfull)
+        self.kv_seq_len = int(past[8])
+
+
+class KiviLayerCache(KiviCacheBase):
     """One layer's quantised KV cache with capacity `max_len` tokens, appended in place."""
 
     def __init__(self, cfg: KiviConfig, batch: int, num_kv_heads: int, head_dim: int, max_len: int,
                  device, dtype=torch.float16, page_tokens: int = None):
-        assert dtype == torch.float16, "the reference extension is fp16 only (gemv_cuda.cu:526-529)"
-        self.cfg = cfg
+        super().__init__(cfg, batch, num_kv_heads, head_dim, max_len, dtype)
         R, g = cfg.residual_length, cfg.group_size
-        self.B, self.nh_kv, self.D = batch, num_kv_heads, head_dim
         assert head_dim % g == 0 and head_dim % (32 // cfg.v_bits) == 0
         if page_tokens is None:
             # a K flush of R tokens must not straddle pages AND a page is whole tiles of the default qK^T kernels: the smallest common
@@ -91,7 +232,6 @@ class KiviLayerCache:
             page_tokens = PAGE_TOKENS * R // math.gcd(PAGE_TOKENS, R)
         assert page_tokens % R == 0 and page_tokens % g == 0, "a K flush of R tokens must not straddle pages"
         self.page_tokens = page_tokens
-        self.cap = ((max_len + R - 1) // R) * R
         self.n_pages = (self.cap + page_tokens - 1) // page_tokens
         kf, vf = 32 // cfg.k_bits, 32 // cfg.v_bits
         dev = device
@@ -107,12 +247,6 @@ class KiviLayerCache:
         self.v_mn = torch.empty_like(self.v_scale)
         # fp16 V window: R (+1 transient) live tokens inside a 2R+1 buffer, compacted every R steps
         self.v_res = torch.empty((batch, num_kv_heads, 2 * R + 1, head_dim), dtype=dtype, device=dev)
-        self.k_quant_len = 0   # tokens in the packed K prefix (multiple of R)
-        self.k_res_len = 0     # tokens in the fp16 K residual (< R between steps)
-        self.v_quant_len = 0   # tokens in the packed V prefix
-        self.v_res_start = 0
-        self.v_res_len = 0     # tokens in the fp16 V window (<= R between steps)
-        self.kv_seq_len = 0
 
     @staticmethod
     def _paged(shape, dtype, device) -> torch.Tensor:
@@ -147,44 +281,17 @@ class KiviLayerCache:
             self.n_pages = n_pages
         self.v_code, self.v_scale, self.v_mn = (grown(x, 2, cap) for x in (self.v_code, self.v_scale, self.v_mn))
         self.cap = cap
-        for name in ("_native", "_scores", "_probs"):
-            if hasattr(self, name):
-                delattr(self, name)
+        self._invalidate()
 
-    def ensure_room(self, tokens: int = 1) -> None:
-        """Make room for `tokens` more tokens, doubling the capacity when it runs out (amortised O(1) copies)."""
-        need = self.kv_seq_len + tokens
-        if need > self.cap:
-            self.reserve(max(need, 2 * self.cap))
-
-    def clone(self) -> "KiviLayerCache":
-        """Independent copy of the cache (what holding on to an old reference tuple gives for free): use it to continue one
-        prefix twice (beam / contrastive / assisted decoding)."""
-        import copy
-        other = copy.copy(self)
-        for name in ("k_code", "k_scale", "k_mn", "k_res", "v_code", "v_scale", "v_mn", "v_res"):
+    def _own_buffers(self, idx) -> None:
+        """Replace the buffers (still those of the cache this one was copied from) by copies of their own: whole, or rows `idx`."""
+        for name in ("k_code", "k_scale", "k_mn"):
             src = getattr(self, name)
-            dst = torch.empty_strided(src.shape, src.stride(), dtype=src.dtype, device=src.device)
-            dst.copy_(src)
-            setattr(other, name, dst)
-        for name in ("_native", "_scores", "_probs"):
-            other.__dict__.pop(name, None)
-        return other
-
-    # ------------------------------------------------------------------ beam search (DESIGN.md section 11)
-    def reorder_(self, idx, group: Optional[int] = None, from_token: int = 0, check: bool = True) -> "KiviLayerCache":
-        """row[b] <- row[idx[b]] in place (one kivi_cache_reorder launch): `idx` (B,) int32 / int64, idx[b] in b's group of `group`
-        consecutive rows (default: B, an arbitrary reorder).  Only what was written from token `from_token` on moves -- rows of a
-        group must be identical before it (beams forked at that length); 0 moves the rows up to the lengths in use.  Buffers,
-        lengths and the native descriptors stay valid.  `check=False` skips the host-side check of the index values (a device
-        read): the kernel leaves a row whose index lies outside its group as it is."""
-        from . import reorder
-        group = self.B if group is None else int(group)
-        if not 0 <= int(from_token) <= self.kv_seq_len:
-            raise ValueError(f"from_token={from_token} lies beyond the cache length {self.kv_seq_len}")
-        idx = reorder.check_idx(idx, self.B, group, self.k_res.device, check)
-        reorder.run(self._reorder_slabs(int(from_token)), self.B, group, idx)
-        return self
+            dst = self._paged((self.B,) + tuple(src.shape[1:]), src.dtype, src.device)
+            setattr(self, name, dst.copy_(src if idx is None else src.index_select(0, idx)))
+        for name in ("k_res", "v_code", "v_scale", "v_mn", "v_res"):
+            src = getattr(self, name)
+            setattr(self, name, src.clone() if idx is None else src.index_select(0, idx))
 
     def _reorder_slabs(self, from_token: int):
         from .reorder import _span, slab
@@ -210,26 +317,6 @@ class KiviLayerCache:
             out.append(slab(self.v_res, b0, [(h, self.v_res.stride(1) * 2)], b1 - b0))
         return out
 
-    def index_select(self, idx) -> "KiviLayerCache":
-        """A new cache of len(idx) rows, row i a bit-identical copy of row idx[i] (whole rows): the fork of B requests into
-        B * num_beams beams."""
-        import copy
-        idx = torch.as_tensor(idx, device=self.k_res.device).long().flatten()
-        if idx.numel() == 0 or not bool(((idx >= 0) & (idx < self.B)).all()):
-            raise ValueError(f"index_select: indices must lie in [0, {self.B})")
-        other = copy.copy(self)
-        for name in ("k_code", "k_scale", "k_mn"):
-            src = getattr(self, name)
-            dst = self._paged((idx.numel(),) + tuple(src.shape[1:]), src.dtype, src.device)
-            dst.copy_(src.index_select(0, idx))
-            setattr(other, name, dst)
-        for name in ("k_res", "v_code", "v_scale", "v_mn", "v_res"):
-            setattr(other, name, getattr(self, name).index_select(0, idx))
-        other.B = idx.numel()
-        for name in ("_native", "_scores", "_probs"):
-            other.__dict__.pop(name, None)
-        return other
-
     # ------------------------------------------------------------------ the 9-tuple
     def k_quant_reference_layout(self):
         """(K_code_T, K_scale_T, K_mn_T) in the reference layout (B, nh_kv, D, Tq/...): gathers the pages (a copy)."""
@@ -250,27 +337,8 @@ class KiviLayerCache:
         n = self.v_quant_len
         return self.v_code[:, :, :n], self.v_scale[:, :, :n], self.v_mn[:, :, :n]
 
-    def k_res_view(self) -> Optional[torch.Tensor]:
-        return self.k_res[:, :, : self.k_res_len] if self.k_res_len else None
-
     def v_res_view(self) -> torch.Tensor:
         return self.v_res[:, :, self.v_res_start: self.v_res_start + self.v_res_len]
-
-    def _tuple_members(self):
-        kc, ks, km = self.k_quant_reference_layout()
-        vc, vs, vm = self.v_quant_views()
-        return (kc, self.k_res_view(), ks, km, vc, self.v_res_view(), vs, vm)
-
-    def as_tuple(self) -> KiviCacheTuple:
-        return KiviCacheTuple(self)
-
-    def nbytes(self) -> int:
-        """Resident cache bytes = what the reference's 9-tuple tensors would hold for the same state."""
-        c = self.cfg
-        per_k = self.D * self.k_quant_len * c.k_bits // 8 + 2 * self.D * (self.k_quant_len // c.group_size) * 2
-        per_v = self.v_quant_len * self.D * c.v_bits // 8 + 2 * self.v_quant_len * (self.D // c.group_size) * 2
-        res = (self.k_res_len + self.v_res_len) * self.D * 2
-        return self.B * self.nh_kv * (per_k + per_v + res)
 
     def allocated_bytes(self) -> int:
         return sum(x.numel() * x.element_size() for x in (self.k_code, self.k_scale, self.k_mn, self.k_res, self.v_code,
@@ -367,6 +435,209 @@ class KiviLayerCache:
             self.v_res_start += 1
             self.v_res_len -= 1
 
+    # ------------------------------------------------------------------ decode step (llama_kivi.py:314-399)
+    def decode_step(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
+                    attention_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                    fused_kernels: bool = True) -> torch.Tensor:
+        """One new token: query (B, nh, 1, D), key / value (B, nh_kv, 1, D), RoPE applied -> (B, nh, 1, D) fp16 (`out` when the
+        one-call step ran, a new tensor otherwise).  The most fused form the shape has a kernel for: one library call, the fused
+        launches with the bookkeeping in Python, or -- also with `fused_kernels=False` -- the reference's op sequence composed
+        from the fused GEMVs and torch ops."""
+        cfg = self.cfg
+        B, nh, q_len, D = query_states.shape
+        assert q_len == 1, "decode branch: one new token (the reference kernel is q_len == 1 only)"
+        if fused_kernels and not self._fused_unsupported:
+            if _hook()._NATIVE_STEP and _fusion_level() == 2 and not self._attend_unfusable:
+                try:
+                    return self._decode_native(query_states, key_states, value_states, attention_mask, out)
+                except KiviUnsupported as e:         # the Python path below picks the next fusion level
+                    self._drop_fusion("_attend_unfusable", "the one-call layer step (kivi_decode_layer) is not available", str(e))
+            try:
+                return self._decode_fused(query_states, key_states, value_states, attention_mask)
+            except KiviUnsupported as e:          # shape without a tuned kernel: compose the unfused ops from now on
+                self._drop_fusion("_fused_unsupported", "no fused decode kernel covers the shape: composing the reference's op sequence "
+                                  "from the fused GEMVs and torch ops", str(e))
+        nh_kv = self.nh_kv
+        rep = nh // nh_kv
+        kv_seq_len = self.kv_seq_len + 1                                     # llama_kivi.py:307-309
+        g = cfg.group_size
+
+        # ---- scores over [quantised K prefix | fp16 K residual]  (:323-341)
+        Tq = self.k_quant_len
+        scores = self._row_buffer("_scores", nh)[..., :kv_seq_len]
+        if Tq:   # :324, reading the K pages in place and writing straight into the scores buffer (scratch: may still raise)
+            matmul.gemv_k_paged(g, query_states, self.k_code, self.k_scale, self.k_mn, Tq, cfg.k_bits, out=scores[..., :Tq])
+        self.append_k(key_states)                                            # :333-336
+        k_full = self.k_res_view()                                           # (B, nh_kv, L, D)
+        att_qkfull = torch.matmul(query_states.reshape(B, nh_kv, rep, D), k_full.transpose(2, 3))  # :337 (repeat_kv folded)
+        scores[..., Tq:].copy_(att_qkfull.view(B, nh, 1, -1))
+        attn_weights = scores / math.sqrt(D)                                  # :339, fp16 division like the reference
+        self.maybe_flush_k()                                                  # :343-356
+
+        if attn_weights.size() != (B, nh, 1, kv_seq_len):
+            raise ValueError(f"Attention weights should be of size {(B, nh, 1, kv_seq_len)}, but is {attn_weights.size()}")
+        if attention_mask is not None:                                        # :364-372
+            check_mask_size(attention_mask, (B, 1, 1, kv_seq_len))
+            attn_weights = attn_weights + attention_mask
+            attn_weights = torch.max(attn_weights, torch.tensor(torch.finfo(attn_weights.dtype).min, device=attn_weights.device))
+        attn_weights = F.softmax(attn_weights, dim=-1, dtype=torch.float32).to(query_states.dtype)   # :375
+
+        attn_output = self._composed_output(attn_weights, value_states, nh)   # :377-399
+        self.kv_seq_len = kv_seq_len
+        return attn_output
+
+    def _drop_fusion(self, attr: str, what: str, why: str = "") -> None:
+        """Mark this cache as unable to use one fusion level and say so ONCE per layer and level: a shape without a tuned kernel
+        otherwise runs the slower composition forever without a word."""
+        if getattr(self, attr):
+            return
+        setattr(self, attr, True)
+        if _FUSION_ENV:          # a tuning session asked for the lower level
+            return
+        c = self.cfg
+        warnings.warn(f"kivi_amd: {what} for this cache (k_bits={c.k_bits} v_bits={c.v_bits} group={c.group_size} "
+                      f"residual={c.residual_length} head_dim={self.D} kv_heads={self.nh_kv}){': ' + why if why else ''} -- the step "
+                      f"runs as more, slower launches from now on; results are unchanged", KiviPerformanceWarning, stacklevel=4)
+
+    def _row_buffer(self, name: str, nh: int) -> torch.Tensor:
+        """(B, nh, 1, pitch) per-layer fp16 scratch row buffer (`_scores` / `_probs`), pitch = a multiple of 8 halves >= capacity + 1
+        (16-byte stores of the fused GEMV)."""
+        pitch = ((self.cap + 1 + 7) // 8) * 8
+        buf = getattr(self, name)
+        if buf is None or buf.shape[1] != nh:
+            buf = torch.empty((self.B, nh, 1, pitch), dtype=torch.float16, device=self.k_code.device)
+            setattr(self, name, buf)
+        return buf
+
+    def _native_desc(self, nh: int):
+        """The kivi_layer_desc of this layer (built once: buffers and strides never change), its state array."""
+        cached = self._native
+        if cached is not None and cached[2] == nh:
+            return cached
+        cfg = self.cfg
+        scores = self._row_buffer("_scores", nh)
+        ws = fused._workspace(self.k_code.device, self.B * nh, self.D)
+        kc, ks, kr, vc, vs, vr = self.k_code, self.k_scale, self.k_res, self.v_code, self.v_scale, self.v_res
+        d = _lib.LayerDesc(
+            B=self.B, nh_kv=self.nh_kv, D=self.D, k_bits=cfg.k_bits, v_bits=cfg.v_bits, group_size=cfg.group_size,
+            residual_length=cfg.residual_length, inv_scale=1.0 / math.sqrt(self.D),
+            cap=self.cap, page_tokens=self.page_tokens, v_window_rows=vr.shape[2], s_pitch=scores.shape[3],
+            k_code=kc.data_ptr(), kc_sb=kc.stride(0), kc_sh=kc.stride(1), kc_sp=kc.stride(2), kc_sr=kc.stride(3),
+            k_scale=ks.data_ptr(), k_mn=self.k_mn.data_ptr(), ks_sb=ks.stride(0), ks_sh=ks.stride(1), ks_sp=ks.stride(2),
+            ks_sr=ks.stride(3),
+            k_res=kr.data_ptr(), kr_sb=kr.stride(0), kr_sh=kr.stride(1), kr_st=kr.stride(2),
+            v_code=vc.data_ptr(), vc_sb=vc.stride(0), vc_sh=vc.stride(1), vc_sr=vc.stride(2),
+            v_scale=vs.data_ptr(), v_mn=self.v_mn.data_ptr(), vs_sb=vs.stride(0), vs_sh=vs.stride(1), vs_sr=vs.stride(2),
+            v_res=vr.data_ptr(), vr_sb=vr.stride(0), vr_sh=vr.stride(1), vr_st=vr.stride(2),
+            scores=scores.data_ptr(), s_sb=scores.stride(0), s_sh=scores.stride(1),
+            workspace=ws.data_ptr(), workspace_bytes=ws.numel() * ws.element_size())
+        state = (ctypes.c_int64 * 6)()
+        self._native = (d, state, nh, _lib.load().kivi_decode_layer, ws)   # ws: keeps the shared workspace alive
+        return self._native
+
+    def _decode_native(self, query_states, key_states, value_states, attention_mask, out=None) -> torch.Tensor:
+        """The whole step (both launches + cache bookkeeping + K flush) through ONE library call (kivi_decode_layer):
+        the host side of a layer step drops from ~40 us of Python to one ctypes call.  Same launches, same results as
+        _decode_fused; raises KiviUnsupported (state untouched) when no tuned kernel covers the shape."""
+        B, nh, _, D = query_states.shape
+        d, state, _, fn, _ = self._native_desc(nh)
+        q, k, v = unit_rows(query_states), unit_rows(key_states), unit_rows(value_states)
+        mask_ptr, mask_sb = mask_arg(attention_mask, B, self.kv_seq_len + 1)
+        self._store_state(state)
+        out = out_arg(out, (B, nh, 1, D), q.device)
+        hook = matmul.launch_hook
+        if hook is not None and self.k_quant_len:   # bench.py: bracket the qK^T dispatch (the first launch of the call)
+            hook("pre", "k", dict(B=B, nh=nh, nh_kv=self.nh_kv, K=D, N=self.k_quant_len, bits=self.cfg.k_bits,
+                                  group_size=self.cfg.group_size, v_bits=self.cfg.v_bits, Tv=self.v_quant_len,
+                                  k_res=self.k_res_len + 1, v_res=self.v_res_len + 1))
+        rc = fn(ctypes.byref(d), state, q.data_ptr(), q.stride(0), q.stride(1), nh, k.data_ptr(), k.stride(0), k.stride(1),
+                v.data_ptr(), v.stride(0), v.stride(1), mask_ptr, mask_sb, out.data_ptr(), out.stride(0), out.stride(1),
+                torch.cuda.current_stream(q.device).cuda_stream)
+        # the library writes `state` after every phase it has enqueued (a refused step leaves it untouched apart from a
+        # completed window compaction), so the lengths are read back whether or not the call succeeded
+        self._load_state(state)
+        if rc:
+            _lib.check(rc, "kivi_decode_layer")
+        return out
+
+    def _decode_fused(self, query_states, key_states, value_states, attention_mask) -> torch.Tensor:
+        """The decode step in two launches (three when only the separate softmax fits; +1 when the K residual fills up): same arithmetic and roundings as the
+        composed path of decode_step.  Raises KiviUnsupported when no tuned kernel covers the shape."""
+        cfg = self.cfg
+        B, nh, _, D = query_states.shape
+        kv_seq_len = self.kv_seq_len + 1
+        scores = self._row_buffer("_scores", nh)
+        probs = self._row_buffer("_probs", nh)
+        if attention_mask is not None:
+            check_mask_size(attention_mask, (B, 1, 1, kv_seq_len))
+        assert self.k_quant_len + self.k_res_len + 1 <= self.cap, "cache capacity exceeded"
+        if self.v_res_start + self.v_res_len + 1 > self.v_res.shape[2]:     # make room in the window buffer
+            self.compact_v_window()
+        out = torch.empty((B, nh, 1, D), dtype=torch.float16, device=query_states.device)
+        inv = 1.0 / math.sqrt(D)
+        flushed = None
+        level = _fusion_level()
+        if level < 2:
+            self._drop_fusion("_attend_unfusable", "fusion level lowered")
+        if level < 1:
+            self._drop_fusion("_softmax_unfusable", "fusion level lowered")
+        if not self._attend_unfusable:
+            # two launches: packed qK^T GEMV (:324), then residual scores + K append + softmax + output + V append/flush
+            # only the launches that may be refused sit inside the try (they write scratch rows until the attend launch
+            # runs); the bookkeeping follows once they have been enqueued
+            try:
+                if self.k_quant_len:
+                    matmul.gemv_k_paged(cfg.group_size, query_states, self.k_code, self.k_scale, self.k_mn, self.k_quant_len,
+                                        cfg.k_bits, out=scores[..., : self.k_quant_len])
+                flushed = fused.decode_attend(self, query_states, key_states, value_states, scores, out, inv, attention_mask)
+            except KiviUnsupported as e:             # e.g. rows too long for the LDS: use the three-launch form below
+                self._drop_fusion("_attend_unfusable", "the fused attend launch (residual scores + softmax + output in one launch) is not available", str(e))
+            else:
+                self.k_res_len += 1
+                self.maybe_flush_k()                                          # :343-356
+        if flushed is None:
+            fused.decode_scores(self, query_states, key_states, scores)      # :323-337 (+ the K append of :333-336)
+            self.k_res_len += 1                      # committed: the launch above appended the key
+            self.maybe_flush_k()                                              # :343-356
+            if not self._softmax_unfusable:
+                try:   # scale + mask + softmax (:339, :364-375) inside the sV launch (:377-399)
+                    flushed = fused.decode_output(self, scores, value_states, out, softmax_inv_scale=inv, mask=attention_mask)
+                except KiviUnsupported as e:         # keep the softmax as its own launch
+                    self._drop_fusion("_softmax_unfusable", "the softmax cannot be folded into the sV launch", str(e))
+        if flushed is None:
+            fused.softmax_scaled(scores, probs, kv_seq_len, inv, attention_mask)
+            try:
+                flushed = fused.decode_output(self, probs, value_states, out)
+            except KiviUnsupported:   # no tuned sV kernel for this head_dim / group: compose the output part
+                out = self._composed_output(probs[..., :kv_seq_len], value_states, nh)
+                self.kv_seq_len = kv_seq_len
+                return out
+        self.v_res_len += 1
+        if flushed:
+            self.v_quant_len += 1
+            self.v_res_start += 1
+            self.v_res_len -= 1
+        self.kv_seq_len = kv_seq_len
+        return out
+
+    def _composed_output(self, attn_weights: torch.Tensor, value_states: torch.Tensor, nh: int) -> torch.Tensor:
+        """Output over [quantised V prefix | fp16 V window], one launch per reference op (llama_kivi.py:377-399)."""
+        cfg = self.cfg
+        B, nh_kv, D = self.B, self.nh_kv, self.D
+        rep = nh // nh_kv
+        self.append_v(value_states)
+        Tv, Lv = self.v_quant_len, self.v_res_len
+        v_full = self.v_res_view()
+        w_full = attn_weights[..., Tv:].reshape(B, nh_kv, rep, Lv)
+        if Tv == 0:
+            attn_output = torch.matmul(w_full, v_full).view(B, nh, 1, D)     # :380
+        else:
+            vc, vs, vm = self.v_quant_views()
+            attn_output = matmul.cuda_bmm_fA_qB_outer(cfg.group_size, attn_weights[..., :Tv], vc, vs, vm, cfg.v_bits)   # :382
+            attn_output += torch.matmul(w_full, v_full).view(B, nh, 1, D)    # :384
+        self.maybe_flush_v()                                                  # :386-399
+        return attn_output
+
     # ------------------------------------------------------------------ multi-token extend (untuned)
     def extend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
                attention_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -374,7 +645,6 @@ class KiviLayerCache:
         plus chunk tokens 0..i; per row the rounding sequence of one decode step) for the shapes the matrix pipe does not cover.
         The UNTUNED path: composed from torch ops on the GPU (fp32 dequantisation of the packed prefix, fp32 matmuls rounded to
         fp16 where the hook rounds), then the cache bookkeeping of Q decode steps through append / flush, one token at a time."""
-        import math
         cfg = self.cfg
         B, nh, Q, D = query_states.shape
         assert B == self.B and D == self.D and Q >= 1 and nh % self.nh_kv == 0
@@ -403,8 +673,7 @@ class KiviLayerCache:
         parts.append(torch.matmul(qf, heads(kfull).float().transpose(2, 3)).half())
         w = torch.cat(parts, -1) / math.sqrt(D)
         if attention_mask is not None:
-            if attention_mask.size() != (B, 1, Q, total):
-                raise ValueError(f"Attention mask should be of size {(B, 1, Q, total)}, but is {attention_mask.size()}")
+            check_mask_size(attention_mask, (B, 1, Q, total))
             w = w + attention_mask
             w = torch.max(w, torch.tensor(torch.finfo(w.dtype).min, device=w.device, dtype=w.dtype))
         causal = torch.ones((Q, Q), dtype=torch.bool, device=w.device).triu(1)
@@ -444,15 +713,10 @@ class KiviLayerCache:
                 self.k_code[:, :, p, :, : n // kf].copy_(kc[..., p * P // kf: (p * P + n) // kf])
                 self.k_scale[:, :, p, :, : n // g].copy_(ks[..., p * P // g: (p * P + n) // g])
                 self.k_mn[:, :, p, :, : n // g].copy_(km[..., p * P // g: (p * P + n) // g])
-        if kfull is not None:
-            self.k_res_len = kfull.shape[2]
-            self.k_res[:, :, : self.k_res_len].copy_(kfull)
         if vc is not None:
             self.v_quant_len = vc.shape[2]
             self.v_code[:, :, : self.v_quant_len].copy_(vc)
             self.v_scale[:, :, : self.v_quant_len].copy_(vs)
             self.v_mn[:, :, : self.v_quant_len].copy_(vm)
-        self.v_res_len = vfull.shape[2]
-        self.v_res[:, :, : self.v_res_len].copy_(vfull)
-        self.kv_seq_len = int(kv_len)
+        self._adopt_residuals(past)
         return self

@@ -25,8 +25,9 @@ import math
 import torch
 
 from . import _lib, _tuning
-from .cache import KiviCacheTuple, KiviConfig
-from .quant import mfma, new_pack
+from ._lib import check_mask_size, mask_arg, out_arg, rows16
+from .cache import KiviCacheBase, KiviConfig, KiviLayerCache
+from .quant import matmul, mfma, new_pack
 
 SB = mfma.SB_TOKENS
 _SCRATCH = {}   # (device, stream) -> dict(scores, stats, ws): shared by the layers that decode on that stream (launches are
@@ -65,7 +66,7 @@ def _scratch(device, B: int, nh: int, nh_kv: int, pitch: int, nseg: int, slices:
     return sc, st, ws
 
 
-class KiviLayerCacheMF:
+class KiviLayerCacheMF(KiviCacheBase):
     """One layer's quantised KV cache (capacity `max_len` tokens, appended in place): 2-bit with nh / nh_kv in {1, 4, 8}, 4-bit with
     nh / nh_kv in {1, 4} (multi-head 4-bit: round 6)."""
 
@@ -73,13 +74,11 @@ class KiviLayerCacheMF:
 
     def __init__(self, cfg: KiviConfig, batch: int, num_kv_heads: int, head_dim: int, max_len: int, device,
                  dtype=torch.float16, num_heads: int = None):
-        assert dtype == torch.float16, "the reference extension is fp16 only (gemv_cuda.cu:526-529)"
         assert num_heads is not None and supported(cfg, head_dim, num_heads, num_kv_heads), \
             "matrix-pipe layout: group 32, head_dim 128, residual_length <= 128; 2-bit with nh / nh_kv in {1, 4, 8} or 4-bit with nh / nh_kv in {1, 4}"
-        self.cfg = cfg
+        super().__init__(cfg, batch, num_kv_heads, head_dim, max_len, dtype)
         R = cfg.residual_length
-        self.B, self.nh_kv, self.D, self.nh = batch, num_kv_heads, head_dim, num_heads
-        self.cap = ((max_len + R - 1) // R) * R
+        self.nh = num_heads
         self.n_sb = (self.cap + SB - 1) // SB
         self.kt = mfma.alloc_store(batch, num_kv_heads, self.n_sb, device, cfg.k_bits)
         self.vt = mfma.alloc_store(batch, num_kv_heads, self.n_sb, device, cfg.v_bits)
@@ -87,13 +86,6 @@ class KiviLayerCacheMF:
         # fp16 value window: a RING of R + 1 rows (row of window token t = (v_res_start + t) mod rows): nothing is ever compacted
         self.ring = True
         self.v_res = torch.empty((batch, num_kv_heads, R + 1, head_dim), dtype=dtype, device=device)
-        self.k_quant_len = 0
-        self.k_res_len = 0
-        self.v_quant_len = 0
-        self.v_res_start = 0
-        self.v_res_len = 0
-        self.kv_seq_len = 0
-        self._native = None       # (descriptor, state array, scratch tensors) of kivi_mf_decode_layer
         self.flags = 0            # _lib.GQA_FORCE_SPLIT / GQA_FORCE_ROW (tests, tuning)
 
     # ------------------------------------------------------------------ capacity
@@ -111,40 +103,25 @@ class KiviLayerCacheMF:
                 setattr(self, name, new)
             self.n_sb = n_sb
         self.cap = cap
-        self._native = None
+        self._invalidate()
 
-    def ensure_room(self, tokens: int = 1) -> None:
-        need = self.kv_seq_len + tokens
-        if need > self.cap:
-            self.reserve(max(need, 2 * self.cap))
-
-    def clone(self) -> "KiviLayerCacheMF":
-        import copy
-        other = copy.copy(self)
+    def _own_buffers(self, idx) -> None:
+        """Replace the buffers (still those of the cache this one was copied from) by copies of their own: whole, or rows `idx`
+        (range words included)."""
         for name in ("kt", "vt"):
             src = getattr(self, name)
             dst = mfma.alloc_store(self.B, self.nh_kv, self.n_sb, src.device, self.cfg.k_bits)
-            mfma.copy_store(dst, src)
-            setattr(other, name, dst)
+            if idx is None:
+                mfma.copy_store(dst, src)
+            else:
+                dst.copy_(src.index_select(0, idx))
+                mfma.range_flags(dst).copy_(mfma.range_flags(src).index_select(0, idx))
+            setattr(self, name, dst)
         for name in ("k_res", "v_res"):
             src = getattr(self, name)
-            dst = torch.empty_strided(src.shape, src.stride(), dtype=src.dtype, device=src.device)
-            dst.copy_(src)
-            setattr(other, name, dst)
-        other._native = None
-        return other
+            setattr(self, name, src.clone() if idx is None else src.index_select(0, idx))
 
     # ------------------------------------------------------------------ beam search (DESIGN.md section 11)
-    def reorder_(self, idx, group: int = None, from_token: int = 0, check: bool = True) -> "KiviLayerCacheMF":
-        """row[b] <- row[idx[b]] in place: the contract of KiviLayerCache.reorder_ (the range words always move)."""
-        from . import reorder
-        group = self.B if group is None else int(group)
-        if not 0 <= int(from_token) <= self.kv_seq_len:
-            raise ValueError(f"from_token={from_token} lies beyond the cache length {self.kv_seq_len}")
-        idx = reorder.check_idx(idx, self.B, group, self.k_res.device, check)
-        reorder.run(self._reorder_slabs(int(from_token)), self.B, group, idx)
-        return self
-
     def _reorder_slabs(self, from_token: int):
         """Super-blocks of 16 blocks of 32 tokens (kivi_mfma_layout.h): codes of block j at words [j BW, (j + 1) BW); V scales /
         zero points of block j at halves j * 128 of their regions; K scales / zero points of group j at halves
@@ -183,25 +160,6 @@ class KiviLayerCacheMF:
         out.append(slab(self.v_res, 0, [(h, self.v_res.stride(1) * 2)], self.v_res.shape[2] * self.D * 2))
         return out
 
-    def index_select(self, idx) -> "KiviLayerCacheMF":
-        """A new cache of len(idx) rows, row i a bit-identical copy of row idx[i] (whole rows, range words included)."""
-        import copy
-        idx = torch.as_tensor(idx, device=self.k_res.device).long().flatten()
-        if idx.numel() == 0 or not bool(((idx >= 0) & (idx < self.B)).all()):
-            raise ValueError(f"index_select: indices must lie in [0, {self.B})")
-        other = copy.copy(self)
-        for name in ("kt", "vt"):
-            src = getattr(self, name)
-            dst = mfma.alloc_store(idx.numel(), self.nh_kv, self.n_sb, src.device, self.cfg.k_bits)
-            dst.copy_(src.index_select(0, idx))
-            mfma.range_flags(dst).copy_(mfma.range_flags(src).index_select(0, idx))
-            setattr(other, name, dst)
-        for name in ("k_res", "v_res"):
-            setattr(other, name, getattr(self, name).index_select(0, idx))
-        other.B = idx.numel()
-        other._native = None
-        return other
-
     # ------------------------------------------------------------------ the 9-tuple
     def k_quant_reference_layout(self):
         if self.k_quant_len == 0:
@@ -213,29 +171,11 @@ class KiviLayerCacheMF:
             return None, None, None
         return mfma.vt_to_ref(self.vt, self.v_quant_len, self.D, self.cfg.group_size, self.cfg.v_bits)
 
-    def k_res_view(self):
-        return self.k_res[:, :, : self.k_res_len] if self.k_res_len else None
-
     def v_res_view(self):
         s, n, rows = self.v_res_start, self.v_res_len, self.v_res.shape[2]
         if s + n <= rows:
             return self.v_res[:, :, s: s + n]
         return torch.cat([self.v_res[:, :, s:], self.v_res[:, :, : s + n - rows]], dim=2)      # the ring wraps (9-tuple reads only)
-
-    def _tuple_members(self):
-        kc, ks, km = self.k_quant_reference_layout()
-        vc, vs, vm = self.v_quant_views()
-        return (kc, self.k_res_view(), ks, km, vc, self.v_res_view(), vs, vm)
-
-    def as_tuple(self) -> KiviCacheTuple:
-        return KiviCacheTuple(self)
-
-    def nbytes(self) -> int:
-        c = self.cfg
-        per_k = self.D * self.k_quant_len * c.k_bits // 8 + 2 * self.D * (self.k_quant_len // c.group_size) * 2
-        per_v = self.v_quant_len * self.D * c.v_bits // 8 + 2 * self.v_quant_len * (self.D // c.group_size) * 2
-        res = (self.k_res_len + self.v_res_len) * self.D * 2
-        return self.B * self.nh_kv * (per_k + per_v + res)
 
     def allocated_bytes(self) -> int:
         return sum(x.numel() * x.element_size() for x in (self.kt, self.vt, self.k_res, self.v_res))
@@ -280,15 +220,10 @@ class KiviLayerCacheMF:
         if kc is not None:
             self.k_quant_len = kc.shape[-1] * (32 // cfg.k_bits)
             mfma.kt_from_ref(self.kt, kc.contiguous(), ks.contiguous(), km.contiguous(), cfg.group_size, cfg.k_bits)
-        if kfull is not None:
-            self.k_res_len = kfull.shape[2]
-            self.k_res[:, :, : self.k_res_len].copy_(kfull)
         if vc is not None:
             self.v_quant_len = vc.shape[2]
             mfma.vt_from_ref(self.vt, vc.contiguous(), vs.contiguous(), vm.contiguous(), cfg.group_size, cfg.v_bits)
-        self.v_res_len = vfull.shape[2]
-        self.v_res[:, :, : self.v_res_len].copy_(vfull)
-        self.kv_seq_len = int(kv_len)
+        self._adopt_residuals(past)
         return self
 
     # ------------------------------------------------------------------ decode step (llama_kivi.py:314-399)
@@ -321,26 +256,18 @@ class KiviLayerCacheMF:
         return self.flags | (_lib.GQA_WINDOW_RING if self.ring else 0)
 
     def decode_step(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
-                    attention_mask: torch.Tensor = None, out: torch.Tensor = None) -> torch.Tensor:
+                    attention_mask: torch.Tensor = None, out: torch.Tensor = None, fused_kernels: bool = True) -> torch.Tensor:
+        """One new token in ONE library call (kivi_mf_decode_layer); `fused_kernels` is the other layout's switch (this one has no
+        composed form)."""
         B, nh, _, D = query_states.shape
         assert nh == self.nh and B == self.B and D == self.D
-        q, k, v = _rows16(query_states), _rows16(key_states), _rows16(value_states)
-        kv_seq_len = self.kv_seq_len + 1
-        mask_ptr, mask_sb = None, 0
-        if attention_mask is not None:
-            if attention_mask.size() != (B, 1, 1, kv_seq_len):
-                raise ValueError(f"Attention mask should be of size {(B, 1, 1, kv_seq_len)}, but is {attention_mask.size()}")
-            assert attention_mask.dtype == torch.float16 and attention_mask.stride(3) == 1
-            mask_ptr, mask_sb = attention_mask.data_ptr(), attention_mask.stride(0)
-        if out is None:
-            out = torch.empty((B, nh, 1, D), dtype=torch.float16, device=q.device)
-        else:
-            assert out.shape == (B, nh, 1, D) and out.dtype == torch.float16 and out.stride(3) == 1
+        q, k, v = rows16(query_states), rows16(key_states), rows16(value_states)
+        mask_ptr, mask_sb = mask_arg(attention_mask, B, self.kv_seq_len + 1)
+        out = out_arg(out, (B, nh, 1, D), q.device)
         d, state, key, fn, _ = self._desc(nh, q.device)     # key = (nh, stream handle the descriptor was built for = the current one)
         d.flags = self._flags()
-        state[0], state[1], state[2] = self.k_quant_len, self.k_res_len, self.v_quant_len
-        state[3], state[4], state[5] = self.v_res_start, self.v_res_len, self.kv_seq_len
-        hook = _launch_hook()
+        self._store_state(state)
+        hook = matmul.launch_hook
         if hook is not None and self.k_quant_len:
             hook("pre", "k", dict(B=B, nh=nh, nh_kv=self.nh_kv, K=D, N=self.k_quant_len, bits=self.cfg.k_bits,
                                   group_size=self.cfg.group_size, v_bits=self.cfg.v_bits, Tv=self.v_quant_len,
@@ -348,12 +275,10 @@ class KiviLayerCacheMF:
         rc = fn(ctypes.byref(d), state, q.data_ptr(), q.stride(0), q.stride(1), nh, k.data_ptr(), k.stride(0), k.stride(1),
                 v.data_ptr(), v.stride(0), v.stride(1), mask_ptr, mask_sb, out.data_ptr(), out.stride(0), out.stride(1), key[1])
         # the library writes `state` after every phase it has enqueued: read the lengths back whether or not the call succeeded
-        self.k_quant_len, self.k_res_len, self.v_quant_len = state[0], state[1], state[2]
-        self.v_res_start, self.v_res_len, self.kv_seq_len = state[3], state[4], state[5]
+        self._load_state(state)
         if rc:
             _lib.check(rc, "kivi_mf_decode_layer")
         return out
-
 
     # ------------------------------------------------------------------ multi-token extend
     def extend(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
@@ -369,12 +294,11 @@ class KiviLayerCacheMF:
         assert key_states.shape == value_states.shape == (B, self.nh_kv, Q, D)
         assert self.kv_seq_len > 0, "extend needs a cache: run the prompt pass first"
         self.ensure_room(Q)
-        q, k, v = _rows16(query_states), _rows16(key_states), _rows16(value_states)
+        q, k, v = rows16(query_states), rows16(key_states), rows16(value_states)
         total = self.kv_seq_len + Q
         mask_ptr, mask_sb, mask_sq = None, 0, 0
         if attention_mask is not None:
-            if attention_mask.size() != (B, 1, Q, total):
-                raise ValueError(f"Attention mask should be of size {(B, 1, Q, total)}, but is {attention_mask.size()}")
+            check_mask_size(attention_mask, (B, 1, Q, total))
             assert attention_mask.dtype == torch.float16
             if attention_mask.stride(2) == 0:    # one key row per batch row, expanded over the chunk: passed as mask_sq = 0
                 if attention_mask.stride(3) != 1 or attention_mask.stride(0) < total:
@@ -383,10 +307,7 @@ class KiviLayerCacheMF:
             elif attention_mask.stride(3) != 1 or attention_mask.stride(0) < Q * attention_mask.stride(2):
                 attention_mask = attention_mask.contiguous()
             mask_ptr, mask_sb, mask_sq = attention_mask.data_ptr(), attention_mask.stride(0), attention_mask.stride(2)
-        if out is None:
-            out = torch.empty((B, nh, Q, D), dtype=torch.float16, device=q.device)
-        else:
-            assert out.shape == (B, nh, Q, D) and out.dtype == torch.float16 and out.stride(3) == 1
+        out = out_arg(out, (B, nh, Q, D), q.device)
         d, state, key, _, _ = self._desc(nh, q.device)
         d.flags = self._flags() & ~_lib.GQA_DUMP_SCORES     # the decode steps' dump flag: their scratch rows cannot hold Q rows
         if scores_dump is not None:              # a copy of the descriptor: the decode steps keep their scratch rows
@@ -396,15 +317,13 @@ class KiviLayerCacheMF:
             d = _lib.MfLayerDesc.from_buffer_copy(d)
             d.flags |= _lib.GQA_DUMP_SCORES
             d.scores, d.s_sb, d.s_sh, d.s_pitch = sd.data_ptr(), sd.stride(0), sd.stride(1), sd.stride(2)
-        state[0], state[1], state[2] = self.k_quant_len, self.k_res_len, self.v_quant_len
-        state[3], state[4], state[5] = self.v_res_start, self.v_res_len, self.kv_seq_len
+        self._store_state(state)
         rc = _lib.load().kivi_mf_extend_layer(ctypes.byref(d), state, Q, q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), nh,
                                               k.data_ptr(), k.stride(0), k.stride(1), k.stride(2), v.data_ptr(), v.stride(0),
                                               v.stride(1), v.stride(2), mask_ptr, mask_sb, mask_sq, out.data_ptr(), out.stride(0),
                                               out.stride(1), out.stride(2), key[1])
         _lib.check(rc, "kivi_mf_extend_layer")
-        self.k_quant_len, self.k_res_len, self.v_quant_len = state[0], state[1], state[2]
-        self.v_res_start, self.v_res_len, self.kv_seq_len = state[3], state[4], state[5]
+        self._load_state(state)
         return out
 
     # ------------------------------------------------------------------ device-resident lengths (hipGraph capture; kivi_amd/graph.py)
@@ -429,11 +348,9 @@ class KiviLayerCacheMF:
         assert nh == self.nh and B == self.B and D == self.D
         for t in (query_states, key_states, value_states):
             assert t.stride(3) == 1 and t.data_ptr() % 16 == 0 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0, "static 16-byte rows"
-        mask_ptr, mask_sb = None, 0
-        if attention_mask is not None:          # a static (B, 1, 1, pitch >= capacity) buffer the caller refills every step
-            assert attention_mask.dtype == torch.float16 and attention_mask.stride(3) == 1 and attention_mask.shape[3] >= self.kv_seq_len + 1
-            mask_ptr, mask_sb = attention_mask.data_ptr(), attention_mask.stride(0)
-        assert out.shape == (B, nh, 1, D) and out.dtype == torch.float16 and out.stride(3) == 1
+        # the mask: a static (B, 1, 1, pitch >= capacity) buffer the caller refills every step
+        mask_ptr, mask_sb = mask_arg(attention_mask, B, self.kv_seq_len + 1, wider=True)
+        out = out_arg(out, (B, nh, 1, D), query_states.device)
         d, _, key, _, _ = self._desc(nh, query_states.device)
         d.flags = self._flags()
         q, k, v = query_states, key_states, value_states
@@ -452,28 +369,10 @@ class KiviLayerCacheMF:
         self.k_res_len = 0
 
 
-def _rows16(x):
-    """16-byte loads of whole rows: unit inner stride, 16-byte aligned rows (a copy otherwise)."""
-    ok = x.stride(3) == 1 and x.data_ptr() % 16 == 0 and x.stride(0) % 8 == 0 and x.stride(1) % 8 == 0
-    return x if ok else x.contiguous()
-
-
-_MATMUL = None
-
-
-def _launch_hook():
-    global _MATMUL
-    if _MATMUL is None:           # (imported lazily: quant.matmul imports this package)
-        from .quant import matmul
-        _MATMUL = matmul
-    return _MATMUL.launch_hook
-
-
 def make_layer_cache(cfg: KiviConfig, batch: int, num_kv_heads: int, head_dim: int, max_len: int, device,
                      dtype=torch.float16, num_heads: int = None):
     """The cache class for a model shape: the matrix-pipe layout for grouped queries it covers, the hook-state layout
     (KiviLayerCache) otherwise."""
-    from .cache import KiviLayerCache
     if num_heads is not None and supported(cfg, head_dim, num_heads, num_kv_heads):
         return KiviLayerCacheMF(cfg, batch, num_kv_heads, head_dim, max_len, device, dtype, num_heads=num_heads)
     return KiviLayerCache(cfg, batch, num_kv_heads, head_dim, max_len, device, dtype)

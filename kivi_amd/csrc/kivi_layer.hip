@@ -111,6 +111,36 @@ extern "C" int kivi_decode_layer(const kivi_layer_desc* L, int64_t* st, const vo
     return 0;
 }
 
+// kivi_gqa_decode_args of one step of a KT / VT cache: the buffers of the descriptor, the step's inputs, its six lengths (`hs`)
+// and, for a step whose kernels read the lengths on the device, where (`dyn_step`, else null).
+static kivi_gqa_decode_args mf_decode_args(const kivi_mf_layer_desc* L, const kivi_mf_step* hs, const void* dyn_step, const void* q,
+                                           int64_t q_sb, int64_t q_sh, int nh, const void* knew, int64_t kn_sb, int64_t kn_sh,
+                                           const void* vnew, int64_t vn_sb, int64_t vn_sh, const void* mask, int64_t mask_sb, void* out,
+                                           int64_t out_sb, int64_t out_sh) {
+    kivi_gqa_decode_args a;
+    a.B = L->B; a.nh = nh; a.nh_kv = L->nh_kv; a.D = L->D; a.group_size = L->group_size; a.bits = L->bits;
+    a.inv_scale = L->inv_scale;
+    a.q = q; a.q_sb = q_sb; a.q_sh = q_sh;
+    a.mask = mask; a.mask_sb = mask_sb;
+    a.kt = L->kt; a.kt_sb = L->kt_sb; a.kt_sh = L->kt_sh; a.kt_ss = L->kt_ss; a.Tq = hs->Tq;
+    a.kres = L->k_res; a.kres_sb = L->kr_sb; a.kres_sh = L->kr_sh; a.kres_st = L->kr_st;
+    a.knew = knew; a.knew_sb = kn_sb; a.knew_sh = kn_sh; a.k_res_len = hs->k_res_len;
+    a.vt = L->vt; a.vt_sb = L->vt_sb; a.vt_sh = L->vt_sh; a.vt_ss = L->vt_ss; a.Tv = hs->Tv;
+    a.vres = L->v_res; a.vres_sb = L->vr_sb; a.vres_sh = L->vr_sh; a.vres_st = L->vr_st;
+    a.v_win_start = hs->v_win_start; a.v_res_len = hs->v_res_len;
+    a.vnew = vnew; a.vnew_sb = vn_sb; a.vnew_sh = vn_sh; a.v_flush = hs->v_flush;
+    a.scores = L->scores; a.s_sb = L->s_sb; a.s_sh = L->s_sh;
+    a.stats = L->stats; a.stats_bytes = L->stats_bytes;
+    a.workspace = L->workspace; a.workspace_bytes = L->workspace_bytes;
+    a.out = out; a.out_sb = out_sb; a.out_sh = out_sh;
+    a.residual_length = L->residual_length; a.v_window_rows = L->v_window_rows;
+    a.kt_superblocks = L->cap / 512; a.vt_superblocks = L->cap / 512;
+    a.flags = L->flags;
+    a.kt_range = L->kt_range; a.vt_range = L->vt_range;
+    a.dyn_step = dyn_step;
+    return a;
+}
+
 // The same for a cache in the KT / VT layouts (kivi_mfma_layout.h): kivi_gqa_decode (one launch for multi-head rows that fit
 // the LDS, two launches otherwise) + lengths + the K flush through kivi_kt_pack every residual_length steps
 // (llama_kivi.py:343-356) + window compaction.  Same state array, same atomicity contract as kivi_decode_layer.
@@ -173,27 +203,9 @@ extern "C" int kivi_mf_decode_layer(const kivi_mf_layer_desc* L, int64_t* st, co
         st[3] = 0;
     }
     const int flush = vres + 1 > R;
-    kivi_gqa_decode_args a;
-    a.B = L->B; a.nh = nh; a.nh_kv = L->nh_kv; a.D = L->D; a.group_size = L->group_size; a.bits = L->bits;
-    a.inv_scale = L->inv_scale;
-    a.q = q; a.q_sb = q_sb; a.q_sh = q_sh;
-    a.mask = mask; a.mask_sb = mask_sb;
-    a.kt = L->kt; a.kt_sb = L->kt_sb; a.kt_sh = L->kt_sh; a.kt_ss = L->kt_ss; a.Tq = Tq;
-    a.kres = L->k_res; a.kres_sb = L->kr_sb; a.kres_sh = L->kr_sh; a.kres_st = L->kr_st;
-    a.knew = knew; a.knew_sb = kn_sb; a.knew_sh = kn_sh; a.k_res_len = (int)kres;
-    a.vt = L->vt; a.vt_sb = L->vt_sb; a.vt_sh = L->vt_sh; a.vt_ss = L->vt_ss; a.Tv = Tv;
-    a.vres = L->v_res; a.vres_sb = L->vr_sb; a.vres_sh = L->vr_sh; a.vres_st = L->vr_st;
-    a.v_win_start = (int)wstart; a.v_res_len = (int)vres;
-    a.vnew = vnew; a.vnew_sb = vn_sb; a.vnew_sh = vn_sh; a.v_flush = flush;
-    a.scores = L->scores; a.s_sb = L->s_sb; a.s_sh = L->s_sh;
-    a.stats = L->stats; a.stats_bytes = L->stats_bytes;
-    a.workspace = L->workspace; a.workspace_bytes = L->workspace_bytes;
-    a.out = out; a.out_sb = out_sb; a.out_sh = out_sh;
-    a.residual_length = R; a.v_window_rows = L->v_window_rows;
-    a.kt_superblocks = L->cap / 512; a.vt_superblocks = L->cap / 512;
-    a.flags = L->flags;
-    a.kt_range = L->kt_range; a.vt_range = L->vt_range;
-    a.dyn_step = nullptr;
+    const kivi_mf_step hs = {Tq, Tv, (int32_t)kres, (int32_t)vres, (int32_t)wstart, flush};
+    const kivi_gqa_decode_args a = mf_decode_args(L, &hs, nullptr, q, q_sb, q_sh, nh, knew, kn_sb, kn_sh, vnew, vn_sb, vn_sh, mask, mask_sb,
+                                                  out, out_sb, out_sh);
     int rc = kivi_gqa_decode(&a, stream);
     if (rc) return rc;            // nothing of the step has been committed
     kres += 1;
@@ -239,27 +251,8 @@ extern "C" int kivi_mf_decode_layer_dyn(const kivi_mf_layer_desc* L, const kivi_
     KIVI_REQUIRE(L->cap % 512 == 0 && kv + 1 <= L->cap && nsbk * 512 + R <= L->s_pitch, KIVI_EINVAL,
                  "kivi_mf_decode_layer_dyn: capacity %lld / score pitch %lld too small for the step's geometry class", (long long)L->cap,
                  (long long)L->s_pitch);
-    kivi_gqa_decode_args a;
-    a.B = L->B; a.nh = nh; a.nh_kv = L->nh_kv; a.D = L->D; a.group_size = L->group_size; a.bits = L->bits;
-    a.inv_scale = L->inv_scale;
-    a.q = q; a.q_sb = q_sb; a.q_sh = q_sh;
-    a.mask = mask; a.mask_sb = mask_sb;
-    a.kt = L->kt; a.kt_sb = L->kt_sb; a.kt_sh = L->kt_sh; a.kt_ss = L->kt_ss; a.Tq = hs->Tq;
-    a.kres = L->k_res; a.kres_sb = L->kr_sb; a.kres_sh = L->kr_sh; a.kres_st = L->kr_st;
-    a.knew = knew; a.knew_sb = kn_sb; a.knew_sh = kn_sh; a.k_res_len = hs->k_res_len;
-    a.vt = L->vt; a.vt_sb = L->vt_sb; a.vt_sh = L->vt_sh; a.vt_ss = L->vt_ss; a.Tv = hs->Tv;
-    a.vres = L->v_res; a.vres_sb = L->vr_sb; a.vres_sh = L->vr_sh; a.vres_st = L->vr_st;
-    a.v_win_start = hs->v_win_start; a.v_res_len = hs->v_res_len;
-    a.vnew = vnew; a.vnew_sb = vn_sb; a.vnew_sh = vn_sh; a.v_flush = hs->v_flush;
-    a.scores = L->scores; a.s_sb = L->s_sb; a.s_sh = L->s_sh;
-    a.stats = L->stats; a.stats_bytes = L->stats_bytes;
-    a.workspace = L->workspace; a.workspace_bytes = L->workspace_bytes;
-    a.out = out; a.out_sb = out_sb; a.out_sh = out_sh;
-    a.residual_length = R; a.v_window_rows = L->v_window_rows;
-    a.kt_superblocks = L->cap / 512; a.vt_superblocks = L->cap / 512;
-    a.flags = L->flags;
-    a.kt_range = L->kt_range; a.vt_range = L->vt_range;
-    a.dyn_step = dev_step;
+    const kivi_gqa_decode_args a = mf_decode_args(L, hs, dev_step, q, q_sb, q_sh, nh, knew, kn_sb, kn_sh, vnew, vn_sb, vn_sh, mask, mask_sb,
+                                                  out, out_sb, out_sh);
     return kivi_gqa_decode(&a, stream);
 }
 

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .attention import LlamaAttention_KIVI
+from .attention import LlamaAttention_KIVI, rope_cos_sin
 
 
 def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32, residual_length: int = 32,
@@ -123,6 +123,31 @@ def padding_prompt_mask(mask: torch.Tensor) -> torch.Tensor:
     return causal[None, None].repeat(B, 1, 1, 1).masked_fill_((mask == 0)[:, None, None, :], _MIN16)
 
 
+class _PaddedBatch:
+    """What a left-padded batch adds to the passes of one call, derived once from HF's 2D mask (B, past_len + T): `mask` and
+    `position_ids` of the pass over the T new tokens (the prompt's 4D causal + padding mask; with a history, the key row expanded
+    over the chunk), then per decode step a view of the key row one column longer (new tokens are real) and the advancing
+    position.  `beams`: the decode steps run on every row repeated that often (the prompt pass does not)."""
+
+    def __init__(self, mask2d: torch.Tensor, past_len: int, T: int, max_new_tokens: int = 0, beams: int = 1):
+        n = past_len + T
+        row = padding_key_row(mask2d, n + max_new_tokens)
+        self.mask = padding_prompt_mask(mask2d) if past_len == 0 else row[..., :n].expand(-1, -1, T, -1)
+        self.position_ids = padding_position_ids(mask2d, T)
+        if max_new_tokens:
+            pos = mask2d.long().sum(-1, keepdim=True)                  # (B, 1): position of the next token
+            if beams > 1:
+                row, pos = row.repeat_interleave(beams, dim=0), pos.repeat_interleave(beams, dim=0)
+            self._row, self._pos, self._len = row, pos, n
+
+    def step(self):
+        """(additive key row (B, 1, 1, kv length incl. the new token), position ids (B, 1)) of the next decode step."""
+        self._len += 1
+        pos = self._pos
+        self._pos = pos + 1
+        return self._row[..., : self._len], pos
+
+
 class LlamaForCausalLM_KIVI(nn.Module):
     """`past_key_values` is a list with one entry per layer: None before the prompt pass, afterwards the 9-tuple of
     models/llama_kivi.py:454-455 (here the lazy KiviCacheTuple over the in-place cache).
@@ -153,12 +178,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
         past_len = self._past_len(past_key_values)
         if not self._padded(padding_mask, input_ids.shape[0], past_len + input_ids.shape[1], past_len):
             return self._forward(input_ids, past_key_values, None, None, last_token_only, False)
-        T = input_ids.shape[1]
-        if past_len == 0:
-            mask = padding_prompt_mask(padding_mask)
-        else:
-            mask = padding_key_row(padding_mask).expand(-1, -1, T, -1)
-        return self._forward(input_ids, past_key_values, mask, padding_position_ids(padding_mask, T), last_token_only, True)
+        pb = _PaddedBatch(padding_mask, past_len, input_ids.shape[1])
+        return self._forward(input_ids, past_key_values, pb.mask, pb.position_ids, last_token_only, True)
 
     def _forward(self, input_ids, past_key_values, attention_mask, position_ids, last_token_only, mask_prompt):
         pasts = past_key_values or [None] * len(self.model.layers)
@@ -186,6 +207,21 @@ class LlamaForCausalLM_KIVI(nn.Module):
             raise ValueError(f"{type(self.model.layers[0].self_attn).__name__}: the prompt pass of this attention class ignores "
                              f"masks (llama_kivi.py:420-423), so padded prompts cannot be run; use the eager class")
         return True
+
+    def _prompt_pass(self, input_ids, past_key_values, attention_mask, max_new_tokens: int, beams: int = 1):
+        """The pass over `input_ids` of a generate call -> (the _PaddedBatch of a mask with a pad in it, else None; logits; pasts)."""
+        B, T = input_ids.shape
+        past_len = self._past_len(past_key_values)
+        if attention_mask is not None and self._padded(attention_mask, B, past_len + T, past_len):
+            pb = _PaddedBatch(attention_mask, past_len, T, max_new_tokens, beams)
+            return (pb,) + self._forward(input_ids, past_key_values, pb.mask, pb.position_ids, True, True)
+        return (None,) + self.forward(input_ids, past_key_values)
+
+    def _decode_pass(self, tok, pasts, pb):
+        """One decode step of a generate call -> (logits, pasts)."""
+        if pb is None:
+            return self.forward(tok, pasts)
+        return self._forward(tok, pasts, *pb.step(), True, True)
 
     @staticmethod
     def _reorder_cache(past_key_values, beam_idx: torch.Tensor):
@@ -234,33 +270,20 @@ class LlamaForCausalLM_KIVI(nn.Module):
                                         num_beams, length_penalty, early_stopping, num_return_sequences, return_scores)
         if return_scores:
             raise ValueError("return_scores: sequences_scores exist for beam search (num_beams > 1) only")
-        B, T = input_ids.shape
-        past_len = self._past_len(past_key_values)
-        pos = row = None
-        if attention_mask is not None and self._padded(attention_mask, B, past_len + T, past_len):
-            # one additive key row per request; every decode step reads a view one column longer (new tokens are real)
-            row = padding_key_row(attention_mask, past_len + T + max_new_tokens)
-            mask = padding_prompt_mask(attention_mask) if past_len == 0 else row[..., : past_len + T].expand(-1, -1, T, -1)
-            logits, pasts = self._forward(input_ids, past_key_values, mask, padding_position_ids(attention_mask, T), True, True)
-            pos = attention_mask.long().sum(-1, keepdim=True)          # (B, 1): position of the next token
-        else:
-            logits, pasts = self.forward(input_ids, past_key_values)
+        B = input_ids.shape[0]
+        pb, logits, pasts = self._prompt_pass(input_ids, past_key_values, attention_mask, max_new_tokens)
         out = [input_ids]
         pick = (lambda lg: lg.argmax(-1)) if sampler is None else sampler
         tok = pick(logits)
         live = None if eos_token_id is None else torch.ones((B, 1), dtype=torch.bool, device=tok.device)
-        for s in range(max_new_tokens):
+        for _ in range(max_new_tokens):
             if live is not None:
                 tok = torch.where(live, tok, torch.full_like(tok, pad_token_id))
                 live = live & (tok != eos_token_id)
             out.append(tok)
             if live is not None and not bool(live.any()):
                 break
-            if row is None:
-                logits, pasts = self.forward(tok, pasts)
-            else:
-                logits, pasts = self._forward(tok, pasts, row[..., : past_len + T + s + 1], pos, True, True)
-                pos = pos + 1
+            logits, pasts = self._decode_pass(tok, pasts, pb)
             tok = pick(logits)
         return torch.cat(out, dim=1)
 
@@ -281,31 +304,15 @@ class LlamaForCausalLM_KIVI(nn.Module):
         past_len = self._past_len(past_key_values)
         if past_key_values is not None:              # the caller's caches stay as they are
             past_key_values = [p.layer.clone().as_tuple() for p in past_key_values]
-        pos = row = None
-        if attention_mask is not None and self._padded(attention_mask, B, past_len + T, past_len):
-            row = padding_key_row(attention_mask, past_len + T + max_new_tokens)
-            mask = padding_prompt_mask(attention_mask) if past_len == 0 else row[..., : past_len + T].expand(-1, -1, T, -1)
-            logits, pasts = self._forward(input_ids, past_key_values, mask, padding_position_ids(attention_mask, T), True, True)
-            pos = attention_mask.long().sum(-1, keepdim=True).repeat_interleave(nb, dim=0)
-            row = row.repeat_interleave(nb, dim=0)
-        else:
-            logits, pasts = self.forward(input_ids, past_key_values)
+        pb, logits, pasts = self._prompt_pass(input_ids, past_key_values, attention_mask, max_new_tokens, nb)
         # the fork: every request's rows repeated over its beams; rows of a group agree on every byte before `fork`
         fork = past_len + T
         caches = [p.layer.index_select(torch.arange(B, device=input_ids.device).repeat_interleave(nb)) for p in pasts]
-        s = 0
 
         def step(tok, beam_idx):
-            nonlocal s, pos
             for c in caches:
                 c.reorder_(beam_idx, group=nb, from_token=fork, check=False)
-            pasts = [c.as_tuple() for c in caches]
-            if row is None:
-                logits, _ = self.forward(tok, pasts)
-            else:
-                logits, _ = self._forward(tok, pasts, row[..., : fork + s + 1], pos, True, True)
-                pos = pos + 1
-            s += 1
+            logits, _ = self._decode_pass(tok, [c.as_tuple() for c in caches], pb)
             return logits[:, -1].float()
 
         seqs, scores = beam_search(step, input_ids, logits[:, -1].float(), nb, max_new_tokens, eos_token_id, pad_token_id,
@@ -415,14 +422,17 @@ class LlamaForCausalLM_KIVI(nn.Module):
         g.mask = new
         return True
 
-    def _rope_rows(self, g) -> None:
-        """cos / sin of the per-row positions g.pos (B,), as LlamaAttention_KIVI._rope computes them; then the positions advance."""
+    def _graph_inputs(self, g, caches, whole: bool, padded: bool, position: int) -> bool:
+        """The inputs of one graphed step in their static buffers: cos / sin of the step's position (padded: of the per-row positions
+        g.pos, which then advance, and room in the mask buffer -- True when that was reallocated)."""
         inv_freq = self.model.layers[0].self_attn.inv_freq
-        freqs = g.pos[:, None].float() * inv_freq[None, :].float()
-        emb = torch.cat((freqs, freqs), dim=-1)
-        g.cos.copy_(emb.cos().view(g.B, 1, 1, -1))
-        g.sin.copy_(emb.sin().view(g.B, 1, 1, -1))
+        cos, sin = rope_cos_sin(inv_freq, g.pos if padded else position)
+        g.cos.copy_(cos.view(-1, 1, 1, cos.shape[-1]))
+        g.sin.copy_(sin.view(-1, 1, 1, sin.shape[-1]))
+        if not padded:
+            return False
         g.pos += 1
+        return self._mask_room(g, caches, whole)
 
     @torch.no_grad()
     def decode_graphed(self, tok: torch.LongTensor, past_key_values: List, position: int, steps: int,
@@ -441,7 +451,6 @@ class LlamaForCausalLM_KIVI(nn.Module):
         padded = attention_mask is not None and self._padded(attention_mask, B, kv0 + 1, kv0)
         self.prepare_graphs(B, tok.device, whole, padded, sampler)
         g = self._graphs
-        attn0 = self.model.layers[0].self_attn
         g.tok.copy_(tok)
         if padded:
             if self._mask_room(g, caches, whole):
@@ -473,31 +482,16 @@ class LlamaForCausalLM_KIVI(nn.Module):
                 self._graphed = (g, drv, gd)
             for _ in range(steps):
                 out.append(g.tok.clone())
-                if padded:
-                    self._rope_rows(g)
-                    if self._mask_room(g, caches, whole):     # the stores grew: so did the buffer, capture again
-                        gd.graph, gd.warm = None, False
-                else:
-                    freqs = position * attn0.inv_freq.float()
-                    emb = torch.cat((freqs, freqs), dim=-1)
-                    g.cos.copy_(emb.cos().view(1, 1, 1, -1))
-                    g.sin.copy_(emb.sin().view(1, 1, 1, -1))
+                if self._graph_inputs(g, caches, whole, padded, position):     # the stores grew: so did the buffer, capture again
+                    gd.graph, gd.warm = None, False
                 gd.step()
                 position += 1
             self._last_graph_stats = (gd.eager, gd.captures, gd.replays)
             return torch.cat(out, dim=1)
         for _ in range(steps):
             out.append(g.tok.clone())
-            mask = None
-            if padded:
-                self._rope_rows(g)
-                self._mask_room(g, caches, whole)
-                mask = g.mask[..., : caches[0].kv_seq_len + 1]
-            else:
-                freqs = position * attn0.inv_freq.float()
-                emb = torch.cat((freqs, freqs), dim=-1)
-                g.cos.copy_(emb.cos().view(1, 1, 1, -1))
-                g.sin.copy_(emb.sin().view(1, 1, 1, -1))
+            self._graph_inputs(g, caches, whole, padded, position)
+            mask = g.mask[..., : caches[0].kv_seq_len + 1] if padded else None
             for i in range(len(self.model.layers)):
                 g.pre[i].replay()
                 q, k, v = g.qkv[i]

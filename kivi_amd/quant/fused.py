@@ -19,8 +19,7 @@ def decode_scores(layer, query_states: torch.Tensor, key_states: torch.Tensor, s
     key is appended to layer.k_res (the caller bumps layer.k_res_len).  query (B, nh, 1, D), key (B, nh_kv, 1, D)."""
     cfg = layer.cfg
     B, nh, _, D = query_states.shape
-    q = query_states if query_states.stride(3) == 1 else query_states.contiguous()
-    k = key_states if key_states.stride(3) == 1 else key_states.contiguous()
+    q, k = _lib.unit_rows(query_states), _lib.unit_rows(key_states)
     kc, ks, km, kr = layer.k_code, layer.k_scale, layer.k_mn, layer.k_res
     lib = _lib.load()
     hook = _matmul.launch_hook
@@ -44,11 +43,9 @@ def softmax_scaled(scores: torch.Tensor, probs: torch.Tensor, n: int, inv_scale:
     B, nh = scores.shape[0], scores.shape[1]
     assert scores.is_contiguous() and probs.is_contiguous() and scores.dtype == probs.dtype == torch.float16
     lib = _lib.load()
-    if mask is not None:
-        assert mask.shape == (B, 1, 1, n) and mask.dtype == torch.float16 and mask.stride(3) == 1
+    mask_ptr, mask_sb = _lib.mask_arg(mask, B, n)
     _lib.check(lib.kivi_softmax_scaled(_lib.ptr(scores), _lib.ptr(probs), B * nh, n, scores.stride(1), probs.stride(1),
-                                       float(inv_scale), _lib.ptr(mask) if mask is not None else None,
-                                       mask.stride(0) if mask is not None else 0, nh, _lib.stream_ptr(scores)),
+                                       float(inv_scale), mask_ptr, mask_sb, nh, _lib.stream_ptr(scores)),
                "kivi_softmax_scaled")
 
 
@@ -60,16 +57,14 @@ def decode_output(layer, probs: torch.Tensor, value_states: torch.Tensor, out: t
     With `softmax_inv_scale`, `probs` holds the PRE-softmax scores and scale + mask + softmax run inside the same launch."""
     cfg = layer.cfg
     B, nh = probs.shape[0], probs.shape[1]
-    v = value_states if value_states.stride(3) == 1 else value_states.contiguous()
+    v = _lib.unit_rows(value_states)
     vc, vs, vm, vr = layer.v_code, layer.v_scale, layer.v_mn, layer.v_res
     flush = layer.v_res_len + 1 > cfg.residual_length
     lib = _lib.load()
     if softmax_inv_scale is not None:
-        if mask is not None:
-            assert mask.dtype == torch.float16 and mask.stride(3) == 1
+        mask_ptr, mask_sb = _lib.mask_arg(mask, B, layer.kv_seq_len + 1)
         _lib.check(lib.kivi_decode_softmax_output(
-            _lib.ptr(probs), probs.stride(0), probs.stride(1), float(softmax_inv_scale),
-            _lib.ptr(mask) if mask is not None else None, mask.stride(0) if mask is not None else 0,
+            _lib.ptr(probs), probs.stride(0), probs.stride(1), float(softmax_inv_scale), mask_ptr, mask_sb,
             _lib.ptr(vc), vc.stride(0), vc.stride(1), vc.stride(2),
             _lib.ptr(vs), _lib.ptr(vm), vs.stride(0), vs.stride(1), vs.stride(2),
             _lib.ptr(vr), vr.stride(0), vr.stride(1), vr.stride(2), layer.v_res_start, layer.v_res_len,
@@ -112,21 +107,17 @@ def decode_attend(layer, query_states: torch.Tensor, key_states: torch.Tensor, v
     `scores[..., :Tq]` must already hold the packed part.  Returns True if the V flush happened."""
     cfg = layer.cfg
     B, nh, _, D = query_states.shape
-    q = query_states if query_states.stride(3) == 1 else query_states.contiguous()
-    k = key_states if key_states.stride(3) == 1 else key_states.contiguous()
-    v = value_states if value_states.stride(3) == 1 else value_states.contiguous()
+    q, k, v = _lib.unit_rows(query_states), _lib.unit_rows(key_states), _lib.unit_rows(value_states)
     vc, vs, vm, vr, kr = layer.v_code, layer.v_scale, layer.v_mn, layer.v_res, layer.k_res
     flush = layer.v_res_len + 1 > cfg.residual_length
-    if mask is not None:
-        assert mask.dtype == torch.float16 and mask.stride(3) == 1
+    mask_ptr, mask_sb = _lib.mask_arg(mask, B, layer.kv_seq_len + 1)
     ws = _workspace(q.device, B * nh, D)
     a = _lib.DecodeAttendArgs(
         q=q.data_ptr(), q_sb=q.stride(0), q_sh=q.stride(1),
         kres=kr.data_ptr(), kres_sb=kr.stride(0), kres_sh=kr.stride(1), kres_st=kr.stride(2),
         knew=k.data_ptr(), knew_sb=k.stride(0), knew_sh=k.stride(1), k_res_len=layer.k_res_len,
         scores=scores.data_ptr(), s_sb=scores.stride(0), s_sh=scores.stride(1),
-        inv_scale=float(inv_scale), mask=mask.data_ptr() if mask is not None else None,
-        mask_sb=mask.stride(0) if mask is not None else 0,
+        inv_scale=float(inv_scale), mask=mask_ptr, mask_sb=mask_sb,
         v_code=vc.data_ptr(), vc_sb=vc.stride(0), vc_sh=vc.stride(1), vc_sr=vc.stride(2),
         v_scale=vs.data_ptr(), v_mn=vm.data_ptr(), vs_sb=vs.stride(0), vs_sh=vs.stride(1), vs_sr=vs.stride(2),
         vres=vr.data_ptr(), vres_sb=vr.stride(0), vres_sh=vr.stride(1), vres_st=vr.stride(2),
