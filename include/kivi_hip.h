@@ -28,6 +28,8 @@
  *                               2-bit with nh / nh_kv in {1, 4, 8} or 4-bit with nh / nh_kv in {1, 4}), with the packers of that
  *                               cache: kivi_kt_pack, kivi_vt_pack, kivi_vt_pack_at, kivi_kt_relayout, kivi_vt_relayout
  *               beam search:    kivi_cache_reorder (in-place row reorder of either cache layout, from a fork point on)
+ *               rollback:       kivi_cache_snapshot (the fp16 residual / window and range words of a cache into a flat buffer and
+ *                               back: checkpoint and restore of either cache layout)
  *               sampling:       kivi_sample (temperature / top-k / top-p / min-p draw of one token per row, Philox RNG state on
  *                               the device)
  *   BUILDING BLOCKS (what the layer steps are composed of; exported for tests, tools and callers that keep their own cache
@@ -42,6 +44,7 @@
 #ifndef KIVI_HIP_H
 #define KIVI_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -536,6 +539,20 @@ typedef struct kivi_reorder_slab {
 } kivi_reorder_slab;
 int kivi_cache_reorder(const kivi_reorder_slab* slabs, int n_slabs, int B, int group, const void* idx, int idx_bytes,
                        kivi_stream_t stream);
+/*
+ * kivi_cache_snapshot: the byte ranges the slabs name, of every row, gathered into a flat buffer (direction 0) or scattered back
+ * from it (direction 1): checkpoint and rollback of a cache.  The slabs are those of kivi_cache_reorder
+ * (one store each, up to three (count, stride) levels, `run` bytes; base, strides and run multiples of 16 bytes, or of 4 for word
+ * moves).  Row b of the buffer starts at buf + b*buf_row_stride; inside it the slabs follow each other in the order given, byte
+ * (i0, i1, i2, j) of a slab at ((i0*n[1] + i1)*n[2] + i2)*run + j from the slab's start, and every slab starts on a 16-byte boundary
+ * (a slab with a zero count or run takes no room).  One launch, no LDS, no scratch memory; a thread issues four independent loads
+ * before its first store.  The cache side of direction 1 may be another allocation than the one direction 0 read (the cache grew).
+ * Before anything is enqueued: KIVI_EINVAL for n_slabs outside [1, KIVI_REORDER_MAX_SLABS], B outside [1, 65535], a null slabs /
+ * buf / slab base, a negative count, buf_row_stride zero or below what the slabs of a row take, direction not 0 or 1; KIVI_EALIGN for
+ * a slab base / stride / run that is not a multiple of 4 bytes, buf or buf_row_stride not a multiple of 16.
+ */
+int kivi_cache_snapshot(const kivi_reorder_slab* slabs, int n_slabs, int B, void* buf, size_t buf_row_stride, int direction,
+                        kivi_stream_t stream);
 /*
  * kivi_sample: one token per row drawn from (B, V) logits the way transformers' do_sample path does:
  * s = float(logit) / temperature; keep s >= the top_k-th largest s (ties kept; top_k = 0 or >= V: off); renormalise over those and

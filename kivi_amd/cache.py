@@ -33,7 +33,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from . import _lib, _tuning, reorder
+from . import _lib, _tuning, checkpoint, reorder
 from ._lib import KiviUnsupported, check_mask_size, mask_arg, out_arg, unit_rows
 from .quant import fused, matmul, new_pack
 
@@ -113,7 +113,7 @@ class KiviPerformanceWarning(UserWarning):
 class KiviCacheBase:
     """What the two layouts of a layer's cache (KiviLayerCache here, KiviLayerCacheMF in cache_mf.py) share: the geometry, the six
     lengths of the state machine, the scratch of a decode step, and everything that follows from them alone.  A layout adds its
-    buffers (`reserve`, `_own_buffers`, `_reorder_slabs`, `prefill`), the readers of the reference layout
+    buffers (`reserve`, `_own_buffers`, `_reorder_slabs`, `_checkpoint_slabs`, `prefill`), the readers of the reference layout
     (`k_quant_reference_layout`, `v_quant_views`, `v_res_view`) and its steps (`decode_step`, `extend`)."""
 
     def __init__(self, cfg: KiviConfig, batch: int, num_kv_heads: int, head_dim: int, max_len: int, dtype):
@@ -132,6 +132,7 @@ class KiviCacheBase:
         self._scores = self._probs = None     # (B, nh, 1, pitch) fp16 scratch rows of the multi-launch forms (hook-state layout)
         # fusion levels this cache has left for good (hook-state layout: KiviLayerCache._drop_fusion)
         self._attend_unfusable = self._softmax_unfusable = self._fused_unsupported = False
+        self._forget_checkpoints()
 
     def _invalidate(self) -> None:
         """Forget the native descriptor and the scratch rows: they point into / are sized for buffers that have just been replaced."""
@@ -159,6 +160,7 @@ class KiviCacheBase:
         other = copy.copy(self)
         other._own_buffers(None)
         other._invalidate()
+        other._forget_checkpoints()
         return other
 
     def index_select(self, idx):
@@ -171,6 +173,7 @@ class KiviCacheBase:
         other.B = idx.numel()
         other._own_buffers(idx)
         other._invalidate()
+        other._forget_checkpoints()
         return other
 
     # ------------------------------------------------------------------ beam search
@@ -185,6 +188,66 @@ class KiviCacheBase:
             raise ValueError(f"from_token={from_token} lies beyond the cache length {self.kv_seq_len}")
         idx = reorder.check_idx(idx, self.B, group, self.k_res.device, check)
         reorder.run(self._reorder_slabs(int(from_token)), self.B, group, idx)
+        self._void_checkpoints()          # rows have changed places: no rollback across a reorder
+        return self
+
+    # ------------------------------------------------------------------ checkpoint / rollback
+    def _forget_checkpoints(self) -> None:
+        """A cache of its own (new, cloned, index_selected): no checkpoint issued so far belongs to it."""
+        self._ck_owner = object()
+        self._ck_serial = 0      # checkpoints issued so far
+        self._ck_lows = []       # [(serial at the time, length)]: restores (and, with length -1, reorders / prompt passes) that made
+                                 # checkpoints stale -- only the entries no later one covers, so lengths rise with the serials
+
+    def _void_checkpoints(self) -> None:
+        """Every checkpoint issued so far becomes stale (reorder_, a new prompt pass)."""
+        self._ck_lows = [(self._ck_serial, -1)]
+
+    def _geometry(self) -> tuple:
+        c = self.cfg
+        return (type(self).__name__, self.B, self.nh_kv, self.D, getattr(self, "nh", None), c.k_bits, c.v_bits, c.group_size,
+                c.residual_length)
+
+    def checkpoint(self) -> "checkpoint.KiviCheckpoint":
+        """The state to come back to with restore_(): the six lengths, the fusion flags and, through ONE kivi_cache_snapshot launch
+        into a buffer the checkpoint owns, the bytes later steps overwrite in place (`_checkpoint_slabs`: the live fp16 K residual,
+        the fp16 V window, the range words).  The packed stores are not copied: steps only write them from the packed lengths on.
+        Any number of checkpoints may be outstanding; they hold no view into the cache and survive reserve()."""
+        slabs = self._checkpoint_slabs()
+        buf = torch.empty((self.B, checkpoint.row_bytes(slabs)), dtype=torch.uint8, device=self.k_res.device)
+        checkpoint.run(slabs, self.B, buf, 0)
+        self._ck_serial += 1
+        return checkpoint.KiviCheckpoint(self._geometry(), self._ck_owner, self._ck_serial,
+                                         tuple(int(getattr(self, n)) for n in checkpoint.LENGTHS),
+                                         tuple(bool(getattr(self, n)) for n in checkpoint.FLAGS), buf)
+
+    def check_restore(self, ck) -> None:
+        """Raise ValueError when restore_(ck) would not give back the state `ck` was taken at (nothing runs on a device)."""
+        if not isinstance(ck, checkpoint.KiviCheckpoint):
+            raise ValueError(f"restore_ takes a KiviCheckpoint (KiviCacheBase.checkpoint()), got {type(ck).__name__}")
+        if ck.geometry != self._geometry():
+            raise ValueError(f"the checkpoint comes from another geometry or layout: {ck.geometry}, this cache is {self._geometry()}")
+        if ck.owner is not self._ck_owner:
+            raise ValueError("the checkpoint comes from another cache (a clone or index_select starts without checkpoints)")
+        if ck.kv_seq_len > self.kv_seq_len:
+            raise ValueError(f"the checkpoint was taken at kv length {ck.kv_seq_len}, beyond the cache's {self.kv_seq_len}")
+        for serial, low in self._ck_lows:
+            if serial >= ck.serial and low < ck.kv_seq_len:
+                what = "reordered or prefilled again" if low < 0 else f"restored to kv length {low}"
+                raise ValueError(f"stale checkpoint: taken at kv length {ck.kv_seq_len}, the cache has since been {what}, so the "
+                                 f"packed stores beyond that point no longer hold what the checkpoint continues")
+
+    def restore_(self, ck):
+        """Back to the state checkpoint() saw, exactly (the 9-tuple, the range words and every later step are bit-identical to a
+        cache that never went further): one scatter launch into the buffers as they are now, then the lengths and flags.  Nothing
+        is reallocated or shrunk; the native descriptors and captured graphs stay valid.  Tuples issued before are stale: take
+        as_tuple() again.  ValueError (before anything runs on a device) for a checkpoint of another geometry, layout or cache, one
+        beyond the current length, or a stale one: the cache has since been restored below it, reordered or prefilled again."""
+        self.check_restore(ck)
+        checkpoint.run(self._checkpoint_slabs(dict(zip(checkpoint.LENGTHS, ck.state))), self.B, ck.buf, 1)
+        for n, v in zip(checkpoint.LENGTHS + checkpoint.FLAGS, ck.state + ck.flags):
+            setattr(self, n, v)
+        self._ck_lows = [(s, low) for s, low in self._ck_lows if low < ck.kv_seq_len] + [(self._ck_serial, ck.kv_seq_len)]
         return self
 
     # ------------------------------------------------------------------ the 9-tuple
@@ -317,6 +380,20 @@ class KiviLayerCache(KiviCacheBase):
             out.append(slab(self.v_res, b0, [(h, self.v_res.stride(1) * 2)], b1 - b0))
         return out
 
+    def _checkpoint_slabs(self, state=None):
+        """What steps overwrite in place, at the lengths `state` (default: the current ones): the live rows of the fp16 K residual and
+        of the fp16 V window.  (This layout has no range words.)"""
+        from .reorder import slab
+        kl, vs, vl = (self.k_res_len, self.v_res_start, self.v_res_len) if state is None else \
+            (state["k_res_len"], state["v_res_start"], state["v_res_len"])
+        h, rowb = self.nh_kv, self.D * 2
+        out = []
+        if kl:
+            out.append(slab(self.k_res, 0, [(h, self.k_res.stride(1) * 2)], kl * rowb))
+        if vl:
+            out.append(slab(self.v_res, vs * rowb, [(h, self.v_res.stride(1) * 2)], vl * rowb))
+        return out
+
     # ------------------------------------------------------------------ the 9-tuple
     def k_quant_reference_layout(self):
         """(K_code_T, K_scale_T, K_mn_T) in the reference layout (B, nh_kv, D, Tq/...): gathers the pages (a copy)."""
@@ -367,6 +444,7 @@ class KiviLayerCache(KiviCacheBase):
         R, g = cfg.residual_length, cfg.group_size
         T = key_states.shape[2]
         self.reserve(T)
+        self._void_checkpoints()
         nq = (T // R) * R                      # quantised K prefix, fp16 remainder T % R
         if nq:
             self._quantise_k(key_states[:, :, :nq], 0)

@@ -160,6 +160,20 @@ class KiviLayerCacheMF(KiviCacheBase):
         out.append(slab(self.v_res, 0, [(h, self.v_res.stride(1) * 2)], self.v_res.shape[2] * self.D * 2))
         return out
 
+    def _checkpoint_slabs(self, state=None):
+        """What steps overwrite in place: the fp16 K residual up to its length (`state`: the lengths to use, default the current ones),
+        the whole fp16 V ring, the range words of both stores."""
+        from .reorder import slab
+        kl = self.k_res_len if state is None else state["k_res_len"]
+        h = self.nh_kv
+        out = []
+        if kl:
+            out.append(slab(self.k_res, 0, [(h, self.k_res.stride(1) * 2)], kl * self.D * 2))
+        out.append(slab(self.v_res, 0, [(h, self.v_res.stride(1) * 2)], self.v_res.shape[2] * self.D * 2))
+        for st in (self.kt, self.vt):
+            out.append(slab(mfma.range_flags(st), 0, [], h * 4))
+        return out
+
     # ------------------------------------------------------------------ the 9-tuple
     def k_quant_reference_layout(self):
         if self.k_quant_len == 0:
@@ -186,6 +200,7 @@ class KiviLayerCacheMF(KiviCacheBase):
         R, g = cfg.residual_length, cfg.group_size
         T = key_states.shape[2]
         self.reserve(T)
+        self._void_checkpoints()
         if self.kv_seq_len:        # reuse of the object: the V slots are filled token by token later, start from clean storage
             for st in (self.kt, self.vt):
                 st.zero_()

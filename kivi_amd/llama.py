@@ -237,6 +237,35 @@ class LlamaForCausalLM_KIVI(nn.Module):
                 out.append(layer.reorder_(beam_idx).as_tuple())
         return tuple(out)
 
+    # ------------------------------------------------------------------ checkpoint / rollback
+    @staticmethod
+    def _layer_caches(past_key_values, what: str):
+        caches = [getattr(p, "layer", None) for p in past_key_values or ()]
+        if not caches or any(c is None for c in caches):
+            raise ValueError(f"{what} needs the tuples of an in-place cache (what forward() / generate() return), not plain 9-tuples")
+        return caches
+
+    @classmethod
+    def checkpoint(cls, past_key_values) -> "KiviModelCheckpoint":
+        """The state of every layer's cache to come back to with restore_(): one launch per layer, a few MB where the caches hold
+        hundreds (KiviCacheBase.checkpoint).  `past_key_values`: the tuples of forward() / generate(); a tuple whose length is stale
+        still names its cache."""
+        from .checkpoint import KiviModelCheckpoint
+        caches = cls._layer_caches(past_key_values, "checkpoint")
+        return KiviModelCheckpoint([c.checkpoint() for c in caches], caches[0].kv_seq_len)
+
+    @classmethod
+    def restore_(cls, past_key_values, ck) -> List:
+        """Every layer's cache back to the checkpoint, exactly and in place (KiviCacheBase.restore_); returns fresh tuples to
+        continue from with forward(), generate(past_key_values=...) or decode_graphed().  ValueError before any cache is touched when
+        one of them refuses the checkpoint (another model shape, a stale checkpoint)."""
+        caches = cls._layer_caches(past_key_values, "restore_")
+        if len(caches) != len(ck.layers):
+            raise ValueError(f"the checkpoint holds {len(ck.layers)} layers, past_key_values {len(caches)}")
+        for c, k in zip(caches, ck.layers):
+            c.check_restore(k)
+        return [c.restore_(k).as_tuple() for c, k in zip(caches, ck.layers)]
+
     @torch.no_grad()
     def generate(self, input_ids: torch.LongTensor, max_new_tokens: int, past_key_values: Optional[List] = None,
                  attention_mask: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
