@@ -32,6 +32,7 @@
  *                               back: checkpoint and restore of either cache layout)
  *               sampling:       kivi_sample (temperature / top-k / top-p / min-p draw of one token per row, Philox RNG state on
  *                               the device)
+ *               scoring:        kivi_token_logprob (log-probability and rank of one given token per row of logits)
  *   BUILDING BLOCKS (what the layer steps are composed of; exported for tests, tools and callers that keep their own cache
  *               bookkeeping -- same contracts, but no stability promise beyond the ABI version):  kivi_gemv_k_paged,
  *               kivi_decode_scores, kivi_softmax_scaled, kivi_decode_output, kivi_decode_softmax_output, kivi_decode_attend,
@@ -574,6 +575,26 @@ int kivi_cache_snapshot(const kivi_reorder_slab* slabs, int n_slabs, int B, void
 #define KIVI_SAMPLE_MAX_V (1 << 20)
 int kivi_sample(const void* logits, int logits_bits, int64_t row_stride, int B, int V, float temperature, int top_k, float top_p,
                 float min_p, int64_t* rng_state, int64_t* out_tokens, int64_t out_stride, kivi_stream_t stream);
+/*
+ * kivi_token_logprob: the log-probability of one given token per row of (N, V) logits, log-softmax + gather in one launch without
+ * an fp32 (N, V) intermediate (teacher-forced scoring, perplexity, the log-probabilities of generated tokens).
+ * Per row r, with t = targets[r * target_stride] and x_j = float(logit[r, j]):
+ *   m = max_j x_j;  S = sum_j floor(exp(x_j - m) * 2^40), a 64-bit integer sum of the weights kivi_sample draws from, so the result
+ *   does not depend on the order of the additions (the same row gives the same bits strided or contiguous, eager or replayed);
+ *   lse = m + log(S * 2^-40);  out_logprob[r] = x_t - lse;  out_lse[r] = lse (when given);
+ *   out_rank[r] (when given) = #{j : x_j > x_t, or x_j == x_t and j < t}: 0 exactly when argmax of the row is t.
+ *   t == ignore_index: logprob 0, rank -1, lse written.  Any other t outside [0, V): logprob NaN, rank -1, lse written.
+ *   logits      fp16 (logits_bits 16) or fp32 (32); row r starts at logits + r * row_stride elements and is contiguous
+ *   targets     int64;  out_logprob / out_lse fp32 and out_rank int32, N contiguous entries each; out_lse and out_rank may be null
+ * -inf logits are legal and weigh 0; a target on one gives -inf.  A row that is all -inf or holds NaN / +inf gets some value.
+ * One 1024-thread workgroup per row, rows taken grid-stride: N is not bounded by the grid.
+ * KIVI_EINVAL (nothing enqueued) for logits_bits not 16 / 32, N < 1, V outside [1, KIVI_SAMPLE_MAX_V], row_stride < V or
+ * target_stride < 1 (N > 1), a null logits / targets / out_logprob; KIVI_EALIGN for logits not aligned to its element, targets not
+ * 8-byte aligned, an output not 4-byte aligned.
+ */
+int kivi_token_logprob(const void* logits, int logits_bits, int64_t row_stride, int64_t N, int V, const int64_t* targets,
+                       int64_t target_stride, int64_t ignore_index, float* out_logprob, float* out_lse, int32_t* out_rank,
+                       kivi_stream_t stream);
 /* geometry class of a step (-1: bad arguments): the super-block counts of both stores and whether the step flushes a value; the
  * launch plan (one launch / S slices / two launches) is a function of the class and of constants of the call (shape, bits, flags) */
 int64_t kivi_mf_step_key(const kivi_mf_step* step, int B, int nh, int nh_kv, int residual_length, int flags);

@@ -182,26 +182,34 @@ class LlamaForCausalLM_KIVI(nn.Module):
         return self._forward(input_ids, past_key_values, pb.mask, pb.position_ids, last_token_only, True)
 
     def _forward(self, input_ids, past_key_values, attention_mask, position_ids, last_token_only, mask_prompt):
+        x, new = self._hidden(input_ids, past_key_values, attention_mask, position_ids, mask_prompt)
+        if last_token_only:
+            x = x[:, -1:]
+        return self.lm_head(self.model.norm(x)), new
+
+    def _hidden(self, input_ids, past_key_values, attention_mask, position_ids, mask_prompt):
+        """The decoder blocks of a pass -> (hidden states (B, T, H) before the final norm, new past_key_values)."""
         pasts = past_key_values or [None] * len(self.model.layers)
         x = self.model.embed_tokens(input_ids)
         new = []
         for layer, past in zip(self.model.layers, pasts):
             x, p = layer(x, past, attention_mask if past is not None or mask_prompt else None, position_ids)
             new.append(p)
-        if last_token_only:
-            x = x[:, -1:]
-        return self.lm_head(self.model.norm(x)), new
+        return x, new
 
     @staticmethod
     def _past_len(past_key_values) -> int:
         return int(past_key_values[0][-1]) if past_key_values and past_key_values[0] is not None else 0
 
-    def _padded(self, mask: torch.Tensor, B: int, length: int, past_len: int) -> bool:
-        """Validate a 2D padding mask; True when it holds a pad (False: the caller takes the unmasked path, no mask is built)."""
+    def _padded(self, mask: torch.Tensor, B: int, length: int, past_len: int, has_pad: Optional[bool] = None) -> bool:
+        """Validate a 2D padding mask; True when it holds a pad (False: the caller takes the unmasked path, no mask is built).
+        `has_pad`: what the caller already knows about the mask (spares the synchronisation)."""
         if mask.dim() != 2 or tuple(mask.shape) != (B, length):
             raise ValueError(f"the 2D attention / padding mask should be of size {(B, length)} (history + new tokens), "
                              f"but is {tuple(mask.shape)}")
-        if bool((mask != 0).all()):
+        if has_pad is None:
+            has_pad = not bool((mask != 0).all())
+        if not has_pad:
             return False
         if past_len == 0 and not all(layer.self_attn._prefill_uses_mask for layer in self.model.layers):
             raise ValueError(f"{type(self.model.layers[0].self_attn).__name__}: the prompt pass of this attention class ignores "
@@ -266,13 +274,111 @@ class LlamaForCausalLM_KIVI(nn.Module):
             c.check_restore(k)
         return [c.restore_(k).as_tuple() for c, k in zip(caches, ck.layers)]
 
+    # ------------------------------------------------------------------ scoring given tokens
+    _HEAD_SLAB = 4096            # rows of hidden states per lm_head call of score(): logits exist for one slab at a time
+
+    def _score_plan(self, input_ids, first_chunk, chunk_size):
+        """The [a, b) token ranges of the passes of a score() call; ValueError for arguments that cannot be scored (no device work)."""
+        if input_ids.dim() != 2 or input_ids.shape[1] < 2:
+            raise ValueError(f"score needs input_ids (B, T) with T >= 2 (entry i scores token i + 1), got {tuple(input_ids.shape)}")
+        T = input_ids.shape[1]
+        first = T if first_chunk is None else first_chunk
+        if isinstance(first, bool) or not isinstance(first, int) or not 1 <= first <= T:
+            raise ValueError(f"first_chunk has to be an integer in [1, T = {T}], got {first_chunk!r}")
+        step = max(T - first, 1) if chunk_size is None else chunk_size
+        if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+            raise ValueError(f"chunk_size has to be a positive integer, got {chunk_size!r}")
+        return [(0, first)] + [(a, min(a + step, T)) for a in range(first, T, step)]
+
+    def _head_logprobs(self, x, targets, return_rank):
+        """token_logprobs of `targets` (B, q) under lm_head(norm(x)), x (B, q, H): the head runs on slabs of at most _HEAD_SLAB rows
+        (one slab: the very call forward() makes), so logits never exist for more rows than that."""
+        from .scoring import token_logprobs
+        h = self.model.norm(x)
+        B, q = targets.shape
+        if B * q <= self._HEAD_SLAB:
+            res = token_logprobs(self.lm_head(h), targets, return_rank=return_rank)
+            return res if return_rank else (res, None)
+        h, t = h.reshape(B * q, -1), targets.reshape(-1)
+        lp = torch.empty(B * q, dtype=torch.float32, device=x.device)
+        rk = torch.empty(B * q, dtype=torch.int32, device=x.device) if return_rank else None
+        for s in range(0, B * q, self._HEAD_SLAB):
+            res = token_logprobs(self.lm_head(h[s: s + self._HEAD_SLAB]), t[s: s + self._HEAD_SLAB], return_rank=return_rank)
+            if return_rank:
+                lp[s: s + self._HEAD_SLAB], rk[s: s + self._HEAD_SLAB] = res
+            else:
+                lp[s: s + self._HEAD_SLAB] = res
+        return lp.view(B, q), rk.view(B, q) if return_rank else None
+
+    @torch.no_grad()
+    def score(self, input_ids: torch.LongTensor, attention_mask: Optional[torch.Tensor] = None,
+              past_key_values: Optional[List] = None, first_chunk: Optional[int] = None, chunk_size: Optional[int] = None,
+              return_rank: bool = False):
+        """Teacher-forced log-probabilities of given tokens: (logprobs (B, T - 1) fp32, valid (B, T - 1) bool, past_key_values)
+        [, ranks (B, T - 1) int32 with `return_rank`: 0 where the token is the argmax of its distribution, -1 where not valid].
+        Entry i is log p(input_ids[:, i + 1] | tokens <= i) under the model's raw distribution (kivi_amd/scoring.py,
+        kivi_token_logprob); the caches are advanced over all T tokens, in place when `past_key_values` is given.
+
+        `first_chunk` / `chunk_size` decide what the score measures.  The first `first_chunk` tokens (default: all T) go through the
+        prompt pass -- with `past_key_values` through the multi-token extend over the caches of the earlier turn -- and the rest in
+        pieces of `chunk_size` tokens (default: one piece), each a q_len > 1 extend over the QUANTISED cache, or the decode step when
+        chunk_size == 1.  The prompt pass attends in fp16 and quantises afterwards, as the reference does, so a one-pass score does
+        not see the quantiser at all; a chunked score does, and score(first_chunk=P, chunk_size=1) is exactly the arithmetic of
+        generate() after a P-token prompt.  To measure what k_bits / v_bits / group_size / residual_length cost a model, chunk.
+
+        `attention_mask`: HF's 2D left-padding mask (B, past + T) over the history and `input_ids`; entries whose target or context
+        token is a pad have valid == False and logprob 0.  Every piece runs the padded path of forward() on the mask's first
+        past + (tokens so far) columns (pads are on the left, so every such slice holds them).  Token ids are validated against
+        vocab_size, and the mask is looked at, once: one synchronisation per call.  T < 2, a chunk size < 1 or first_chunk outside
+        [1, T] raise ValueError before any device work."""
+        plan = self._score_plan(input_ids, first_chunk, chunk_size)
+        B, T = input_ids.shape
+        facts = list(torch.aminmax(input_ids))
+        if attention_mask is not None:
+            facts.append((attention_mask == 0).any().to(input_ids.device, torch.long))
+        lo, hi, *has_pad = (int(v) for v in torch.stack(facts).tolist())
+        if lo < 0 or hi >= self.config.vocab_size:
+            raise ValueError(f"input_ids hold token ids in [{lo}, {hi}], outside the vocabulary [0, {self.config.vocab_size})")
+        past_len = self._past_len(past_key_values)
+        valid = torch.ones((B, T - 1), dtype=torch.bool, device=input_ids.device)
+        padded = attention_mask is not None and self._padded(attention_mask, B, past_len + T, past_len, bool(has_pad[0]))
+        if padded:
+            real = attention_mask[:, past_len:] != 0
+            valid = real[:, 1:] & real[:, :-1]
+        targets = torch.full((B, T), -100, dtype=torch.long, device=input_ids.device)     # the last token has nothing to predict
+        targets[:, :-1] = torch.where(valid, input_ids[:, 1:], targets[:, :-1])
+        logprobs = torch.empty((B, T), dtype=torch.float32, device=input_ids.device)
+        ranks = torch.empty((B, T), dtype=torch.int32, device=input_ids.device) if return_rank else None
+        pasts = past_key_values
+        for a, b in plan:
+            if padded:
+                pb = _PaddedBatch(attention_mask[:, : past_len + b], past_len + a, b - a)
+                x, pasts = self._hidden(input_ids[:, a:b], pasts, pb.mask, pb.position_ids, True)
+            else:
+                x, pasts = self._hidden(input_ids[:, a:b], pasts, None, None, False)
+            lp, rk = self._head_logprobs(x, targets[:, a:b], return_rank)
+            logprobs[:, a:b] = lp
+            if return_rank:
+                ranks[:, a:b] = rk
+        res = (logprobs[:, :-1], valid, pasts)
+        return res + (ranks[:, :-1],) if return_rank else res
+
+    @torch.no_grad()
+    def perplexity(self, input_ids: torch.LongTensor, attention_mask: Optional[torch.Tensor] = None,
+                   past_key_values: Optional[List] = None, first_chunk: Optional[int] = None, chunk_size: Optional[int] = None):
+        """exp(-sum of the valid log-probabilities / number of valid entries) of score() with the same arguments:
+        (per row (B,), over all rows ()) float64 on the device, the sums taken in fp64.  A row without a valid entry gives NaN."""
+        lp, valid, _ = self.score(input_ids, attention_mask, past_key_values, first_chunk, chunk_size)
+        s, n = lp.double().sum(-1), valid.sum(-1).double()              # invalid entries are exactly 0
+        return torch.exp(-s / n), torch.exp(-s.sum() / n.sum())
+
     @torch.no_grad()
     def generate(self, input_ids: torch.LongTensor, max_new_tokens: int, past_key_values: Optional[List] = None,
                  attention_mask: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False, do_sample: bool = False,
                  temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
-                 seed: Optional[int] = None):
+                 seed: Optional[int] = None, return_logprobs: bool = False):
         """Greedy decoding (the recipe of the reference's mem_spd_test.py / example.py), or sampling with `do_sample=True`.
         With `past_key_values` (the caches of an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one
         pass (kivi_attention_extend) and decoding continues from there; the caches are advanced in place.  `attention_mask`:
@@ -288,7 +394,19 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
         `do_sample=True`: transformers' sampling path with HF's parameters and defaults (`temperature`, `top_k`, `top_p`, `min_p`),
         drawn by the fused HIP sampler (kivi_amd/sampling.py).  `seed`: the Philox seed of the call (None: one
-        drawn from torch's default CPU generator); token i of the call is draw i of every row.  Not with beams."""
+        drawn from torch's default CPU generator); token i of the call is draw i of every row.  Not with beams.
+
+        `return_logprobs=True` (greedy and sampling): returns (sequences, logprobs (B, generated) fp32), the log-probability of each
+        emitted token under the model's RAW distribution -- temperature 1 and unfiltered, what HF derives from `output_logits`, not
+        from the processed `output_scores` -- one kivi_token_logprob call per step on the logits the step has anyway; the pads of a
+        row that has finished get 0.  On live positions they are score(sequences, first_chunk=T, chunk_size=1)[0][:, T - 1:]: bit for
+        bit from the second new token on (the same head call on the same states); the first new token is scored on the prompt
+        pass, whose head runs here on the last position alone and in score() on all T positions -- the same arithmetic, in
+        whatever kernel the GEMM library picks for each row count.
+        With beams use `return_scores`."""
+        if return_logprobs and num_beams > 1:
+            raise ValueError("return_logprobs is for greedy decoding and sampling; beam search (num_beams > 1) returns its "
+                             "sequences_scores with return_scores=True")
         sampler = self._sampler(input_ids.device, do_sample, num_beams, temperature, top_k, top_p, min_p, seed)
         if eos_token_id is not None and pad_token_id is None:
             raise ValueError("eos_token_id needs a pad_token_id for the rows that have finished")
@@ -301,19 +419,26 @@ class LlamaForCausalLM_KIVI(nn.Module):
             raise ValueError("return_scores: sequences_scores exist for beam search (num_beams > 1) only")
         B = input_ids.shape[0]
         pb, logits, pasts = self._prompt_pass(input_ids, past_key_values, attention_mask, max_new_tokens)
-        out = [input_ids]
+        out, lps = [input_ids], []
+        if return_logprobs:
+            from .scoring import token_logprobs
         pick = (lambda lg: lg.argmax(-1)) if sampler is None else sampler
         tok = pick(logits)
         live = None if eos_token_id is None else torch.ones((B, 1), dtype=torch.bool, device=tok.device)
         for _ in range(max_new_tokens):
             if live is not None:
                 tok = torch.where(live, tok, torch.full_like(tok, pad_token_id))
+            if return_logprobs:                            # a finished row scores nothing: its target is the ignore_index
+                lps.append(token_logprobs(logits, tok if live is None else torch.where(live, tok, torch.full_like(tok, -100))))
+            if live is not None:
                 live = live & (tok != eos_token_id)
             out.append(tok)
             if live is not None and not bool(live.any()):
                 break
             logits, pasts = self._decode_pass(tok, pasts, pb)
             tok = pick(logits)
+        if return_logprobs:
+            return torch.cat(out, dim=1), torch.cat(lps or [logits.new_empty((B, 0), dtype=torch.float32)], dim=1)
         return torch.cat(out, dim=1)
 
     @staticmethod
