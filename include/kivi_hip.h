@@ -31,7 +31,8 @@
  *               rollback:       kivi_cache_snapshot (the fp16 residual / window and range words of a cache into a flat buffer and
  *                               back: checkpoint and restore of either cache layout)
  *               sampling:       kivi_sample (temperature / top-k / top-p / min-p draw of one token per row, Philox RNG state on
- *                               the device)
+ *                               the device), kivi_sample_rows (the same draw with per-row parameters, seeds, streams and
+ *                               greedy rows read from device memory)
  *               scoring:        kivi_token_logprob (log-probability and rank of one given token per row of logits)
  *   BUILDING BLOCKS (what the layer steps are composed of; exported for tests, tools and callers that keep their own cache
  *               bookkeeping -- same contracts, but no stability promise beyond the ABI version):  kivi_gemv_k_paged,
@@ -575,6 +576,42 @@ int kivi_cache_snapshot(const kivi_reorder_slab* slabs, int n_slabs, int B, void
 #define KIVI_SAMPLE_MAX_V (1 << 20)
 int kivi_sample(const void* logits, int logits_bits, int64_t row_stride, int B, int V, float temperature, int top_k, float top_p,
                 float min_p, int64_t* rng_state, int64_t* out_tokens, int64_t out_stride, kivi_stream_t stream);
+/*
+ * kivi_sample_rows: kivi_sample with the parameters and the RNG stream of every row read from device memory:
+ * requests with different parameters -- greedy ones among them -- share one launch, and a row's token is a function of its logits,
+ * its record and its draw index alone, not of the row it sits in.  Row b is processed exactly as kivi_sample processes a row, with
+ * temperature / top_k / top_p / min_p of rows[b] (the same fp32 arithmetic, tie classes and 2^40 integer weights), and
+ *   u = (x0 >> 8) * 2^-24, x0 the first word of Philox4x32-10 at key (seed low 32 bits, seed high 32 bits) and counter
+ *   (rows[b].stream, 0, n low 32 bits, n high 32 bits), n = draw_index[b].
+ * THE IDENTITY: kivi_sample on B rows at {seed, n} gives, token for token, what kivi_sample_rows gives with rows[b].seed = seed,
+ * rows[b].stream = b, draw_index[b] = n and the same four parameters in every record.
+ *   rows        B records in device memory, read only
+ *   draw_index  int64[B] in device memory; after its draw the workgroup of row b stores n + 1 itself (one launch in all: a captured
+ *               graph replays without host writes, and a host write to one row's record or index touches no other row)
+ *   flags       KIVI_SAMPLE_ROW_GREEDY: the token is the lowest index j that maximises float(logit[j]) (the tie rule of
+ *               kivi_token_logprob's rank; a -inf logit is chosen only when the whole row is -inf).  No random number is consumed,
+ *               temperature and the filters are ignored; draw_index[b] still advances, so it counts calls.
+ * logits, out_tokens and the unusual rows (all -inf, NaN, +inf: some token in [0, V)) as in kivi_sample.
+ * The values INSIDE the records cannot be checked by the host entry (the caller validates them; kivi_amd/sampling.py does).  A record
+ * outside the contract degrades, it never loops and never indexes outside its row:  top_k < 0 is read as 0 (off);  top_p is clamped
+ * into (0, 1] (NaN or > 1: 1, off; <= 0: the smallest positive float, the top tie class alone);  min_p is clamped into [0, 1) (NaN
+ * or < 0: 0, off; >= 1: the largest float below 1);  a temperature that is not finite or is <= 0 makes the row greedy.
+ * KIVI_EINVAL (nothing enqueued) for logits_bits not 16 / 32, B outside [1, KIVI_SAMPLE_MAX_B], V outside [1, KIVI_SAMPLE_MAX_V],
+ * row_stride < V or out_stride < 1 (B > 1), a null logits / rows / draw_index / out_tokens; KIVI_EALIGN for logits not aligned to
+ * its element, rows, draw_index or out_tokens not 8-byte aligned.
+ */
+#define KIVI_SAMPLE_ROW_GREEDY 1u
+typedef struct {         /* 32 bytes, 8-byte aligned */
+    float temperature;   /* finite, > 0 (ignored for a greedy row) */
+    int32_t top_k;       /* >= 0, 0 = off */
+    float top_p;         /* (0, 1], 1 = off */
+    float min_p;         /* [0, 1), 0 = off */
+    int64_t seed;        /* Philox key (low 32 bits, high 32 bits) */
+    uint32_t stream;     /* Philox counter word 0 */
+    uint32_t flags;      /* KIVI_SAMPLE_ROW_* */
+} kivi_sample_row;
+int kivi_sample_rows(const void* logits, int logits_bits, int64_t row_stride, int B, int V, const kivi_sample_row* rows,
+                     int64_t* draw_index, int64_t* out_tokens, int64_t out_stride, kivi_stream_t stream);
 /*
  * kivi_token_logprob: the log-probability of one given token per row of (N, V) logits, log-softmax + gather in one launch without
  * an fp32 (N, V) intermediate (teacher-forced scoring, perplexity, the log-probabilities of generated tokens).

@@ -14,7 +14,9 @@
 //   draw          1 pass: per bucket (BS consecutive tokens, one wave each) the kept weight; a block scan over the <= 1024 buckets
 //                 finds the bucket where the running sum crosses u * S; wave 0 scans that bucket's tokens.
 // The row is read from memory in every pass (an L2 hit after the first); nothing is staged, so any V up to KIVI_SAMPLE_MAX_V works.
-// A second, one-thread launch advances the draw counter n of the RNG state after the sampler has read it.
+// kivi_sample: a second, one-thread launch advances the draw counter n of the RNG state after the sampler has read it.
+// kivi_sample_rows: the same row body with parameters, seed, stream and draw index read per row from device
+// memory; a greedy flag per row; each block advances its own row's draw index.
 #include "kivi_common.h"
 
 namespace {
@@ -167,13 +169,14 @@ __device__ uint32_t radix_select(Shared& sh, const Row<T>& row, int e0, int e1, 
     return prefix;
 }
 
+// One row, by the whole workgroup: the body of both kernels.  Every branch below is on values that are the same for all threads of
+// the block (the row's parameters, V, BS), so every __syncthreads() is reached by all 1024 threads on every path.
+// Counter word 0 of the draw is `c0`, the key `seed`, the draw index `n`.
 template <typename T>
-__global__ __launch_bounds__(kThreads) void sample_kernel(const T* __restrict__ logits, int64_t row_stride, int V, int BS, float temp,
-                                                          int top_k, float top_p, float min_p, const int64_t* __restrict__ state,
-                                                          int64_t* __restrict__ out, int64_t out_stride) {
-    __shared__ Shared sh;
+__device__ __forceinline__ void sample_row(Shared& sh, const T* __restrict__ logits, int V, int BS, float temp, int top_k, float top_p,
+                                           float min_p, uint32_t c0, uint64_t seed, int64_t n, int64_t* __restrict__ out) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const Row<T> row{logits + (int64_t)blockIdx.x * row_stride, temp, temp != 1.0f};
+    const Row<T> row{logits, temp, temp != 1.0f};
     const int nbk = (V + BS - 1) / BS, bpw = (nbk + kWaves - 1) / kWaves;
     const int bk0 = min(nbk, wave * bpw), bk1 = min(nbk, (wave + 1) * bpw);
     const int e0 = min(V, bk0 * BS), e1 = min(V, bk1 * BS);
@@ -220,9 +223,7 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const T* __restrict__ 
         if (w < wave) incl += sh.wsum[w];
         S += sh.wsum[w];
     }
-    const int64_t n = state[1];
-    const uint64_t seed = (uint64_t)state[0];
-    const uint32_t u24 = philox_x0(blockIdx.x, 0, (uint32_t)n, (uint32_t)((uint64_t)n >> 32), (uint32_t)seed, (uint32_t)(seed >> 32)) >> 8;
+    const uint32_t u24 = philox_x0(c0, 0, (uint32_t)n, (uint32_t)((uint64_t)n >> 32), (uint32_t)seed, (uint32_t)(seed >> 32)) >> 8;
     // floor(S * u24 / 2^24), exactly (S < 2^61)
     const uint64_t target = (S >> 24) * u24 + (((S & 0xFFFFFFu) * u24) >> 24);
     if (S > 0 && tid < nbk && incl - v <= target && target < incl) {
@@ -242,7 +243,66 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const T* __restrict__ 
         }
     }
     __syncthreads();
-    if (tid == 0) out[(int64_t)blockIdx.x * out_stride] = (int64_t)sh.token;
+    if (tid == 0) *out = (int64_t)sh.token;
+}
+
+// A greedy row: the lowest index that maximises float(logit) (-0 and +0 tie), the tie rule of kivi_token_logprob's rank.  The key
+// image orders -inf below every finite value, so a -inf logit wins only when the whole row is -inf; NaN / +inf rows get some index.
+template <typename T>
+__device__ __forceinline__ void greedy_row(Shared& sh, const T* __restrict__ logits, int V, int64_t* __restrict__ out) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const Row<T> row{logits, 1.0f, false};
+    uint64_t best = 0;                                // (key << 32) | ~index: the maximum is the largest key at the lowest index
+    for (int e = tid; e < V; e += kThreads) best = max(best, ((uint64_t)key_of(row.s(e)) << 32) | (uint32_t)~(uint32_t)e);
+#pragma unroll
+    for (int d = 1; d < KIVI_WAVE; d <<= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)best, d), hi = __shfl_xor((uint32_t)(best >> 32), d);
+        best = max(best, ((uint64_t)hi << 32) | lo);
+    }
+    if (lane == 0) sh.wsum[wave] = best;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 0; w < kWaves; ++w) best = max(best, sh.wsum[w]);
+        const uint32_t j = ~(uint32_t)best;
+        *out = j < (uint32_t)V ? (int64_t)j : 0;      // (V >= 1: thread 0 always has an entry, so j < V; the guard is for form)
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void sample_kernel(const T* __restrict__ logits, int64_t row_stride, int V, int BS, float temp,
+                                                          int top_k, float top_p, float min_p, const int64_t* __restrict__ state,
+                                                          int64_t* __restrict__ out, int64_t out_stride) {
+    __shared__ Shared sh;
+    sample_row<T>(sh, logits + (int64_t)blockIdx.x * row_stride, V, BS, temp, top_k, top_p, min_p, blockIdx.x, (uint64_t)state[0],
+                  state[1], out + (int64_t)blockIdx.x * out_stride);
+}
+
+// Per-row parameters and RNG streams (kivi_sample_rows): block b reads rows[b] and draw_index[b], takes the greedy or the sampling
+// path -- a block-uniform choice -- and then stores draw_index[b] + 1 itself (one lane, a plain vector store): no second launch.
+// Every thread has read n before the first barrier of either path, and the store comes after the last one.
+// Records outside the contract degrade as the header says: they never loop and never index outside the row.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void sample_rows_kernel(const T* __restrict__ logits, int64_t row_stride, int V, int BS,
+                                                               const kivi_sample_row* __restrict__ rows, int64_t* draw_index,
+                                                               int64_t* __restrict__ out, int64_t out_stride) {
+    __shared__ Shared sh;
+    const int b = blockIdx.x;
+    const kivi_sample_row r = rows[b];
+    const int64_t n = draw_index[b];
+    const T* row = logits + (int64_t)b * row_stride;
+    int64_t* dst = out + (int64_t)b * out_stride;
+    const bool greedy = (r.flags & KIVI_SAMPLE_ROW_GREEDY) || !(r.temperature > 0.0f) || !__builtin_isfinite(r.temperature);
+    if (greedy) {
+        greedy_row<T>(sh, row, V, dst);
+    } else {
+        const int top_k = max(r.top_k, 0);
+        float top_p = r.top_p <= 1.0f ? r.top_p : 1.0f;                 // NaN and > 1: off
+        if (!(top_p > 0.0f)) top_p = 1.17549435e-38f;                   // <= 0: the smallest (0, 1] value, the top class alone
+        float min_p = r.min_p >= 0.0f ? r.min_p : 0.0f;                 // NaN and < 0: off
+        if (min_p >= 1.0f) min_p = 0.99999994f;                         // the largest value below 1: the maximum stays
+        sample_row<T>(sh, row, V, BS, r.temperature, top_k, top_p, min_p, r.stream, (uint64_t)r.seed, n, dst);
+    }
+    if (threadIdx.x == 0) draw_index[b] = n + 1;
 }
 
 __global__ void advance_kernel(int64_t* state) { state[1] += 1; }
@@ -279,4 +339,29 @@ extern "C" int kivi_sample(const void* logits, int logits_bits, int64_t row_stri
     if (rc) return rc;
     KIVI_LAUNCH(advance_kernel, dim3(1), dim3(1), s, rng_state);
     return kivi_launch_status("kivi_sample (advance)");
+}
+
+extern "C" int kivi_sample_rows(const void* logits, int logits_bits, int64_t row_stride, int B, int V, const kivi_sample_row* rows,
+                                int64_t* draw_index, int64_t* out_tokens, int64_t out_stride, kivi_stream_t stream) {
+    KIVI_REQUIRE(logits_bits == 16 || logits_bits == 32, KIVI_EINVAL, "kivi_sample_rows: logits_bits=%d (16: fp16, 32: fp32)",
+                 logits_bits);
+    KIVI_REQUIRE(B >= 1 && B <= KIVI_SAMPLE_MAX_B, KIVI_EINVAL, "kivi_sample_rows: B=%d (1 <= B <= %d)", B, KIVI_SAMPLE_MAX_B);
+    KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "kivi_sample_rows: V=%d (1 <= V <= %d)", V, KIVI_SAMPLE_MAX_V);
+    KIVI_REQUIRE(row_stride >= V || B == 1, KIVI_EINVAL, "kivi_sample_rows: row_stride=%lld below V=%d", (long long)row_stride, V);
+    KIVI_REQUIRE(out_stride >= 1 || B == 1, KIVI_EINVAL, "kivi_sample_rows: out_stride=%lld", (long long)out_stride);
+    KIVI_REQUIRE(logits && rows && draw_index && out_tokens, KIVI_EINVAL, "kivi_sample_rows: null pointer");
+    const int esz = logits_bits / 8;
+    KIVI_REQUIRE((uintptr_t)logits % esz == 0 && (uintptr_t)rows % 8 == 0 && (uintptr_t)draw_index % 8 == 0 &&
+                     (uintptr_t)out_tokens % 8 == 0,
+                 KIVI_EALIGN, "kivi_sample_rows: misaligned logits (%d-byte elements), rows, draw_index or out_tokens (8 bytes)", esz);
+    int BS = KIVI_WAVE;                              // as kivi_sample
+    while ((int64_t)BS * 1024 < V) BS <<= 1;
+    const hipStream_t s = (hipStream_t)stream;
+    if (logits_bits == 16)
+        KIVI_LAUNCH(sample_rows_kernel<f16>, dim3(B), dim3(kThreads), s, (const f16*)logits, row_stride, V, BS, rows, draw_index,
+                    out_tokens, out_stride);
+    else
+        KIVI_LAUNCH(sample_rows_kernel<float>, dim3(B), dim3(kThreads), s, (const float*)logits, row_stride, V, BS, rows, draw_index,
+                    out_tokens, out_stride);
+    return kivi_launch_status("kivi_sample_rows");
 }

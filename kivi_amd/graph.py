@@ -17,7 +17,9 @@ per row and the replayed one sliced the row are gone: tests/test_graph_gpu.py co
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import gc
 import weakref
 from typing import Callable, List, Optional
 
@@ -97,6 +99,22 @@ class MfStepDriver:
             self.host.k_res_len = 0
 
 
+@contextlib.contextmanager
+def no_gc_in_capture():
+    """Around a stream capture.  A pass of Python's cycle collector may run at any allocation, also while a capture is open, and
+    may then destroy what an earlier request left behind in a reference cycle -- a captured graph with its memory pool, device
+    buffers.  The runtime refuses such calls during a capture (the capture mode is global) and the process aborts.  torch's graph
+    context does not collect before a capture any more, so: collect now, and keep the collector off until the capture has ended."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
+
+
 class GraphedDecode:
     """`step_fn()` enqueues one whole decode step (dense parts + `driver.enqueue(i, ...)` per layer) on the current stream, reading
     and writing static buffers; `step()` runs it -- the first step of a geometry class eagerly (which also settles everything the
@@ -122,7 +140,7 @@ class GraphedDecode:
             else:
                 if self.graph is None:
                     g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=self.stream):   # (records, does not execute)
+                    with no_gc_in_capture(), torch.cuda.graph(g, stream=self.stream):   # (records, does not execute)
                         self.step_fn()
                     self.graph = g
                     self.captures += 1

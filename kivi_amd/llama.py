@@ -378,7 +378,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
                  pad_token_id: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False, do_sample: bool = False,
                  temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
-                 seed: Optional[int] = None, return_logprobs: bool = False):
+                 seed: Optional[int] = None, return_logprobs: bool = False, sampling=None):
         """Greedy decoding (the recipe of the reference's mem_spd_test.py / example.py), or sampling with `do_sample=True`.
         With `past_key_values` (the caches of an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one
         pass (kivi_attention_extend) and decoding continues from there; the caches are advanced in place.  `attention_mask`:
@@ -396,6 +396,14 @@ class LlamaForCausalLM_KIVI(nn.Module):
         drawn by the fused HIP sampler (kivi_amd/sampling.py).  `seed`: the Philox seed of the call (None: one
         drawn from torch's default CPU generator); token i of the call is draw i of every row.  Not with beams.
 
+        `sampling=`: per-request sampling (kivi_amd/sampling.py) -- one SamplingParams for every request, a
+        list of B of them (greedy requests, do_sample=False, among sampled ones), or a ready RowSampler, which is used as it is
+        (its draw indices are not reset) and has to hold B * num_return_sequences rows.  Not together with `do_sample=True`, a
+        non-default `temperature` / `top_k` / `top_p` / `min_p` / `seed`, or beams.  With it `num_return_sequences=n` draws n samples
+        of every prompt after ONE prompt pass: the caches are forked to B * n rows (with `past_key_values`: a clone of them, the
+        caller's stay unchanged), output row b * n + j uses request b's parameters and seed with Philox stream j, and the n first
+        tokens of a request are drawn from the same row of prompt logits.  Returns (B * n, T + generated).
+
         `return_logprobs=True` (greedy and sampling): returns (sequences, logprobs (B, generated) fp32), the log-probability of each
         emitted token under the model's RAW distribution -- temperature 1 and unfiltered, what HF derives from `output_logits`, not
         from the processed `output_scores` -- one kivi_token_logprob call per step on the logits the step has anyway; the pads of a
@@ -407,18 +415,30 @@ class LlamaForCausalLM_KIVI(nn.Module):
         if return_logprobs and num_beams > 1:
             raise ValueError("return_logprobs is for greedy decoding and sampling; beam search (num_beams > 1) returns its "
                              "sequences_scores with return_scores=True")
-        sampler = self._sampler(input_ids.device, do_sample, num_beams, temperature, top_k, top_p, min_p, seed)
+        B, fan = input_ids.shape[0], 1
+        if sampling is not None:
+            sampler = self._row_sampler(input_ids.device, sampling, B, num_return_sequences, num_beams, do_sample, temperature,
+                                        top_k, top_p, min_p, seed)
+            fan = num_return_sequences
+        else:
+            sampler = self._sampler(input_ids.device, do_sample, num_beams, temperature, top_k, top_p, min_p, seed)
         if eos_token_id is not None and pad_token_id is None:
             raise ValueError("eos_token_id needs a pad_token_id for the rows that have finished")
-        if num_beams < 1 or num_return_sequences < 1 or num_return_sequences > num_beams:
+        if sampling is None and (num_beams < 1 or num_return_sequences < 1 or num_return_sequences > num_beams):
             raise ValueError(f"num_return_sequences ({num_return_sequences}) must lie in [1, num_beams ({num_beams})]")
         if num_beams > 1:
             return self._generate_beams(input_ids, max_new_tokens, past_key_values, attention_mask, eos_token_id, pad_token_id,
                                         num_beams, length_penalty, early_stopping, num_return_sequences, return_scores)
         if return_scores:
             raise ValueError("return_scores: sequences_scores exist for beam search (num_beams > 1) only")
-        B = input_ids.shape[0]
-        pb, logits, pasts = self._prompt_pass(input_ids, past_key_values, attention_mask, max_new_tokens)
+        if fan > 1 and past_key_values is not None:        # the fork below runs on a copy: the caller's caches stay as they are
+            past_key_values = [p.layer.clone().as_tuple() for p in past_key_values]
+        pb, logits, pasts = self._prompt_pass(input_ids, past_key_values, attention_mask, max_new_tokens, fan)
+        if fan > 1:             # n samples per prompt: one prompt pass, then every request's row repeated n times (as the beams are)
+            rows = torch.arange(B, device=input_ids.device).repeat_interleave(fan)
+            pasts = [p.layer.index_select(rows).as_tuple() for p in pasts]
+            logits, input_ids = logits.index_select(0, rows), input_ids.index_select(0, rows)
+            B *= fan
         out, lps = [input_ids], []
         if return_logprobs:
             from .scoring import token_logprobs
@@ -450,6 +470,31 @@ class LlamaForCausalLM_KIVI(nn.Module):
             raise ValueError(f"beam sampling (do_sample=True with num_beams={num_beams}) is not supported")
         from .sampling import Sampler
         return Sampler(temperature, top_k, top_p, min_p, seed, device)
+
+    @staticmethod
+    def _row_sampler(device, sampling, B, n, num_beams, do_sample, temperature, top_k, top_p, min_p, seed):
+        """The RowSampler of a `sampling=` call over B requests with n samples each (row b * n + j: request b, stream j); every
+        argument is checked before anything runs on a device."""
+        from .sampling import RowSampler, SamplingParams
+        if do_sample or temperature != 1.0 or top_k != 50 or top_p != 1.0 or min_p is not None or seed is not None:
+            raise ValueError("sampling= carries the parameters of every row: it cannot be combined with do_sample=True or with "
+                             "temperature / top_k / top_p / min_p / seed arguments")
+        if num_beams != 1:
+            raise ValueError(f"sampling= with beam search (num_beams={num_beams}) is not supported")
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"num_return_sequences ({n!r}) must be a positive integer")
+        if isinstance(sampling, RowSampler):
+            if sampling.B != B * n:
+                raise ValueError(f"the RowSampler holds {sampling.B} rows; {B} requests x {n} samples need {B * n}")
+            return sampling
+        if isinstance(sampling, SamplingParams):
+            sampling = [sampling] * B
+        elif not isinstance(sampling, (list, tuple)) or not all(isinstance(p, SamplingParams) for p in sampling):
+            raise ValueError("sampling has to be a SamplingParams, a list of B of them, or a RowSampler")
+        if len(sampling) != B:
+            raise ValueError(f"{len(sampling)} SamplingParams for a batch of {B} requests")
+        bound = [RowSampler._bind(p) for p in sampling]          # one seed per request, shared by its n streams
+        return RowSampler([p for p in bound for _ in range(n)], device, [j for _ in bound for j in range(n)])
 
     def _generate_beams(self, input_ids, max_new_tokens, past_key_values, attention_mask, eos_token_id, pad_token_id, nb,
                         length_penalty, early_stopping, num_return_sequences, return_scores):
@@ -485,6 +530,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
     # buffer, pitch >= the cache capacity, that the attention of every step reads (its new column is 0: new tokens are real).
     # Sampling (sampler=): the last layer's post() draws into g.tok with the sampler instead of argmax; the captured call holds the
     # sampler's parameters and state buffer, so the graphs are keyed by Sampler.key() and captured again for another sampler.
+    # A RowSampler keeps its parameters in device memory: its key() is the row count and two buffer pointers, so new parameter
+    # values in the same RowSampler (set_row, or another request mix) replay the graphs that exist.
     def _build_graphs(self, B: int, device, whole: bool = False, padded: bool = False, sampler=None):
         cfg = self.config
         nh, nkv = cfg.num_attention_heads, cfg.num_key_value_heads
@@ -542,14 +589,16 @@ class LlamaForCausalLM_KIVI(nn.Module):
                 post(i)
         torch.cuda.current_stream(device).wait_stream(side)
         g.warmup = False
+        from .graph import no_gc_in_capture
         pool = None
-        for i in range(len(self.model.layers)):
-            for fn, dst in ((pre, g.pre), (post, g.post)):
-                cg = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(cg, pool=pool):
-                    fn(i)
-                pool = pool or cg.pool()
-                dst.append(cg)
+        with no_gc_in_capture():
+            for i in range(len(self.model.layers)):
+                for fn, dst in ((pre, g.pre), (post, g.post)):
+                    cg = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(cg, pool=pool):
+                        fn(i)
+                    pool = pool or cg.pool()
+                    dst.append(cg)
         g.tok.zero_()
         return g
 
@@ -590,13 +639,23 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     @torch.no_grad()
     def decode_graphed(self, tok: torch.LongTensor, past_key_values: List, position: int, steps: int,
-                       attention_mask: Optional[torch.Tensor] = None, sampler=None) -> torch.LongTensor:
+                       attention_mask: Optional[torch.Tensor] = None, sampler=None, sampling=None) -> torch.LongTensor:
         """`steps` decode steps from token `tok` (B, 1) at position `position` with the dense part replayed from
         hipGraphs; the caches in `past_key_values` are advanced in place.  Returns the (B, steps) tokens fed to the model
         (tok first); the token following them is left in the graph's token buffer (`self._graphs.tok`).
         `attention_mask`: HF's 2D mask (B, kv_len + 1) over the cached tokens and `tok` (1 = real token); with a pad in it
         every row takes its own position from the mask (`position` is not used) and the pads are masked in every step.
-        `sampler`: a kivi_amd.sampling.Sampler that draws each next token (one draw per step, inside the graph); None: greedy."""
+        `sampler`: a kivi_amd.sampling.Sampler that draws each next token (one draw per step, inside the graph); None: greedy.
+        `sampling`: a kivi_amd.sampling.RowSampler of B rows in its place (per-row parameters; not together with `sampler`).  The
+        graphs depend on its buffers only: set_row() between steps or calls replays what was captured."""
+        if sampling is not None:
+            if sampler is not None:
+                raise ValueError("pass either sampler= or sampling=, not both")
+            if not callable(sampling) or not hasattr(sampling, "key"):
+                raise ValueError("decode_graphed(sampling=) takes a RowSampler")
+            if getattr(sampling, "B", tok.shape[0]) != tok.shape[0]:
+                raise ValueError(f"the RowSampler holds {sampling.B} rows, the step has {tok.shape[0]}")
+            sampler = sampling
         from .attention import kivi_attention_decode
         from .cache_mf import KiviLayerCacheMF
         caches = [p.layer for p in past_key_values]
@@ -658,14 +717,19 @@ class LlamaForCausalLM_KIVI(nn.Module):
     def generate_graphed(self, input_ids: torch.LongTensor, max_new_tokens: int,
                          attention_mask: Optional[torch.Tensor] = None, num_beams: int = 1, do_sample: bool = False,
                          temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
-                         seed: Optional[int] = None) -> torch.LongTensor:
+                         seed: Optional[int] = None, sampling=None) -> torch.LongTensor:
         """generate() with the dense part of every decode step replayed from hipGraphs (see _build_graphs).
         `attention_mask`: HF's 2D (B, T) mask of left-padded prompts (1 = real token).  Greedy, or sampling with `do_sample=True`
         and the parameters of generate() (the draw inside the graph; the same tokens as generate() with the same seed).  Beams
-        are refused (a graphed beam step is open; use generate())."""
-        if num_beams != 1 and not do_sample:
-            raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
-        sampler = self._sampler(input_ids.device, do_sample, num_beams, temperature, top_k, top_p, min_p, seed)
+        are refused (a graphed beam step is open; use generate()).  `sampling=`: per-request parameters as in
+        generate() (a SamplingParams, a list of B, or a RowSampler of B rows); the graphs are keyed by the RowSampler's buffers."""
+        if sampling is not None:
+            sampler = self._row_sampler(input_ids.device, sampling, input_ids.shape[0], 1, num_beams, do_sample, temperature,
+                                        top_k, top_p, min_p, seed)
+        else:
+            if num_beams != 1 and not do_sample:
+                raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
+            sampler = self._sampler(input_ids.device, do_sample, num_beams, temperature, top_k, top_p, min_p, seed)
         logits, pasts = self.forward(input_ids, padding_mask=attention_mask)
         if attention_mask is not None:
             attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, :1])], dim=1)

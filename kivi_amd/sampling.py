@@ -6,13 +6,19 @@ s >= the k-th largest s; top-p keeps a token when the mass strictly above it (ov
 p >= min_p * p_max; the draw takes the first token in vocabulary order whose inclusive running sum of kept probabilities exceeds
 u * (kept mass), u = (x0 >> 8) * 2^-24 from Philox4x32-10 at key (seed low, seed high), counter (row, 0, n low, n high).
 
+`SamplingParams` / `RowSampler`: the same draw with the parameters, seed and RNG stream of every row in
+device memory (kivi_sample_rows), so requests with different parameters -- greedy ones among them -- share one launch, a row's
+tokens do not depend on its place in the batch, and a captured decode step depends on two buffers, not on parameter values.
+
 `philox4x32` and `reference_sample` (fp64, explicit u) restate the contract on the CPU for tests and tools; the product path
 never calls them.
 """
 from __future__ import annotations
 
+import ctypes
+import dataclasses
 import math
-from typing import Optional
+from typing import Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -36,6 +42,11 @@ def check_params(temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, 
         raise ValueError(f"min_p has to be None or a float in [0, 1), got {min_p!r}")
 
 
+def check_seed(seed) -> None:
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64):
+        raise ValueError(f"seed has to be None or an integer in [0, 2^64), got {seed!r}")
+
+
 def draw_seed() -> int:
     """A 63-bit seed from torch's default CPU generator (so torch.manual_seed makes a seed=None run reproducible)."""
     return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
@@ -49,8 +60,7 @@ class Sampler:
     def __init__(self, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
                  seed: Optional[int] = None, device="cuda"):
         check_params(temperature, top_k, top_p, min_p)
-        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64):
-            raise ValueError(f"seed has to be None or an integer in [0, 2^64), got {seed!r}")
+        check_seed(seed)
         self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
         self.min_p = float(min_p or 0.0)
         self.state = torch.zeros(2, dtype=torch.int64, device=device)
@@ -89,6 +99,149 @@ class Sampler:
         return out
 
 
+# ------------------------------------------------------------------ per-row parameters (kivi_sample_rows)
+GREEDY = 1          # include/kivi_hip.h: KIVI_SAMPLE_ROW_GREEDY
+
+
+class SampleRow(ctypes.Structure):
+    """include/kivi_hip.h: kivi_sample_row (32 bytes)."""
+    _fields_ = [("temperature", ctypes.c_float), ("top_k", ctypes.c_int32), ("top_p", ctypes.c_float), ("min_p", ctypes.c_float),
+                ("seed", ctypes.c_int64), ("stream", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+@dataclasses.dataclass(frozen=True)
+class SamplingParams:
+    """The sampling parameters of one request, with HF's names, ranges and defaults.  `do_sample=False`: a greedy row (the lowest
+    index of the largest logit; the other fields are still validated, and ignored).  `seed=None`: one is drawn with draw_seed()
+    when the parameters are bound to a row of a RowSampler."""
+    do_sample: bool = True
+    temperature: float = 1.0
+    top_k: int = 50
+    top_p: float = 1.0
+    min_p: Optional[float] = None
+    seed: Optional[int] = None
+
+    def __post_init__(self):
+        if not isinstance(self.do_sample, bool):
+            raise ValueError(f"do_sample has to be a bool, got {self.do_sample!r}")
+        check_params(self.temperature, self.top_k, self.top_p, self.min_p)
+        check_seed(self.seed)
+
+
+def _check_stream(stream) -> int:
+    if isinstance(stream, bool) or not isinstance(stream, int) or not 0 <= stream < 2 ** 32:
+        raise ValueError(f"stream has to be an integer in [0, 2^32), got {stream!r}")
+    return stream
+
+
+def _record(p: SamplingParams, stream: int) -> torch.Tensor:
+    """The 32 bytes of one bound row (p.seed is set) as 4 int64 on the CPU."""
+    seed = p.seed - 2 ** 64 if p.seed >= 2 ** 63 else p.seed
+    rec = SampleRow(float(p.temperature), int(p.top_k), float(p.top_p), float(p.min_p or 0.0), seed, stream,
+                    0 if p.do_sample else GREEDY)
+    return torch.tensor(np.frombuffer(bytes(rec), dtype=np.int64))
+
+
+class RowSampler:
+    """The fused sampler with one record {temperature, top_k, top_p, min_p, seed, stream, greedy} and one draw index per row, both
+    in device memory and owned by the sampler (`records` (B, 4) int64, `draw_index` (B,) int64).  `params`: one SamplingParams for
+    every row, or a sequence of B of them; `streams`: the Philox stream of every row (default 0, so a request with seed s draws in
+    ANY row what Sampler(seed=s) draws for a batch of one); rows that share a seed need different streams to draw differently.
+    `B`: the number of rows when `params` is a single SamplingParams (default 1).
+    Every argument is checked before a device is touched."""
+
+    def __init__(self, params: Union[SamplingParams, Sequence[SamplingParams]], device="cuda",
+                 streams: Optional[Sequence[int]] = None, B: Optional[int] = None):
+        if isinstance(params, SamplingParams):
+            if B is None:
+                B = 1 if streams is None else len(streams)
+            if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+                raise ValueError(f"B has to be a positive integer, got {B!r}")
+            params = [params] * B
+        else:
+            params = list(params)
+            if not params or not all(isinstance(p, SamplingParams) for p in params):
+                raise ValueError("params has to be a SamplingParams or a non-empty sequence of them")
+            if B is not None and B != len(params):
+                raise ValueError(f"{len(params)} SamplingParams for B={B} rows")
+        streams = [0] * len(params) if streams is None else [_check_stream(s) for s in streams]
+        if len(streams) != len(params):
+            raise ValueError(f"{len(streams)} streams for {len(params)} rows")
+        self.params = [self._bind(p) for p in params]
+        self.streams = streams
+        self.records = torch.stack([_record(p, s) for p, s in zip(self.params, streams)]).to(device)
+        self.draw_index = torch.zeros(len(params), dtype=torch.int64, device=device)
+
+    @staticmethod
+    def _bind(p: SamplingParams) -> SamplingParams:
+        return p if p.seed is not None else dataclasses.replace(p, seed=draw_seed())
+
+    @property
+    def B(self) -> int:
+        return len(self.params)
+
+    def key(self):
+        """What a captured call depends on: the number of rows and the two buffers -- not the parameter values, which a replay reads
+        from the records.  (The leading string keeps it apart from every Sampler.key().)"""
+        return ("rows", self.B, self.records.data_ptr(), self.draw_index.data_ptr())
+
+    def set_row(self, b: int, params: SamplingParams, stream: int = 0) -> None:
+        """A new request takes over row b: its record is rewritten and its draw index zeroed, by asynchronous copies on the current
+        stream (ordered after the calls already enqueued there); no other row is touched and nothing has to be captured again."""
+        if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < self.B:
+            raise ValueError(f"row {b!r} outside [0, {self.B})")
+        if not isinstance(params, SamplingParams):
+            raise ValueError("params has to be a SamplingParams")
+        stream = _check_stream(stream)
+        p = self._bind(params)
+        rec = _record(p, stream)
+        if self.records.is_cuda:
+            rec = rec.pin_memory()
+        self.records[b].copy_(rec, non_blocking=True)
+        self.draw_index[b: b + 1].zero_()
+        self.params[b], self.streams[b] = p, stream
+
+    def reset(self) -> None:
+        """All draw indices back to 0 (the records stay)."""
+        self.draw_index.zero_()
+
+    def select(self, idx, streams: Optional[Sequence[int]] = None) -> "RowSampler":
+        """A new RowSampler (its own buffers) whose row i is this one's row idx[i], seeds and draw indices included: the sampler side
+        of a cache fork by index_select.  `streams`: new streams for the rows (default: those of the source rows)."""
+        idx = [int(i) for i in (idx.tolist() if torch.is_tensor(idx) else idx)]
+        if not idx or not all(0 <= i < self.B for i in idx):
+            raise ValueError(f"idx has to be a non-empty sequence of rows in [0, {self.B})")
+        new = RowSampler([self.params[i] for i in idx], self.records.device,
+                         [self.streams[i] for i in idx] if streams is None else streams)
+        new.draw_index.copy_(self.draw_index.index_select(0, torch.tensor(idx, device=self.draw_index.device)))
+        return new
+
+    def __call__(self, logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """As Sampler.__call__: one token per row into (B, 1) int64 (`out` when given), in ONE kivi_sample_rows launch."""
+        _lib.require_gpu(logits, "logits")
+        if logits.dim() == 3:
+            if logits.shape[1] != 1:
+                raise ValueError(f"logits (B, 1, V) expected, got {tuple(logits.shape)}")
+            logits = logits[:, 0]
+        if logits.dim() != 2 or logits.dtype not in (torch.float16, torch.float32):
+            raise ValueError(f"logits must be (B, V) or (B, 1, V) fp16 / fp32, got {tuple(logits.shape)} {logits.dtype}")
+        B, V = logits.shape
+        if B != self.B or logits.device != self.records.device:
+            raise ValueError(f"this RowSampler holds {self.B} rows on {self.records.device}, got logits of {B} rows on {logits.device}")
+        if logits.stride(1) != 1:
+            logits = logits.contiguous()
+        if out is None:
+            out = torch.empty((B, 1), dtype=torch.int64, device=logits.device)
+        if out.dtype != torch.int64 or out.numel() != B or out.device != logits.device:
+            raise ValueError(f"out must hold B={B} int64 tokens on {logits.device}")
+        lib = _lib.load()
+        _lib.check(lib.kivi_sample_rows(_lib.ptr(logits), 16 if logits.dtype == torch.float16 else 32, logits.stride(0), B, V,
+                                        _lib.ptr(self.records), _lib.ptr(self.draw_index), _lib.ptr(out),
+                                        out.stride(0) if out.dim() else 1, _lib.stream_ptr(logits)),
+                   "kivi_sample_rows")
+        return out
+
+
 # ------------------------------------------------------------------ CPU restatement (tests, tools)
 def philox4x32(ctr, key, rounds: int = 10) -> np.ndarray:
     """Philox4x32-R over arrays: ctr (..., 4), key (..., 2) uint32 -> (..., 4) uint32 (Random123's philox4x32_R)."""
@@ -116,6 +269,18 @@ def philox_x0(seed: int, rows, n: int) -> np.ndarray:
 def draw_u(seed: int, rows, n: int) -> np.ndarray:
     """u = (x0 >> 8) * 2^-24 in [0, 1), float64."""
     return (philox_x0(seed, rows, n) >> 8).astype(np.float64) * 2.0 ** -24
+
+
+def draw_u_rows(seeds, streams, ns) -> np.ndarray:
+    """u of kivi_sample_rows per row: key seeds[i], counter (streams[i], 0, ns[i] low, ns[i] high); float64 in [0, 1).
+    draw_u_rows([seed] * B, range(B), [n] * B) is draw_u(seed, range(B), n)."""
+    seeds = np.array([int(s) % 2 ** 64 for s in seeds], dtype=np.uint64)
+    ns = np.array([int(n) % 2 ** 64 for n in ns], dtype=np.uint64)
+    streams = np.asarray(streams, dtype=np.uint64)
+    lo, sh = np.uint64(0xFFFFFFFF), np.uint64(32)
+    ctr = np.stack([streams, np.zeros_like(streams), ns & lo, ns >> sh], -1)
+    key = np.stack([seeds & lo, seeds >> sh], -1)
+    return (philox4x32(ctr, key)[..., 0] >> 8).astype(np.float64) * 2.0 ** -24
 
 
 def reference_kept(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
