@@ -129,7 +129,7 @@ def main():
         kv_alloc = sum(p.layer.allocated_bytes() for p in pasts)  # incl. page / window slack of the in-place cache
     print(json.dumps({
         "mode": "fp16 KV + SDPA" if args.baseline else f"KIVI {args.bits}-bit g={args.group} R={args.residual}" + (" + hipGraph" if args.graphs else ""),
-        "hipgraph_eager_captures_replays": getattr(model, "_last_graph_stats", None),
+        "hipgraph_eager_captures_replays": getattr(model.graphs, "stats", None),
         "model": f"llama-shaped random weights: L={args.layers} h={args.hidden} nh={args.heads}/{args.kv_heads} ffn={args.intermediate}",
         "batch": args.batch, "prompt": args.prompt, "gen": args.gen,
         "repeats": args.repeats, "generate_ms": round(1e3 * t_generate, 1),     # what the reference prints as "used time"

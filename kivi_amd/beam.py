@@ -3,9 +3,9 @@
 _beam_search_has_unfinished_sequences), with the same length_penalty / early_stopping semantics, the same beams_to_keep, the same
 padding of finished sequences and the same sequences_scores.  Greedy search only (no sampling, no logits processors).
 
-The model is reached through `step(tokens (B * nb, 1), beam_idx (B * nb,) or None) -> fp32 logits (B * nb, vocab)`: reorder the
-caches by `beam_idx` (flat indices, beam b * nb + j of request b), then run one decode step.  The prompt pass is the caller's:
-its logits come in as `first_logits`.  transformers is not imported.
+The model is reached through `step(tokens (B * nb, 1), beam_idx (B * nb,)) -> logits (B * nb, vocab) or (B * nb, 1, vocab)`:
+reorder the caches by `beam_idx` (flat indices, beam b * nb + j of request b), then run one decode step.  The prompt pass is the
+caller's: its logits come in as `first_logits`, in either shape.  transformers is not imported.
 """
 from __future__ import annotations
 

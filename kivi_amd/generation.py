@@ -1,0 +1,173 @@
+"""What a generate call is made of, apart from the model: left padding, the sampler of the call, the prompt pass with its fork to
+n rows per request, the eager decode step, and the ONE loop of greedy decoding and sampling over two callables, `step(tok) -> logits`
+and `pick(logits) -> tok`.  Beam search (kivi_amd/beam.py) is fed the same EagerStepper; the graphed step: kivi_amd/graph.py."""
+from __future__ import annotations
+
+from typing import Callable, Optional
+
+import torch
+
+_MIN16 = torch.finfo(torch.float16).min
+
+
+def left_pad(seqs, pad_token_id: int = 0, device=None):
+    """A list of token id sequences -> (ids (B, T), mask (B, T)) left-padded to the longest one (HF's tokenizer with
+    padding_side="left"): mask is 1 on real tokens, 0 on the `pad_token_id` fillers."""
+    seqs = [torch.as_tensor(s, dtype=torch.long).flatten() for s in seqs]
+    T = max(len(s) for s in seqs)
+    ids = torch.full((len(seqs), T), pad_token_id, dtype=torch.long)
+    mask = torch.zeros((len(seqs), T), dtype=torch.long)
+    for i, s in enumerate(seqs):
+        if len(s):
+            ids[i, T - len(s):] = s
+            mask[i, T - len(s):] = 1
+    return ids.to(device), mask.to(device)
+
+
+def padding_position_ids(mask: torch.Tensor, q_len: int) -> torch.LongTensor:
+    """HF's prepare_inputs_for_generation: positions cumsum(mask) - 1, pads at 1; the last `q_len` columns."""
+    m = mask.long()
+    pos = m.cumsum(-1) - 1
+    return pos.masked_fill_(m == 0, 1)[:, -q_len:]
+
+
+def padding_key_row(mask: torch.Tensor, length: Optional[int] = None) -> torch.Tensor:
+    """(B, 1, 1, length) additive fp16 key row of a 2D padding mask: 0 on real tokens, finfo(fp16).min on pads (columns past
+    the mask: 0).  Decode steps read views of it; an extend reads it expanded over the chunk."""
+    B, L = mask.shape
+    row = torch.zeros((B, 1, 1, length or L), dtype=torch.float16, device=mask.device)
+    row[..., :L].masked_fill_((mask == 0)[:, None, None, :], _MIN16)
+    return row
+
+
+def padding_prompt_mask(mask: torch.Tensor) -> torch.Tensor:
+    """HF's 4D causal + padding additive mask of a prompt pass (_prepare_4d_causal_attention_mask): (B, 1, T, T) fp16."""
+    B, T = mask.shape
+    causal = torch.full((T, T), _MIN16, dtype=torch.float16, device=mask.device).triu(1)
+    return causal[None, None].repeat(B, 1, 1, 1).masked_fill_((mask == 0)[:, None, None, :], _MIN16)
+
+
+class _PaddedBatch:
+    """What a left-padded batch adds to the passes of one call, derived once from HF's 2D mask (B, past_len + T): `mask` and
+    `position_ids` of the pass over the T new tokens (the prompt's 4D causal + padding mask; with a history, the key row expanded
+    over the chunk), then per decode step a view of the key row one column longer (new tokens are real) and the advancing
+    position.  `beams`: the decode steps run on every row repeated that often (the prompt pass does not)."""
+
+    def __init__(self, mask2d: torch.Tensor, past_len: int, T: int, max_new_tokens: int = 0, beams: int = 1):
+        n = past_len + T
+        row = padding_key_row(mask2d, n + max_new_tokens)
+        self.mask = padding_prompt_mask(mask2d) if past_len == 0 else row[..., :n].expand(-1, -1, T, -1)
+        self.position_ids = padding_position_ids(mask2d, T)
+        if max_new_tokens:
+            pos = mask2d.long().sum(-1, keepdim=True)                  # (B, 1): position of the next token
+            if beams > 1:
+                row, pos = row.repeat_interleave(beams, dim=0), pos.repeat_interleave(beams, dim=0)
+            self._row, self._pos, self._len = row, pos, n
+
+    def step(self):
+        """(additive key row (B, 1, 1, kv length incl. the new token), position ids (B, 1)) of the next decode step."""
+        self._len += 1
+        pos = self._pos
+        self._pos = pos + 1
+        return self._row[..., : self._len], pos
+
+
+def resolve_sampler(device, B: int, num_return_sequences: int, num_beams: int, do_sample: bool, temperature, top_k, top_p, min_p,
+                    seed, sampling):
+    """The sampler of a generate / generate_graphed call -> (pick, fan): `pick(logits) -> tokens` is a Sampler (`do_sample=True`), a
+    RowSampler (`sampling=`: B requests with `fan` = num_return_sequences samples each, row b * fan + j is request b with Philox
+    stream j) or None (greedy); without `sampling=` fan is 1.  Every argument is checked before anything runs on a device."""
+    from .sampling import RowSampler, Sampler, SamplingParams
+    if sampling is None:
+        if not do_sample:
+            return None, 1
+        if num_beams != 1:
+            raise ValueError(f"beam sampling (do_sample=True with num_beams={num_beams}) is not supported")
+        return Sampler(temperature, top_k, top_p, min_p, seed, device), 1
+    n = num_return_sequences
+    if do_sample or temperature != 1.0 or top_k != 50 or top_p != 1.0 or min_p is not None or seed is not None:
+        raise ValueError("sampling= carries the parameters of every row: it cannot be combined with do_sample=True or with "
+                         "temperature / top_k / top_p / min_p / seed arguments")
+    if num_beams != 1:
+        raise ValueError(f"sampling= with beam search (num_beams={num_beams}) is not supported")
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"num_return_sequences ({n!r}) must be a positive integer")
+    if isinstance(sampling, RowSampler):
+        if sampling.B != B * n:
+            raise ValueError(f"the RowSampler holds {sampling.B} rows; {B} requests x {n} samples need {B * n}")
+        return sampling, n
+    if isinstance(sampling, SamplingParams):
+        sampling = [sampling] * B
+    elif not isinstance(sampling, (list, tuple)) or not all(isinstance(p, SamplingParams) for p in sampling):
+        raise ValueError("sampling has to be a SamplingParams, a list of B of them, or a RowSampler")
+    if len(sampling) != B:
+        raise ValueError(f"{len(sampling)} SamplingParams for a batch of {B} requests")
+    bound = [RowSampler._bind(p) for p in sampling]          # one seed per request, shared by its n streams
+    return RowSampler([p for p in bound for _ in range(n)], device, [j for _ in bound for j in range(n)]), n
+
+
+class EagerStepper:
+    """The eager passes of one generate call: the pass over `input_ids` here, then `step(tok) -> logits`, over caches (`pasts`,
+    advanced in place) and the _PaddedBatch of a mask with a pad in it, which it owns.  `n` > 1 is the ONE fork of beams and of n
+    samples per prompt: after the prompt pass on the B requests every request's row is repeated n times -- on a copy when the
+    caches are the caller's (`past_key_values`), which stay byte for byte what they were.  `logits` (B * n, 1, vocab): the prompt
+    pass's; `input_ids` (B * n, T).  Beams: `step(tok, beam_idx)`, the step callback of beam_search, calls `reorder_` first."""
+
+    def __init__(self, model, input_ids, past_key_values, attention_mask, max_new_tokens: int, n: int = 1):
+        B, T = input_ids.shape
+        past_len = model._past_len(past_key_values)
+        if n > 1 and past_key_values is not None:
+            past_key_values = [p.layer.clone().as_tuple() for p in past_key_values]
+        self.model, self.padded, self.group, self.fork = model, None, n, past_len + T
+        if attention_mask is not None and model._padded(attention_mask, B, past_len + T, past_len):
+            self.padded = _PaddedBatch(attention_mask, past_len, T, max_new_tokens, n)
+            logits, pasts = model._forward(input_ids, past_key_values, self.padded.mask, self.padded.position_ids, True, True)
+        else:
+            logits, pasts = model.forward(input_ids, past_key_values)
+        if n > 1:
+            rows = torch.arange(B, device=input_ids.device).repeat_interleave(n)
+            pasts = [p.layer.index_select(rows).as_tuple() for p in pasts]
+            logits, input_ids = logits.index_select(0, rows), input_ids.index_select(0, rows)
+        self.pasts, self.logits, self.input_ids = pasts, logits, input_ids
+
+    def step(self, tok: torch.LongTensor, beam_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if beam_idx is not None:
+            self.reorder_(beam_idx)
+        mask, position_ids = (None, None) if self.padded is None else self.padded.step()
+        logits, self.pasts = self.model._forward(tok, self.pasts, mask, position_ids, True, True)
+        return logits
+
+    def reorder_(self, beam_idx: torch.Tensor) -> None:
+        """Row b of every cache <- row beam_idx[b], in place and from the fork on (rows of a request agree on every byte before it)."""
+        for p in self.pasts:
+            p.layer.reorder_(beam_idx, group=self.group, from_token=self.fork, check=False)
+
+
+def decode_loop(first_logits: torch.Tensor, step: Callable, pick: Callable, max_new_tokens: int,
+                eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, want_logprobs: bool = False):
+    """Greedy decoding and sampling: every token is `pick` of the logits (B, 1, vocab) before it -- `first_logits`, then `step(tok)`.
+    -> (tokens (B, generated) int64, their fp32 log-probabilities under the raw distribution or None).  A row that has produced
+    `eos_token_id` emits `pad_token_id` from then on and scores target -100; the loop stops when every row has finished (the one
+    synchronisation of a step, only with `eos_token_id`).  Otherwise the last token is still stepped and picked over: caches end
+    max_new_tokens tokens on, a sampler max_new_tokens + 1 draws on."""
+    if want_logprobs:
+        from .scoring import token_logprobs
+    logits, out, lps = first_logits, [], []
+    tok = pick(logits)
+    B = tok.shape[0]
+    live = None if eos_token_id is None else torch.ones((B, 1), dtype=torch.bool, device=tok.device)
+    for _ in range(max_new_tokens):
+        if live is not None:
+            tok = torch.where(live, tok, torch.full_like(tok, pad_token_id))
+        if want_logprobs:                              # a finished row scores nothing: its target is the ignore_index
+            lps.append(token_logprobs(logits, tok if live is None else torch.where(live, tok, torch.full_like(tok, -100))))
+        if live is not None:
+            live = live & (tok != eos_token_id)
+        out.append(tok)
+        if live is not None and not bool(live.any()):
+            break
+        logits = step(tok)
+        tok = pick(logits)
+    if want_logprobs:
+        lps = torch.cat(lps, dim=1) if lps else logits.new_empty((B, 0), dtype=torch.float32)
+    return torch.cat(out, dim=1) if out else tok.new_empty((B, 0)), lps if want_logprobs else None

@@ -14,6 +14,9 @@ Replayed and eager steps agree bit for bit: both follow the launch plan of the s
 sized for the class's longest row, ceil(Tq / 512) * 512 + residual_length keys; since round 6 an eager step is planned for that
 bound too, and the one-launch caps are whole super-blocks + a full residual, so the bands of round 5 where an eager step ran a block
 per row and the replayed one sliced the row are gone: tests/test_graph_gpu.py covers Tq just under 8192 / 9216).
+
+`DecodeGraphs` is what a model keeps for its graphed decode: the static buffers, the dense bodies, and either this whole-step graph
+or, for caches in the hook-state layout, per-layer graphs of the dense parts around an eager attention call.
 """
 from __future__ import annotations
 
@@ -26,7 +29,9 @@ from typing import Callable, List, Optional
 import torch
 
 from . import _lib
-from .cache_mf import KiviLayerCacheMF
+from .attention import _rotate_half, kivi_attention_decode, rope_cos_sin
+from .cache_mf import SB, KiviLayerCacheMF
+from .generation import _MIN16
 
 
 class MfStepDriver:
@@ -66,15 +71,16 @@ class MfStepDriver:
         c = self.caches[0]
         return int(self.lib.kivi_mf_step_key(ctypes.byref(self.host), c.B, c.nh, c.nh_kv, c.cfg.residual_length, c._flags()))
 
-    def prepare(self) -> bool:
-        """Room for one more token in every cache, lengths uploaded.  Returns True when captured launches are stale (a cache was
-        reallocated or the geometry class changed since the last call)."""
+    def prepare(self, also=()) -> bool:
+        """Room for one more token in every cache, lengths uploaded.  Returns True when captured launches are stale: a cache was
+        reallocated, the geometry class changed, or an address in `also` (what else the caller's captured step reads: its mask
+        buffer) moved since the last call."""
         stale = False
         for c in self.caches:
             c.ensure_room(1)
         # everything a captured launch holds a raw pointer to: the stores, the fp16 residual / window, the per-stream scratch
         ptrs = tuple((c.kt.data_ptr(), c.vt.data_ptr(), c.k_res.data_ptr(), c.v_res.data_ptr()) +
-                     tuple(t.data_ptr() for t in c._desc(c.nh, c.kt.device)[4]) for c in self.caches) + (self.key(),)
+                     tuple(t.data_ptr() for t in c._desc(c.nh, c.kt.device)[4]) for c in self.caches) + (self.key(),) + tuple(also)
         if ptrs != self._ptrs:
             stale, self._ptrs = True, ptrs
         _lib.check(self.lib.kivi_mf_step_upload(ctypes.byref(self.host), self.dev.data_ptr(), _lib.stream_ptr(self.dev)), "kivi_mf_step_upload")
@@ -127,11 +133,11 @@ class GraphedDecode:
         self.stream = torch.cuda.Stream(driver.dev.device)      # ONE stream for every capture: the library keeps its scratch per stream
         self.captures = self.replays = self.eager = 0
 
-    def step(self) -> None:
+    def step(self, also=()) -> None:
         cur = torch.cuda.current_stream(self.driver.dev.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
-            if self.driver.prepare():                            # room, lengths of THIS step uploaded; stale: reallocation / new class
+            if self.driver.prepare(also):                        # room, lengths of THIS step uploaded; stale: reallocation / new class
                 self.graph, self.warm = None, False
             if self.graph is None and not self.warm:
                 self.step_fn()
@@ -148,3 +154,141 @@ class GraphedDecode:
                 self.replays += 1
             self.driver.finish()
         cur.wait_stream(self.stream)
+
+
+class DecodeGraphs:
+    """Everything a graphed decode of `model` at batch size B needs; LlamaForCausalLM_KIVI.decode_graphed steps it.
+
+    In eager mode the host needs longer to enqueue the ~30 small launches of a layer's dense part than the GPU to run them.  Here
+    they read and write static buffers (`tok`, `cos` / `sin`, `x`, `qkv`, `attn`) through two bodies: `pre(i)`, block input (layer 0:
+    the embedding of `tok`) to the rotated q / k / v, and `post(i)`, attention output to block output (last layer: on to the head and
+    the next token in `tok`).  Same kernels, same results as forward().  Per-layer form: pre(i) and post(i) are captured once, here,
+    and the KIVI step between them stays one eager call per layer (its lengths change every step).  Whole-step form (`whole`: every
+    cache in the matrix-pipe layout): the attention launches read their lengths from device memory (MfStepDriver), so GraphedDecode
+    captures all layers as ONE graph.  Driver and graph are made for the caches of begin() (held weakly: nothing here keeps a finished
+    request's KV cache alive) and serve every call over them; MfStepDriver.prepare() alone finds a capture stale.
+    `padded`: cos / sin hold one position per row (`pos`), and `mask` is a static additive (B, 1, 1, pitch) fp16 buffer, pitch >= the
+    cache capacity, that the attention of every step reads (its new column is 0: new tokens are real).
+    `sampler`: the last post() draws into `tok` with it instead of argmax.  The captured call holds what the sampler's key() names:
+    a Sampler's parameters and state buffer, a RowSampler's row count and two buffers -- other parameter values in the same
+    RowSampler (set_row, another request mix) replay the graphs that exist, another key builds them again.
+    `stats`: (eager steps, captures, replays) of the whole-step form, cumulative over the calls on one set of caches."""
+
+    def __init__(self, model, B: int, device, whole: bool = False, padded: bool = False, sampler=None):
+        cfg, layers = model.config, model.model.layers
+        nh, nkv = cfg.num_attention_heads, cfg.num_key_value_heads
+        D, dt = layers[0].self_attn.head_dim, model.lm_head.weight.dtype
+
+        def zeros(*shape, dtype=dt):
+            return torch.zeros(shape, dtype=dtype, device=device)
+
+        self.model, self.B, self.whole, self.padded, self.sampler = model, B, whole, padded, sampler
+        self.sampler_key = None if sampler is None else sampler.key()
+        self.tok = zeros(B, 1, dtype=torch.long)
+        self.cos, self.sin = (zeros(B if padded else 1, 1, 1, D) for _ in range(2))
+        self.x = [zeros(B, 1, cfg.hidden_size) for _ in range(len(layers) + 1)]
+        self.attn = zeros(B, nh, 1, D)
+        self.qkv = [(zeros(B, nh, 1, D), zeros(B, nkv, 1, D), zeros(B, nkv, 1, D)) for _ in layers]
+        self.mask = self.pos = self.driver = self.graphed = self.stats = None
+        if not whole:
+            self._capture_layers()
+
+    def matches(self, B: int, whole: bool, padded: bool, sampler_key) -> bool:
+        return (self.B, self.whole, self.padded, self.sampler_key) == (B, whole, padded, sampler_key)
+
+    def pre(self, i: int) -> None:
+        layer = self.model.model.layers[i]
+        a, (q, k, v) = layer.self_attn, self.qkv[i]
+        if i == 0:
+            self.x[0].copy_(self.model.model.embed_tokens(self.tok))
+        h = layer.input_layernorm(self.x[i])
+        for dst, proj in ((q, a.q_proj), (k, a.k_proj), (v, a.v_proj)):
+            t = proj(h).view(self.B, 1, -1, a.head_dim).transpose(1, 2)
+            dst.copy_(t if dst is v else t * self.cos + _rotate_half(t) * self.sin)
+
+    def post(self, i: int, draw: bool = True) -> None:
+        """`draw=False`: the next token by argmax whatever the sampler (a warm-up must not consume a draw)."""
+        layer = self.model.model.layers[i]
+        x = self.x[i] + layer.self_attn.o_proj(self.attn.transpose(1, 2).reshape(self.B, 1, -1))
+        self.x[i + 1].copy_(x + layer.mlp(layer.post_attention_layernorm(x)))
+        if i == len(self.x) - 2:
+            logits = self.model.lm_head(self.model.model.norm(self.x[i + 1]))
+            if self.sampler is None or not draw:
+                self.tok.copy_(logits.argmax(-1))
+            else:
+                self.sampler(logits, out=self.tok)
+
+    def _capture_layers(self) -> None:
+        device, n = self.tok.device, len(self.qkv)
+        side = torch.cuda.Stream(device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):          # warm-up outside capture (library workspaces, autotuning)
+            for i in range(n):
+                self.pre(i)
+                self.post(i, draw=False)
+        torch.cuda.current_stream(device).wait_stream(side)
+        self.pre_graphs, self.post_graphs, pool = [], [], None
+        with no_gc_in_capture():
+            for i in range(n):
+                for fn, dst in ((self.pre, self.pre_graphs), (self.post, self.post_graphs)):
+                    cg = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(cg, pool=pool):
+                        fn(i)
+                    pool = pool or cg.pool()
+                    dst.append(cg)
+        self.tok.zero_()
+
+    def _whole_step(self) -> None:
+        for i in range(len(self.qkv)):
+            self.pre(i)
+            self.driver.enqueue(i, *self.qkv[i], self.attn, self.mask)
+            self.post(i)
+
+    def _grow_mask(self, caches) -> None:
+        """Room for a token in every cache, a mask buffer as wide as their capacity (whole: the stores', so that it moves with them)."""
+        for c in caches:
+            c.ensure_room(1)
+        need = caches[0].n_sb * SB if self.whole else ((caches[0].cap + 7) // 8) * 8
+        if self.mask is None or self.mask.shape[3] < need:
+            old, self.mask = self.mask, torch.zeros((self.B, 1, 1, need), dtype=torch.float16, device=self.tok.device)
+            if old is not None:
+                self.mask[..., : old.shape[3]].copy_(old)
+
+    def begin(self, tok: torch.Tensor, caches, attention_mask: Optional[torch.Tensor] = None) -> None:
+        """Decode steps from `tok` over `caches` follow; padded: HF's 2D mask (B, kv_len + 1) fills the mask buffer and positions."""
+        self.tok.copy_(tok)
+        self._caches = [weakref.ref(c) for c in caches]
+        if self.padded:
+            self._grow_mask(caches)
+            self.mask.zero_()
+            self.mask[..., : attention_mask.shape[1]].masked_fill_((attention_mask == 0)[:, None, None, :], _MIN16)
+            self.pos = attention_mask.long().sum(-1) - 1                 # (B,): position of `tok`
+        if self.whole:
+            if self.driver is not None and self.driver.serves(caches):   # the same caches again: replay what was captured instead of
+                self.driver.resync()                                     # paying an eager step and a capture of every layer again
+            else:
+                self.driver = MfStepDriver(caches)
+                self.graphed = GraphedDecode(self.driver, self._whole_step)
+
+    def step(self, position: int) -> None:
+        """One decode step from `tok` at `position` (padded: every row's own); the next token is left in `tok`."""
+        inv_freq = self.model.model.layers[0].self_attn.inv_freq
+        for dst, src in zip((self.cos, self.sin), rope_cos_sin(inv_freq, self.pos if self.padded else position)):
+            dst.copy_(src.view(-1, 1, 1, src.shape[-1]))
+        caches = [c() for c in self._caches]
+        if self.padded:
+            self.pos += 1
+            self._grow_mask(caches)
+        if self.whole:
+            self.graphed.step((self.mask.data_ptr(),) if self.padded else ())
+            self.stats = (self.graphed.eager, self.graphed.captures, self.graphed.replays)
+            return
+        mask = self.mask[..., : caches[0].kv_seq_len + 1] if self.padded else None
+        for i, (q, k, v) in enumerate(self.qkv):
+            self.pre_graphs[i].replay()
+            kivi_attention_decode(q, k, v, caches[i], attention_mask=mask, out=self.attn)
+            self.post_graphs[i].replay()
+
+    def end(self) -> None:
+        """The caches of begin() die with their request: so does what was captured over them (buffers and per-layer graphs stay)."""
+        self.driver = self.graphed = None

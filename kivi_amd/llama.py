@@ -2,11 +2,13 @@
 
 Counterpart of the reference's LlamaForCausalLM_KIVI / MistralForCausalLM_KIVI wrappers (models/llama_kivi.py:564-1000,
 models/mistral_kivi.py:673-1100) reduced to what decoding needs: token embedding, pre-norm decoder blocks
-(RMSNorm, LlamaAttention_KIVI, SwiGLU MLP), final norm, lm_head, generate (greedy, sampling, beam search).  Parameter names
-follow the Hugging Face checkpoints (model.embed_tokens, model.layers.N.self_attn.q_proj, ..., lm_head), so `load_state_dict` /
-`from_pretrained` take an unmodified Llama-2 / Llama-3 / Mistral checkpoint directory; everything outside the attention
-block is plain torch (rocBLAS / hipBLASLt GEMMs).  The reference patches k_bits / v_bits / group_size /
-residual_length onto the HF config (README.md:72-75); the same four fields are read here.
+(RMSNorm, LlamaAttention_KIVI, SwiGLU MLP), final norm, lm_head, and the public methods of generation, scoring and checkpoints.
+Parameter names follow the Hugging Face checkpoints (model.embed_tokens, model.layers.N.self_attn.q_proj, ..., lm_head), so
+`load_state_dict` / `from_pretrained` take an unmodified Llama-2 / Llama-3 / Mistral checkpoint directory; everything outside the
+attention block is plain torch (rocBLAS / hipBLASLt GEMMs).  The reference patches k_bits / v_bits / group_size / residual_length
+onto the HF config (README.md:72-75); the same four fields are read here.
+What a generate call is made of -- left padding, the sampler of the call, the prompt pass and its fork, the eager step, the decode
+loop -- is kivi_amd/generation.py; beam search is kivi_amd/beam.py, the graphed decode step kivi_amd/graph.py (DecodeGraphs).
 """
 from __future__ import annotations
 
@@ -20,7 +22,12 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .attention import LlamaAttention_KIVI, rope_cos_sin
+from .attention import KiviLayerCacheMF, LlamaAttention_KIVI
+from .beam import beam_search
+from .generation import (EagerStepper, _PaddedBatch, decode_loop, left_pad, padding_key_row, padding_position_ids,  # noqa: F401
+                         padding_prompt_mask, resolve_sampler)
+from .graph import DecodeGraphs
+from .sampling import RowSampler
 
 
 def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32, residual_length: int = 32,
@@ -83,71 +90,6 @@ class _Body(nn.Module):
         self.norm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
 
 
-_MIN16 = torch.finfo(torch.float16).min
-
-
-def left_pad(seqs, pad_token_id: int = 0, device=None):
-    """A list of token id sequences -> (ids (B, T), mask (B, T)) left-padded to the longest one (HF's tokenizer with
-    padding_side="left"): mask is 1 on real tokens, 0 on the `pad_token_id` fillers."""
-    seqs = [torch.as_tensor(s, dtype=torch.long).flatten() for s in seqs]
-    T = max(len(s) for s in seqs)
-    ids = torch.full((len(seqs), T), pad_token_id, dtype=torch.long)
-    mask = torch.zeros((len(seqs), T), dtype=torch.long)
-    for i, s in enumerate(seqs):
-        if len(s):
-            ids[i, T - len(s):] = s
-            mask[i, T - len(s):] = 1
-    return ids.to(device), mask.to(device)
-
-
-def padding_position_ids(mask: torch.Tensor, q_len: int) -> torch.LongTensor:
-    """HF's prepare_inputs_for_generation: positions cumsum(mask) - 1, pads at 1; the last `q_len` columns."""
-    m = mask.long()
-    pos = m.cumsum(-1) - 1
-    return pos.masked_fill_(m == 0, 1)[:, -q_len:]
-
-
-def padding_key_row(mask: torch.Tensor, length: Optional[int] = None) -> torch.Tensor:
-    """(B, 1, 1, length) additive fp16 key row of a 2D padding mask: 0 on real tokens, finfo(fp16).min on pads (columns past
-    the mask: 0).  Decode steps read views of it; an extend reads it expanded over the chunk."""
-    B, L = mask.shape
-    row = torch.zeros((B, 1, 1, length or L), dtype=torch.float16, device=mask.device)
-    row[..., :L].masked_fill_((mask == 0)[:, None, None, :], _MIN16)
-    return row
-
-
-def padding_prompt_mask(mask: torch.Tensor) -> torch.Tensor:
-    """HF's 4D causal + padding additive mask of a prompt pass (_prepare_4d_causal_attention_mask): (B, 1, T, T) fp16."""
-    B, T = mask.shape
-    causal = torch.full((T, T), _MIN16, dtype=torch.float16, device=mask.device).triu(1)
-    return causal[None, None].repeat(B, 1, 1, 1).masked_fill_((mask == 0)[:, None, None, :], _MIN16)
-
-
-class _PaddedBatch:
-    """What a left-padded batch adds to the passes of one call, derived once from HF's 2D mask (B, past_len + T): `mask` and
-    `position_ids` of the pass over the T new tokens (the prompt's 4D causal + padding mask; with a history, the key row expanded
-    over the chunk), then per decode step a view of the key row one column longer (new tokens are real) and the advancing
-    position.  `beams`: the decode steps run on every row repeated that often (the prompt pass does not)."""
-
-    def __init__(self, mask2d: torch.Tensor, past_len: int, T: int, max_new_tokens: int = 0, beams: int = 1):
-        n = past_len + T
-        row = padding_key_row(mask2d, n + max_new_tokens)
-        self.mask = padding_prompt_mask(mask2d) if past_len == 0 else row[..., :n].expand(-1, -1, T, -1)
-        self.position_ids = padding_position_ids(mask2d, T)
-        if max_new_tokens:
-            pos = mask2d.long().sum(-1, keepdim=True)                  # (B, 1): position of the next token
-            if beams > 1:
-                row, pos = row.repeat_interleave(beams, dim=0), pos.repeat_interleave(beams, dim=0)
-            self._row, self._pos, self._len = row, pos, n
-
-    def step(self):
-        """(additive key row (B, 1, 1, kv length incl. the new token), position ids (B, 1)) of the next decode step."""
-        self._len += 1
-        pos = self._pos
-        self._pos = pos + 1
-        return self._row[..., : self._len], pos
-
-
 class LlamaForCausalLM_KIVI(nn.Module):
     """`past_key_values` is a list with one entry per layer: None before the prompt pass, afterwards the 9-tuple of
     models/llama_kivi.py:454-455 (here the lazy KiviCacheTuple over the in-place cache).
@@ -161,6 +103,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
         self.config = config
         self.model = _Body(config, attention_cls)
         self.lm_head = nn.Linear(config.hidden_size, config.vocab_size, bias=False)
+        self.graphs = None          # kivi_amd.graph.DecodeGraphs of the last graphed decode (prepare_graphs / release_graphs)
         if getattr(config, "tie_word_embeddings", False):
             self.lm_head.weight = self.model.embed_tokens.weight
 
@@ -215,21 +158,6 @@ class LlamaForCausalLM_KIVI(nn.Module):
             raise ValueError(f"{type(self.model.layers[0].self_attn).__name__}: the prompt pass of this attention class ignores "
                              f"masks (llama_kivi.py:420-423), so padded prompts cannot be run; use the eager class")
         return True
-
-    def _prompt_pass(self, input_ids, past_key_values, attention_mask, max_new_tokens: int, beams: int = 1):
-        """The pass over `input_ids` of a generate call -> (the _PaddedBatch of a mask with a pad in it, else None; logits; pasts)."""
-        B, T = input_ids.shape
-        past_len = self._past_len(past_key_values)
-        if attention_mask is not None and self._padded(attention_mask, B, past_len + T, past_len):
-            pb = _PaddedBatch(attention_mask, past_len, T, max_new_tokens, beams)
-            return (pb,) + self._forward(input_ids, past_key_values, pb.mask, pb.position_ids, True, True)
-        return (None,) + self.forward(input_ids, past_key_values)
-
-    def _decode_pass(self, tok, pasts, pb):
-        """One decode step of a generate call -> (logits, pasts)."""
-        if pb is None:
-            return self.forward(tok, pasts)
-        return self._forward(tok, pasts, *pb.step(), True, True)
 
     @staticmethod
     def _reorder_cache(past_key_values, beam_idx: torch.Tensor):
@@ -415,234 +343,41 @@ class LlamaForCausalLM_KIVI(nn.Module):
         if return_logprobs and num_beams > 1:
             raise ValueError("return_logprobs is for greedy decoding and sampling; beam search (num_beams > 1) returns its "
                              "sequences_scores with return_scores=True")
-        B, fan = input_ids.shape[0], 1
-        if sampling is not None:
-            sampler = self._row_sampler(input_ids.device, sampling, B, num_return_sequences, num_beams, do_sample, temperature,
-                                        top_k, top_p, min_p, seed)
-            fan = num_return_sequences
-        else:
-            sampler = self._sampler(input_ids.device, do_sample, num_beams, temperature, top_k, top_p, min_p, seed)
+        pick, fan = resolve_sampler(input_ids.device, input_ids.shape[0], num_return_sequences, num_beams, do_sample, temperature,
+                                    top_k, top_p, min_p, seed, sampling)
         if eos_token_id is not None and pad_token_id is None:
             raise ValueError("eos_token_id needs a pad_token_id for the rows that have finished")
         if sampling is None and (num_beams < 1 or num_return_sequences < 1 or num_return_sequences > num_beams):
             raise ValueError(f"num_return_sequences ({num_return_sequences}) must lie in [1, num_beams ({num_beams})]")
-        if num_beams > 1:
-            return self._generate_beams(input_ids, max_new_tokens, past_key_values, attention_mask, eos_token_id, pad_token_id,
-                                        num_beams, length_penalty, early_stopping, num_return_sequences, return_scores)
-        if return_scores:
+        if return_scores and num_beams == 1:
             raise ValueError("return_scores: sequences_scores exist for beam search (num_beams > 1) only")
-        if fan > 1 and past_key_values is not None:        # the fork below runs on a copy: the caller's caches stay as they are
-            past_key_values = [p.layer.clone().as_tuple() for p in past_key_values]
-        pb, logits, pasts = self._prompt_pass(input_ids, past_key_values, attention_mask, max_new_tokens, fan)
-        if fan > 1:             # n samples per prompt: one prompt pass, then every request's row repeated n times (as the beams are)
-            rows = torch.arange(B, device=input_ids.device).repeat_interleave(fan)
-            pasts = [p.layer.index_select(rows).as_tuple() for p in pasts]
-            logits, input_ids = logits.index_select(0, rows), input_ids.index_select(0, rows)
-            B *= fan
-        out, lps = [input_ids], []
-        if return_logprobs:
-            from .scoring import token_logprobs
-        pick = (lambda lg: lg.argmax(-1)) if sampler is None else sampler
-        tok = pick(logits)
-        live = None if eos_token_id is None else torch.ones((B, 1), dtype=torch.bool, device=tok.device)
-        for _ in range(max_new_tokens):
-            if live is not None:
-                tok = torch.where(live, tok, torch.full_like(tok, pad_token_id))
-            if return_logprobs:                            # a finished row scores nothing: its target is the ignore_index
-                lps.append(token_logprobs(logits, tok if live is None else torch.where(live, tok, torch.full_like(tok, -100))))
-            if live is not None:
-                live = live & (tok != eos_token_id)
-            out.append(tok)
-            if live is not None and not bool(live.any()):
-                break
-            logits, pasts = self._decode_pass(tok, pasts, pb)
-            tok = pick(logits)
-        if return_logprobs:
-            return torch.cat(out, dim=1), torch.cat(lps or [logits.new_empty((B, 0), dtype=torch.float32)], dim=1)
-        return torch.cat(out, dim=1)
+        stepper = EagerStepper(self, input_ids, past_key_values, attention_mask, max_new_tokens, max(num_beams, fan))
+        if num_beams > 1:
+            seqs, scores = beam_search(stepper.step, input_ids, stepper.logits, num_beams, max_new_tokens, eos_token_id,
+                                       pad_token_id, length_penalty, early_stopping, num_return_sequences)
+            return (seqs, scores) if return_scores else seqs
+        new, logprobs = decode_loop(stepper.logits, stepper.step, pick or (lambda lg: lg.argmax(-1)), max_new_tokens, eos_token_id,
+                                    pad_token_id, return_logprobs)
+        seqs = torch.cat([stepper.input_ids, new], dim=1)
+        return (seqs, logprobs) if return_logprobs else seqs
 
-    @staticmethod
-    def _sampler(device, do_sample, num_beams, temperature, top_k, top_p, min_p, seed):
-        """The Sampler of a do_sample call (None when greedy); every argument is checked before anything runs on a device."""
-        if not do_sample:
-            return None
-        if num_beams != 1:
-            raise ValueError(f"beam sampling (do_sample=True with num_beams={num_beams}) is not supported")
-        from .sampling import Sampler
-        return Sampler(temperature, top_k, top_p, min_p, seed, device)
-
-    @staticmethod
-    def _row_sampler(device, sampling, B, n, num_beams, do_sample, temperature, top_k, top_p, min_p, seed):
-        """The RowSampler of a `sampling=` call over B requests with n samples each (row b * n + j: request b, stream j); every
-        argument is checked before anything runs on a device."""
-        from .sampling import RowSampler, SamplingParams
-        if do_sample or temperature != 1.0 or top_k != 50 or top_p != 1.0 or min_p is not None or seed is not None:
-            raise ValueError("sampling= carries the parameters of every row: it cannot be combined with do_sample=True or with "
-                             "temperature / top_k / top_p / min_p / seed arguments")
-        if num_beams != 1:
-            raise ValueError(f"sampling= with beam search (num_beams={num_beams}) is not supported")
-        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
-            raise ValueError(f"num_return_sequences ({n!r}) must be a positive integer")
-        if isinstance(sampling, RowSampler):
-            if sampling.B != B * n:
-                raise ValueError(f"the RowSampler holds {sampling.B} rows; {B} requests x {n} samples need {B * n}")
-            return sampling
-        if isinstance(sampling, SamplingParams):
-            sampling = [sampling] * B
-        elif not isinstance(sampling, (list, tuple)) or not all(isinstance(p, SamplingParams) for p in sampling):
-            raise ValueError("sampling has to be a SamplingParams, a list of B of them, or a RowSampler")
-        if len(sampling) != B:
-            raise ValueError(f"{len(sampling)} SamplingParams for a batch of {B} requests")
-        bound = [RowSampler._bind(p) for p in sampling]          # one seed per request, shared by its n streams
-        return RowSampler([p for p in bound for _ in range(n)], device, [j for _ in bound for j in range(n)])
-
-    def _generate_beams(self, input_ids, max_new_tokens, past_key_values, attention_mask, eos_token_id, pad_token_id, nb,
-                        length_penalty, early_stopping, num_return_sequences, return_scores):
-        from .beam import beam_search
-        B, T = input_ids.shape
-        past_len = self._past_len(past_key_values)
-        if past_key_values is not None:              # the caller's caches stay as they are
-            past_key_values = [p.layer.clone().as_tuple() for p in past_key_values]
-        pb, logits, pasts = self._prompt_pass(input_ids, past_key_values, attention_mask, max_new_tokens, nb)
-        # the fork: every request's rows repeated over its beams; rows of a group agree on every byte before `fork`
-        fork = past_len + T
-        caches = [p.layer.index_select(torch.arange(B, device=input_ids.device).repeat_interleave(nb)) for p in pasts]
-
-        def step(tok, beam_idx):
-            for c in caches:
-                c.reorder_(beam_idx, group=nb, from_token=fork, check=False)
-            logits, _ = self._decode_pass(tok, [c.as_tuple() for c in caches], pb)
-            return logits[:, -1].float()
-
-        seqs, scores = beam_search(step, input_ids, logits[:, -1].float(), nb, max_new_tokens, eos_token_id, pad_token_id,
-                                   length_penalty, early_stopping, num_return_sequences)
-        return (seqs, scores) if return_scores else seqs
-
-    # ------------------------------------------------------------------ hipGraph decode
-    # The dense part of a decode step is ~30 small launches per layer; in eager mode the host needs longer to enqueue
-    # them than the GPU to run them.  Everything with static shapes is captured once per batch size into hipGraphs
-    # (torch.cuda.CUDAGraph): per layer one graph from the block input to the rotated q / k / v, one from the attention
-    # output to the block output, plus embedding and head; the KIVI step between them stays one eager
-    # kivi_decode_layer call per layer (its lengths change every step).  Same kernels, same results as forward().
-    # Round 4: when every layer's cache is in the matrix-pipe layout the attention launches read their lengths from device
-    # memory (kivi_amd/graph.py), so the WHOLE step -- dense parts and attention of all layers -- is ONE graph (whole=True).
-    # Padded batches (padded=True): cos / sin hold one position per row, and `mask` is a static additive (B, 1, 1, pitch) fp16
-    # buffer, pitch >= the cache capacity, that the attention of every step reads (its new column is 0: new tokens are real).
-    # Sampling (sampler=): the last layer's post() draws into g.tok with the sampler instead of argmax; the captured call holds the
-    # sampler's parameters and state buffer, so the graphs are keyed by Sampler.key() and captured again for another sampler.
-    # A RowSampler keeps its parameters in device memory: its key() is the row count and two buffer pointers, so new parameter
-    # values in the same RowSampler (set_row, or another request mix) replay the graphs that exist (DESIGN.md section 15).
-    def _build_graphs(self, B: int, device, whole: bool = False, padded: bool = False, sampler=None):
-        cfg = self.config
-        nh, nkv = cfg.num_attention_heads, cfg.num_key_value_heads
-        D, H = self.model.layers[0].self_attn.head_dim, cfg.hidden_size
-        dt = self.lm_head.weight.dtype
-        rows = B if padded else 1
-        g = SimpleNamespace(B=B, tok=torch.zeros((B, 1), dtype=torch.long, device=device),
-                            cos=torch.zeros((rows, 1, 1, D), dtype=dt, device=device),
-                            sin=torch.zeros((rows, 1, 1, D), dtype=dt, device=device),
-                            x=[torch.zeros((B, 1, H), dtype=dt, device=device) for _ in range(len(self.model.layers) + 1)],
-                            attn=torch.zeros((B, nh, 1, D), dtype=dt, device=device), qkv=[], pre=[], post=[], whole=whole,
-                            padded=padded, mask=None, pos=None, sampler=sampler,
-                            sample_key=None if sampler is None else sampler.key(), warmup=False)
-
-        def rot(t):
-            return torch.cat((-t[..., D // 2:], t[..., : D // 2]), dim=-1)
-
-        def pre(i):
-            layer = self.model.layers[i]
-            a = layer.self_attn
-            if i == 0:
-                g.x[0].copy_(self.model.embed_tokens(g.tok))
-            h = layer.input_layernorm(g.x[i])
-            q = a.q_proj(h).view(B, 1, nh, D).transpose(1, 2)
-            k = a.k_proj(h).view(B, 1, nkv, D).transpose(1, 2)
-            v = a.v_proj(h).view(B, 1, nkv, D).transpose(1, 2)
-            g.qkv[i][0].copy_(q * g.cos + rot(q) * g.sin)
-            g.qkv[i][1].copy_(k * g.cos + rot(k) * g.sin)
-            g.qkv[i][2].copy_(v)
-
-        def post(i):
-            layer = self.model.layers[i]
-            x = g.x[i] + layer.self_attn.o_proj(g.attn.transpose(1, 2).reshape(B, 1, nh * D))
-            g.x[i + 1].copy_(x + layer.mlp(layer.post_attention_layernorm(x)))
-            if i == len(self.model.layers) - 1:
-                logits = self.lm_head(self.model.norm(g.x[i + 1]))
-                if g.sampler is None or g.warmup:       # (the warm-up must not consume a draw)
-                    g.tok.copy_(logits.argmax(-1))
-                else:
-                    g.sampler(logits, out=g.tok)
-
-        for _ in self.model.layers:
-            g.qkv.append((torch.zeros((B, nh, 1, D), dtype=dt, device=device),
-                          torch.zeros((B, nkv, 1, D), dtype=dt, device=device),
-                          torch.zeros((B, nkv, 1, D), dtype=dt, device=device)))
-        g.pre_fn, g.post_fn = pre, post
-        if whole:               # captured by kivi_amd.graph.GraphedDecode together with the attention launches
-            return g
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        g.warmup = True
-        with torch.cuda.stream(side):          # warm-up outside capture (library workspaces, autotuning)
-            for i in range(len(self.model.layers)):
-                pre(i)
-                post(i)
-        torch.cuda.current_stream(device).wait_stream(side)
-        g.warmup = False
-        from .graph import no_gc_in_capture
-        pool = None
-        with no_gc_in_capture():
-            for i in range(len(self.model.layers)):
-                for fn, dst in ((pre, g.pre), (post, g.post)):
-                    cg = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(cg, pool=pool):
-                        fn(i)
-                    pool = pool or cg.pool()
-                    dst.append(cg)
-        g.tok.zero_()
-        return g
-
+    # ------------------------------------------------------------------ hipGraph decode (kivi_amd/graph.py: DecodeGraphs)
     def prepare_graphs(self, batch: int, device, whole: bool = False, padded: bool = False, sampler=None) -> None:
         """Capture the decode graphs for this batch size now (otherwise on the first graphed step)."""
-        g = getattr(self, "_graphs", None)
         key = None if sampler is None else sampler.key()
-        if g is None or g.B != batch or g.whole != whole or g.padded != padded or g.sample_key != key:
-            self._graphs = self._build_graphs(batch, device, whole, padded, sampler)
+        if self.graphs is None or not self.graphs.matches(batch, whole, padded, key):
+            self.graphs = DecodeGraphs(self, batch, device, whole, padded, sampler)
 
-    @staticmethod
-    def _mask_room(g, caches, whole: bool) -> bool:
-        """Room for one more token in every cache and a mask buffer as wide as their capacity (the whole-step graph: the tokens
-        the stores can hold, so that the buffer moves only when the stores do).  True when the buffer was reallocated."""
-        from .cache_mf import SB
-        for c in caches:
-            c.ensure_room(1)
-        need = caches[0].n_sb * SB if whole else ((caches[0].cap + 7) // 8) * 8
-        if g.mask is not None and g.mask.shape[3] >= need:
-            return False
-        new = torch.zeros((g.B, 1, 1, need), dtype=torch.float16, device=g.tok.device)
-        if g.mask is not None:
-            new[..., : g.mask.shape[3]].copy_(g.mask)
-        g.mask = new
-        return True
-
-    def _graph_inputs(self, g, caches, whole: bool, padded: bool, position: int) -> bool:
-        """The inputs of one graphed step in their static buffers: cos / sin of the step's position (padded: of the per-row positions
-        g.pos, which then advance, and room in the mask buffer -- True when that was reallocated)."""
-        inv_freq = self.model.layers[0].self_attn.inv_freq
-        cos, sin = rope_cos_sin(inv_freq, g.pos if padded else position)
-        g.cos.copy_(cos.view(-1, 1, 1, cos.shape[-1]))
-        g.sin.copy_(sin.view(-1, 1, 1, sin.shape[-1]))
-        if not padded:
-            return False
-        g.pos += 1
-        return self._mask_room(g, caches, whole)
+    def release_graphs(self) -> None:
+        """Drop the static buffers and everything captured; the next graphed decode builds them again."""
+        self.graphs = None
 
     @torch.no_grad()
     def decode_graphed(self, tok: torch.LongTensor, past_key_values: List, position: int, steps: int,
                        attention_mask: Optional[torch.Tensor] = None, sampler=None, sampling=None) -> torch.LongTensor:
         """`steps` decode steps from token `tok` (B, 1) at position `position` with the dense part replayed from
         hipGraphs; the caches in `past_key_values` are advanced in place.  Returns the (B, steps) tokens fed to the model
-        (tok first); the token following them is left in the graph's token buffer (`self._graphs.tok`).
+        (tok first); the token following them is left in the graph's token buffer (`self.graphs.tok`).
         `attention_mask`: HF's 2D mask (B, kv_len + 1) over the cached tokens and `tok` (1 = real token); with a pad in it
         every row takes its own position from the mask (`position` is not used) and the pads are masked in every step.
         `sampler`: a kivi_amd.sampling.Sampler that draws each next token (one draw per step, inside the graph); None: greedy.
@@ -651,66 +386,21 @@ class LlamaForCausalLM_KIVI(nn.Module):
         if sampling is not None:
             if sampler is not None:
                 raise ValueError("pass either sampler= or sampling=, not both")
-            if not callable(sampling) or not hasattr(sampling, "key"):
+            if not isinstance(sampling, RowSampler):
                 raise ValueError("decode_graphed(sampling=) takes a RowSampler")
-            if getattr(sampling, "B", tok.shape[0]) != tok.shape[0]:
+            if sampling.B != tok.shape[0]:
                 raise ValueError(f"the RowSampler holds {sampling.B} rows, the step has {tok.shape[0]}")
             sampler = sampling
-        from .attention import kivi_attention_decode
-        from .cache_mf import KiviLayerCacheMF
         caches = [p.layer for p in past_key_values]
-        whole = all(isinstance(c, KiviLayerCacheMF) for c in caches)
+        whole = all(isinstance(c, KiviLayerCacheMF) for c in caches)      # the whole step as one graph, else per-layer graphs
         B, kv0 = tok.shape[0], caches[0].kv_seq_len
         padded = attention_mask is not None and self._padded(attention_mask, B, kv0 + 1, kv0)
         self.prepare_graphs(B, tok.device, whole, padded, sampler)
-        g = self._graphs
-        g.tok.copy_(tok)
-        if padded:
-            if self._mask_room(g, caches, whole):
-                self._graphed = None             # a graph captured over the old buffer is stale
-            g.mask.zero_()
-            g.mask[..., : kv0 + 1].masked_fill_((attention_mask == 0)[:, None, None, :], _MIN16)
-            g.pos = attention_mask.long().sum(-1) - 1                    # (B,): position of `tok`
+        self.graphs.begin(tok, caches, attention_mask)
         out = []
-        if whole:
-            from .graph import GraphedDecode, MfStepDriver
-            # the driver and its captured graph live on the model, for the caches (held weakly: MfStepDriver.serves) and the static
-            # buffers they were built for: a second decode_graphed call over the same caches replays the graph it already has instead
-            # of paying an eager step and a 32-layer capture again (only a new geometry class or a reallocated buffer re-captures:
-            # MfStepDriver.prepare).  Nothing here keeps a finished request's KV cache alive.
-            st = getattr(self, "_graphed", None)
-            if st is not None and st[0] is g and st[1].serves(caches):
-                drv, gd = st[1], st[2]
-                drv.resync()
-            else:
-                drv = MfStepDriver(caches)
-
-                def body():
-                    for i in range(len(self.model.layers)):
-                        g.pre_fn(i)
-                        drv.enqueue(i, *g.qkv[i], g.attn, g.mask)
-                        g.post_fn(i)
-
-                gd = GraphedDecode(drv, body)
-                self._graphed = (g, drv, gd)
-            for _ in range(steps):
-                out.append(g.tok.clone())
-                if self._graph_inputs(g, caches, whole, padded, position):     # the stores grew: so did the buffer, capture again
-                    gd.graph, gd.warm = None, False
-                gd.step()
-                position += 1
-            self._last_graph_stats = (gd.eager, gd.captures, gd.replays)
-            return torch.cat(out, dim=1)
-        for _ in range(steps):
-            out.append(g.tok.clone())
-            self._graph_inputs(g, caches, whole, padded, position)
-            mask = g.mask[..., : caches[0].kv_seq_len + 1] if padded else None
-            for i in range(len(self.model.layers)):
-                g.pre[i].replay()
-                q, k, v = g.qkv[i]
-                kivi_attention_decode(q, k, v, caches[i], attention_mask=mask, out=g.attn)
-                g.post[i].replay()
-            position += 1
+        for s in range(steps):
+            out.append(self.graphs.tok.clone())
+            self.graphs.step(position + s)
         return torch.cat(out, dim=1)
 
     @torch.no_grad()
@@ -718,24 +408,21 @@ class LlamaForCausalLM_KIVI(nn.Module):
                          attention_mask: Optional[torch.Tensor] = None, num_beams: int = 1, do_sample: bool = False,
                          temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
                          seed: Optional[int] = None, sampling=None) -> torch.LongTensor:
-        """generate() with the dense part of every decode step replayed from hipGraphs (see _build_graphs).
+        """generate() with the dense part of every decode step replayed from hipGraphs (kivi_amd.graph.DecodeGraphs).
         `attention_mask`: HF's 2D (B, T) mask of left-padded prompts (1 = real token).  Greedy, or sampling with `do_sample=True`
         and the parameters of generate() (the draw inside the graph; the same tokens as generate() with the same seed).  Beams
         are refused (a graphed beam step is open; use generate()).  `sampling=`: per-request parameters as in
         generate() (a SamplingParams, a list of B, or a RowSampler of B rows); the graphs are keyed by the RowSampler's buffers."""
-        if sampling is not None:
-            sampler = self._row_sampler(input_ids.device, sampling, input_ids.shape[0], 1, num_beams, do_sample, temperature,
-                                        top_k, top_p, min_p, seed)
-        else:
-            if num_beams != 1 and not do_sample:
-                raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
-            sampler = self._sampler(input_ids.device, do_sample, num_beams, temperature, top_k, top_p, min_p, seed)
+        if sampling is None and num_beams != 1 and not do_sample:
+            raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
+        pick, _ = resolve_sampler(input_ids.device, input_ids.shape[0], 1, num_beams, do_sample, temperature, top_k, top_p, min_p,
+                                  seed, sampling)
         logits, pasts = self.forward(input_ids, padding_mask=attention_mask)
         if attention_mask is not None:
             attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, :1])], dim=1)
-        tok = logits.argmax(-1) if sampler is None else sampler(logits)
-        new = self.decode_graphed(tok, pasts, input_ids.shape[1], max_new_tokens, attention_mask, sampler)
-        self._graphed = None        # the caches of this request die with it: so does the graph captured over them
+        tok = logits.argmax(-1) if pick is None else pick(logits)
+        new = self.decode_graphed(tok, pasts, input_ids.shape[1], max_new_tokens, attention_mask, pick)
+        self.graphs.end()           # the caches of this request die with it: so does the graph captured over them
         return torch.cat([input_ids, new], dim=1)
 
     @classmethod

@@ -52,6 +52,27 @@ def draw_seed() -> int:
     return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
 
 
+def _call_args(logits: torch.Tensor, out: Optional[torch.Tensor], rows: Optional["RowSampler"] = None):
+    """The checks of a sampler call -> (logits (B, V), last dimension contiguous; out).  `rows`: the RowSampler they have to fit."""
+    _lib.require_gpu(logits, "logits")
+    if logits.dim() == 3:
+        if logits.shape[1] != 1:
+            raise ValueError(f"logits (B, 1, V) expected, got {tuple(logits.shape)}")
+        logits = logits[:, 0]
+    if logits.dim() != 2 or logits.dtype not in (torch.float16, torch.float32):
+        raise ValueError(f"logits must be (B, V) or (B, 1, V) fp16 / fp32, got {tuple(logits.shape)} {logits.dtype}")
+    B, V = logits.shape
+    if rows is not None and (B != rows.B or logits.device != rows.records.device):
+        raise ValueError(f"this RowSampler holds {rows.B} rows on {rows.records.device}, got logits of {B} rows on {logits.device}")
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    if out is None:
+        out = torch.empty((B, 1), dtype=torch.int64, device=logits.device)
+    if out.dtype != torch.int64 or out.numel() != B or out.device != logits.device:
+        raise ValueError(f"out must hold B={B} int64 tokens on {logits.device}")
+    return logits, out
+
+
 class Sampler:
     """The fused sampler with its device RNG state.  `__call__(logits, out=None)`: logits (B, V) or (B, 1, V) fp16 / fp32 on the
     GPU (the last dimension contiguous in memory or not -- rows are read with their stride) -> (B, 1) int64 tokens, written into
@@ -77,20 +98,8 @@ class Sampler:
         return (self.temperature, self.top_k, self.top_p, self.min_p, self.state.data_ptr())
 
     def __call__(self, logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        _lib.require_gpu(logits, "logits")
-        if logits.dim() == 3:
-            if logits.shape[1] != 1:
-                raise ValueError(f"logits (B, 1, V) expected, got {tuple(logits.shape)}")
-            logits = logits[:, 0]
-        if logits.dim() != 2 or logits.dtype not in (torch.float16, torch.float32):
-            raise ValueError(f"logits must be (B, V) or (B, 1, V) fp16 / fp32, got {tuple(logits.shape)} {logits.dtype}")
+        logits, out = _call_args(logits, out)
         B, V = logits.shape
-        if logits.stride(1) != 1:
-            logits = logits.contiguous()
-        if out is None:
-            out = torch.empty((B, 1), dtype=torch.int64, device=logits.device)
-        if out.dtype != torch.int64 or out.numel() != B or out.device != logits.device:
-            raise ValueError(f"out must hold B={B} int64 tokens on {logits.device}")
         lib = _lib.load()
         _lib.check(lib.kivi_sample(_lib.ptr(logits), 16 if logits.dtype == torch.float16 else 32, logits.stride(0), B, V,
                                    self.temperature, self.top_k, self.top_p, self.min_p, _lib.ptr(self.state), _lib.ptr(out),
@@ -218,22 +227,8 @@ class RowSampler:
 
     def __call__(self, logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """As Sampler.__call__: one token per row into (B, 1) int64 (`out` when given), in ONE kivi_sample_rows launch."""
-        _lib.require_gpu(logits, "logits")
-        if logits.dim() == 3:
-            if logits.shape[1] != 1:
-                raise ValueError(f"logits (B, 1, V) expected, got {tuple(logits.shape)}")
-            logits = logits[:, 0]
-        if logits.dim() != 2 or logits.dtype not in (torch.float16, torch.float32):
-            raise ValueError(f"logits must be (B, V) or (B, 1, V) fp16 / fp32, got {tuple(logits.shape)} {logits.dtype}")
+        logits, out = _call_args(logits, out, self)
         B, V = logits.shape
-        if B != self.B or logits.device != self.records.device:
-            raise ValueError(f"this RowSampler holds {self.B} rows on {self.records.device}, got logits of {B} rows on {logits.device}")
-        if logits.stride(1) != 1:
-            logits = logits.contiguous()
-        if out is None:
-            out = torch.empty((B, 1), dtype=torch.int64, device=logits.device)
-        if out.dtype != torch.int64 or out.numel() != B or out.device != logits.device:
-            raise ValueError(f"out must hold B={B} int64 tokens on {logits.device}")
         lib = _lib.load()
         _lib.check(lib.kivi_sample_rows(_lib.ptr(logits), 16 if logits.dtype == torch.float16 else 32, logits.stride(0), B, V,
                                         _lib.ptr(self.records), _lib.ptr(self.draw_index), _lib.ptr(out),

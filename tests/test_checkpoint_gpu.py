@@ -270,10 +270,10 @@ def test_model_rollback_then_graphed_decode(layout, monkeypatch):
     for _ in range(2):                                     # the second pass replays the graph the first one captured
         pasts = model.restore_(pasts, ck)
         assert torch.equal(model.decode_graphed(tok, pasts, 45, 40), eager)
-        stats.append(getattr(model, "_last_graph_stats", None))
+        stats.append(model.graphs.stats)
     if layout == "mfma":                                   # (eager steps, captures, replays) of the whole-step graph, cumulative
         assert stats[1][1] == stats[0][1] and stats[1][2] == stats[0][2] + 40
-    model._graphed = None
+    model.release_graphs()
 
 
 def test_model_rollback_and_sampler_reset():

@@ -203,8 +203,23 @@ def test_padded_graphed_equals_eager(nkv, lengths, n, monkeypatch):
         graphed = model.generate_graphed(ids, n, attention_mask=mask)
         assert torch.equal(graphed, eager), layout
         if layout == "mfma":
-            eager_steps, captures, replays = model._last_graph_stats
+            eager_steps, captures, replays = model.graphs.stats
             assert replays > 0 and captures >= (2 if max(lengths) + n > 544 else 1)
+
+
+def test_mask_buffer_grows_between_calls_on_one_model(monkeypatch):
+    """The static mask buffer of the graphed step is as wide as the stores: prompts of one super-block, then of two (a wider buffer
+    at another address, in the graphs that exist), then of one again -- every call equals eager decoding, and on the matrix-pipe
+    layout every call captures its step and replays it."""
+    model = _model(1, 11)
+    small, big = _prompts(7, [20, 9]), _prompts(8, [530, 40])
+    for layout in _layouts(monkeypatch):
+        for ids, mask in (small, big, small):
+            graphed = model.generate_graphed(ids, 6, attention_mask=mask)
+            eager_steps, captures, replays = model.graphs.stats or (0, 0, 0)
+            assert torch.equal(graphed, model.generate(ids, 6, attention_mask=mask)), (layout, ids.shape)
+            if layout == "mfma":
+                assert captures >= 1 and replays >= 1, (layout, ids.shape)
 
 
 # ------------------------------------------------------------------ 4. no change without a pad; the unpadded row

@@ -216,7 +216,7 @@ def test_generate_graphed_sampling_equals_eager(layout, monkeypatch):
         g = model.generate_graphed(ids, n, do_sample=True, **kw)
         assert torch.equal(g, model.generate(ids, n, do_sample=True, **kw)), (layout, kw)
     if layout == "mfma":
-        assert model._last_graph_stats[1] >= 1 and model._last_graph_stats[2] >= n // 2      # captured, then replayed
+        assert model.graphs.stats[1] >= 1 and model.graphs.stats[2] >= n // 2      # captured, then replayed
     pids, mask = left_pad([list(range(3, 30)), list(range(60, 70))], pad_token_id=0, device="cuda")
     g = model.generate_graphed(pids, 36, attention_mask=mask, do_sample=True, seed=33, **KW)
     assert torch.equal(g, model.generate(pids, 36, attention_mask=mask, do_sample=True, seed=33, **KW)), layout

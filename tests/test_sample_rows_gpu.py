@@ -371,7 +371,7 @@ def test_generate_graphed_rows_equals_eager(layout, monkeypatch):
     g = model.generate_graphed(ids, n, sampling=req)
     assert torch.equal(g, model.generate(ids, n, sampling=req)), layout
     if layout == "mfma":
-        assert model._last_graph_stats[1] >= 1 and model._last_graph_stats[2] >= n // 2      # captured, then replayed
+        assert model.graphs.stats[1] >= 1 and model.graphs.stats[2] >= n // 2      # captured, then replayed
     pids, mask = left_pad([list(range(3, 30)), list(range(60, 70)), list(range(80, 99))], pad_token_id=0, device="cuda")
     g = model.generate_graphed(pids, 36, attention_mask=mask, sampling=req)
     assert torch.equal(g, model.generate(pids, 36, attention_mask=mask, sampling=req)), layout
@@ -393,8 +393,8 @@ def test_generate_graphed_rows_equals_eager(layout, monkeypatch):
         for call in range(2):
             if graphed:
                 new = model.decode_graphed(tok, past, short.shape[1] + call * steps, steps, sampling=rs)
-                tok = model._graphs.tok.clone()
-                stats.append(getattr(model, "_last_graph_stats", None))
+                tok = model.graphs.tok.clone()
+                stats.append(model.graphs.stats)
             else:
                 new = []
                 for _ in range(steps):
@@ -408,13 +408,12 @@ def test_generate_graphed_rows_equals_eager(layout, monkeypatch):
             tok = tok.clone()
         return torch.cat(out, 1), stats, rs
 
-    model._graphs = model._graphed = None
-    model._last_graph_stats = None
+    model.release_graphs()
     got, stats, rs = run(True)
-    graphs = model._graphs
+    graphs = model.graphs
     want, _, _ = run(False)
     assert torch.equal(got, want), layout
-    assert model._graphs is graphs and graphs.sample_key == rs.key()            # keyed by buffers: built once for both calls
+    assert model.graphs is graphs and graphs.sampler_key == rs.key()            # keyed by buffers: built once for both calls
     if layout == "mfma":
         (e1, c1, r1), (e2, c2, r2) = stats
         assert (e1, c1, r1) == (1, 1, steps - 1)     # first call: one eager step, one capture, the rest replayed

@@ -102,9 +102,9 @@ def step_rows(rounds, gen=512, prompt=2048, B=32):
             model.decode_graphed(tok, pasts, prompt, gen, sampler=smp)
             torch.cuda.synchronize()
             res[mode].append((time.time() - t0) * 1e3 / gen)
-            print(f"  round {r} {mode}: {res[mode][-1]:.3f} ms/step  graph stats {model._last_graph_stats}", flush=True)
+            print(f"  round {r} {mode}: {res[mode][-1]:.3f} ms/step  graph stats {model.graphs.stats}", flush=True)
             del pasts
-            model._graphed = None
+            model.release_graphs()
     g, s = statistics.median(res["greedy"]), statistics.median(res["sampled"])
     return [f"  greedy  {g:7.3f} ms/step (min {min(res['greedy']):.3f})",
             f"  sampled {s:7.3f} ms/step (min {min(res['sampled']):.3f})   sampled / greedy {s / g:.4f}"]
