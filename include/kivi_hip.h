@@ -28,6 +28,7 @@
  *                               2-bit with nh / nh_kv in {1, 4, 8} or 4-bit with nh / nh_kv in {1, 4}), with the packers of that
  *                               cache: kivi_kt_pack, kivi_vt_pack, kivi_vt_pack_at, kivi_kt_relayout, kivi_vt_relayout
  *               beam search:    kivi_cache_reorder (in-place row reorder of either cache layout, from a fork point on)
+ *               admission:      kivi_cache_admit (rows of one cache into chosen rows of another, living one: continuous batching)
  *               rollback:       kivi_cache_snapshot (the fp16 residual / window and range words of a cache into a flat buffer and
  *                               back: checkpoint and restore of either cache layout)
  *               sampling:       kivi_sample (temperature / top-k / top-p / min-p draw of one token per row, Philox RNG state on
@@ -555,6 +556,38 @@ int kivi_cache_reorder(const kivi_reorder_slab* slabs, int n_slabs, int B, int g
  */
 int kivi_cache_snapshot(const kivi_reorder_slab* slabs, int n_slabs, int B, void* buf, size_t buf_row_stride, int direction,
                         kivi_stream_t stream);
+/*
+ * kivi_cache_admit: row rows[i] of a DESTINATION cache <- row i of a SOURCE cache, i < n_rows, for every byte range the slabs name
+ * (continuous batching, DESIGN.md section 16: a new request's prompt, run as a prompt pass of its own at the living caches' length,
+ * takes over the row of a finished request; no other row, no buffer address and no length changes).  The two caches are different
+ * allocations and may differ in capacity (other strides) and in where their fp16 V window sits, so an admit slab names both sides:
+ * byte (i0, i1, i2, j), j < run, i_k < n[k], of the slab is
+ *   source       src_base + i       * src_row_stride + i0*src_stride[0] + i1*src_stride[1] + i2*src_stride[2] + j
+ *   destination  dst_base + rows[i] * dst_row_stride + i0*dst_stride[0] + i1*dst_stride[1] + i2*dst_stride[2] + j
+ * The level counts and the run are shared.  Slabs and their pieces must not overlap on the destination side, and the source must
+ * not overlap the destination.  Moves are 16 bytes wide when base, row stride, level strides and run of BOTH sides are multiples
+ * of 16, 4 bytes wide otherwise.  `rows`: n_rows int32 (rows_bytes 4) or int64 (8) indices in DEVICE memory, read on the device;
+ * they must be distinct (every destination byte is then written at most once); a value outside [0, B) leaves that source row
+ * unused -- nothing outside the destination's B rows is ever written (the rule of kivi_cache_reorder).  The source holds at least
+ * n_rows rows.  One launch: grid (chunks of a slab, n_rows), no LDS, no scratch, four independent loads per thread before its first
+ * store.  Slabs with a zero count or run move nothing; when nothing is left, nothing is enqueued and the call returns 0.
+ * KIVI_EINVAL (before anything is enqueued) for B outside [1, 65535], n_rows outside [1, B], rows_bytes not 4 or 8, a null or
+ * misaligned rows, n_slabs outside [0, KIVI_REORDER_MAX_SLABS] or null slabs with n_slabs > 0, a negative count, a null base on
+ * either side, a base / stride / run of either side that is not a multiple of 4 bytes, 2^31 units per row or more, a grid of 2^31
+ * chunks or more.
+ */
+typedef struct kivi_admit_slab {
+    void* dst_base;
+    int64_t dst_row_stride;
+    int64_t dst_stride[3];
+    const void* src_base;
+    int64_t src_row_stride;
+    int64_t src_stride[3];
+    int64_t n[3];
+    int64_t run;
+} kivi_admit_slab;
+int kivi_cache_admit(const kivi_admit_slab* slabs, int n_slabs, int n_rows, const void* rows, int rows_bytes, int B,
+                     kivi_stream_t stream);
 /*
  * kivi_sample: one token per row drawn from (B, V) logits the way transformers' do_sample path does:
  * s = float(logit) / temperature; keep s >= the top_k-th largest s (ties kept; top_k = 0 or >= V: off); renormalise over those and

@@ -130,6 +130,13 @@ class ReorderSlab(ctypes.Structure):
     _fields_ = [("base", _vp), ("row_stride", _i64), ("n", _i64 * 3), ("stride", _i64 * 3), ("run", _i64)]
 
 
+class AdmitSlab(ctypes.Structure):
+    """kivi_admit_slab (include/kivi_hip.h): a slab with base, row stride and level strides per side (destination, source); the level
+    counts and the run are shared."""
+    _fields_ = [("dst_base", _vp), ("dst_row_stride", _i64), ("dst_stride", _i64 * 3),
+                ("src_base", _vp), ("src_row_stride", _i64), ("src_stride", _i64 * 3), ("n", _i64 * 3), ("run", _i64)]
+
+
 # name -> (restype, argtypes); must list every symbol include/kivi_hip.h declares
 SIGNATURES = {
     "kivi_abi_version": (_i32, []),
@@ -180,6 +187,7 @@ SIGNATURES = {
     "kivi_vt_pack_at": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _i32, _i64, _i32, _i32, _i32, _vp]),
     "kivi_cache_reorder": (_i32, [ctypes.POINTER(ReorderSlab), _i32, _i32, _i32, _vp, _i32, _vp]),
     "kivi_cache_snapshot": (_i32, [ctypes.POINTER(ReorderSlab), _i32, _i32, _vp, ctypes.c_size_t, _i32, _vp]),
+    "kivi_cache_admit": (_i32, [ctypes.POINTER(AdmitSlab), _i32, _i32, _vp, _i32, _i32, _vp]),
     "kivi_sample": (_i32, [_vp, _i32, _i64, _i32, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float, _vp, _vp, _i64, _vp]),
     "kivi_sample_rows": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "kivi_token_logprob": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),

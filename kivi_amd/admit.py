@@ -1,0 +1,87 @@
+"""Admission of new requests into rows of a living KIVI cache (continuous batching): the admit slabs and the
+call of kivi_cache_admit.
+
+A layer cache has ONE length for all its rows, so a prompt admitted at length L is the prompt left-padded to L and run as an
+ordinary prompt pass of its own (pads are masked cache tokens); what is left to do is to put the rows of that
+temporary cache into chosen rows of the living one without touching any other row, buffer address or length.  Source and
+destination are different allocations, their capacities (hence strides) may differ and their fp16 V windows sit at different
+offsets, so a slab (include/kivi_hip.h, kivi_admit_slab) names both sides; each layout lists them in `_admit_slabs(src)`.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+
+
+def slab(dst: torch.Tensor, dst_off: int, src: torch.Tensor, src_off: int, levels, run: int):
+    """An admit slab from tensor `src` (byte `src_off` from its data pointer) to tensor `dst` (byte `dst_off`): levels
+    [(count, destination byte stride, source byte stride)] (at most three), `run` bytes.
+    -> (dst base, dst row stride, [dst strides], src base, src row stride, [src strides], [counts], run)."""
+    levels = list(levels) + [(1, 0, 0)] * (3 - len(levels))
+    return (dst.data_ptr() + dst_off, dst.stride(0) * dst.element_size(), [d for _, d, _ in levels],
+            src.data_ptr() + src_off, src.stride(0) * src.element_size(), [s for _, _, s in levels],
+            [n for n, _, _ in levels], run)
+
+
+def rows_tensor(rows) -> torch.Tensor:
+    """The destination rows as a 1-D int32 / int64 tensor (where they are): ValueError for anything else."""
+    if not torch.is_tensor(rows):
+        try:
+            rows = torch.as_tensor(list(rows))
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"rows must be a 1-D int32 or int64 tensor or a sequence of row indices, got {rows!r}") from None
+        if rows.numel() == 0:
+            rows = rows.long()
+    if rows.dim() != 1 or rows.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"rows must be a 1-D int32 or int64 tensor or a sequence of row indices, got {tuple(rows.shape)} {rows.dtype}")
+    return rows
+
+
+def check_rows(rows, n: int, B: int, device, check_values: bool = True) -> torch.Tensor:
+    """Validate the destination rows of an admission (raises ValueError) and return them as a contiguous int32 / int64 tensor on
+    `device`: `n` distinct rows in [0, B).  `check_values=False` skips the look at the values (a device read): the kernel leaves a
+    source row whose index lies outside [0, B) unused."""
+    rows = rows_tensor(rows)
+    if rows.shape[0] != n:
+        raise ValueError(f"{rows.shape[0]} rows were named for {n} rows to admit")
+    if not 1 <= n <= B:
+        raise ValueError(f"{n} rows cannot be admitted into a cache of {B} rows")
+    rows = rows.to(device).contiguous()
+    if check_values:
+        if not bool(((rows >= 0) & (rows < B)).all()):
+            raise ValueError(f"rows out of range: every row must lie in [0, {B}), got {rows.tolist()}")
+        if torch.unique(rows).numel() != n:
+            raise ValueError(f"duplicate rows: {rows.tolist()} (every destination row takes one source row)")
+    return rows
+
+
+def live(slabs):
+    return [s for s in slabs if s[7] > 0 and all(c > 0 for c in s[6])]
+
+
+def run(slabs, rows: torch.Tensor, B: int) -> None:
+    """One kivi_cache_admit call per KIVI_REORDER_MAX_SLABS slabs (their destinations are disjoint, so the calls are independent)."""
+    slabs = live(slabs)
+    lib = _lib.load()
+    stream = _lib.stream_ptr(rows)
+    for i in range(0, len(slabs), _lib.REORDER_MAX_SLABS):
+        part = slabs[i: i + _lib.REORDER_MAX_SLABS]
+        arr = (_lib.AdmitSlab * len(part))()
+        for d, (db, drs, dst, sb, srs, sst, cnt, nbytes) in zip(arr, part):
+            d.dst_base, d.dst_row_stride, d.src_base, d.src_row_stride, d.run = db, drs, sb, srs, nbytes
+            for k in range(3):
+                d.dst_stride[k], d.src_stride[k], d.n[k] = dst[k], sst[k], cnt[k]
+        _lib.check(lib.kivi_cache_admit(arr, len(part), rows.shape[0], _lib.ptr(rows), rows.element_size(), B, stream),
+                   "kivi_cache_admit")
+
+
+def moved_bytes(slabs, rows: int) -> int:
+    """Bytes read + written when `rows` rows are admitted (the algorithmic traffic of an admission)."""
+    per_row = 0
+    for s in slabs:
+        n = s[7]
+        for c in s[6]:
+            n *= c
+        per_row += n
+    return 2 * rows * per_row

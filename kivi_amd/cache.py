@@ -33,7 +33,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from . import _lib, _tuning, checkpoint, reorder
+from . import _lib, _tuning, admit, checkpoint, reorder
 from ._lib import KiviUnsupported, check_mask_size, mask_arg, out_arg, unit_rows
 from .quant import fused, matmul, new_pack
 
@@ -113,7 +113,7 @@ class KiviPerformanceWarning(UserWarning):
 class KiviCacheBase:
     """What the two layouts of a layer's cache (KiviLayerCache here, KiviLayerCacheMF in cache_mf.py) share: the geometry, the six
     lengths of the state machine, the scratch of a decode step, and everything that follows from them alone.  A layout adds its
-    buffers (`reserve`, `_own_buffers`, `_reorder_slabs`, `_checkpoint_slabs`, `prefill`), the readers of the reference layout
+    buffers (`_BUFFERS`, `reserve`, `_own_buffers`, `_reorder_slabs`, `_checkpoint_slabs`, `_admit_slabs`, `prefill`), the readers of the reference layout
     (`k_quant_reference_layout`, `v_quant_views`, `v_res_view`) and its steps (`decode_step`, `extend`)."""
 
     def __init__(self, cfg: KiviConfig, batch: int, num_kv_heads: int, head_dim: int, max_len: int, dtype):
@@ -189,6 +189,47 @@ class KiviCacheBase:
         idx = reorder.check_idx(idx, self.B, group, self.k_res.device, check)
         reorder.run(self._reorder_slabs(int(from_token)), self.B, group, idx)
         self._void_checkpoints()          # rows have changed places: no rollback across a reorder
+        return self
+
+    # ------------------------------------------------------------------ continuous batching
+    def _admit_geometry(self) -> tuple:
+        """What source and destination of an admission have to share: everything but the batch size, the capacity and where the V
+        window stands."""
+        return tuple(x for i, x in enumerate(self._geometry()) if i != 1)
+
+    def check_admit(self, src, n: int) -> None:
+        """Raise ValueError when `src` cannot be admitted into `n` rows of this cache (nothing runs on a device)."""
+        if src is self:
+            raise ValueError("admit_: the source is the destination cache itself")
+        if not isinstance(src, KiviCacheBase) or src._admit_geometry() != self._admit_geometry():
+            theirs = src._admit_geometry() if isinstance(src, KiviCacheBase) else type(src).__name__
+            raise ValueError(f"admit_: the source is of another class or geometry: {theirs}, this cache is {self._admit_geometry()}")
+        for name in ("kv_seq_len", "k_quant_len", "k_res_len", "v_quant_len", "v_res_len"):
+            if getattr(src, name) != getattr(self, name):
+                raise ValueError(f"admit_: {name} differs: the source is at {getattr(src, name)}, this cache at {getattr(self, name)} "
+                                 f"(a prompt is admitted left-padded to the living cache's length)")
+        if src.B != n:
+            raise ValueError(f"admit_: the source holds {src.B} rows, {n} rows were named")
+        mine = {getattr(self, b).untyped_storage().data_ptr() for b in self._BUFFERS}
+        if any(getattr(src, b).untyped_storage().data_ptr() in mine for b in src._BUFFERS):
+            raise ValueError("admit_: the source shares a buffer with this cache (admit from a cache of its own, e.g. a clone)")
+
+    def admit_(self, rows, src, check: bool = True):
+        """Row rows[i] of this cache <- row i of `src`, in place (kivi_cache_admit): a new request takes over the row of a finished
+        one.  `src`: a cache of the same class and geometry -- batch size, capacity and v_res_start may differ -- of len(rows) rows at
+        the same six lengths (a prompt pass over the prompts left-padded to this cache's length), sharing no buffer with this one.
+        `rows`: distinct rows in [0, B), a 1-D int32 / int64 tensor or a sequence; `check=False` skips the host-side check of their
+        values (a device read; the kernel leaves a source row with an index outside [0, B) unused).  What moves (`_admit_slabs`): the
+        packed K and V up to their lengths, the range words (replaced), the fp16 K residual, the live fp16 window tokens from the
+        source's window positions to this cache's.  Lengths, data pointers, the native descriptor, the scratch rows and the fusion
+        flags stay: captured graphs remain valid.  Checkpoints issued so far become stale, as after a reorder.  ValueError before
+        anything runs on a device for another class or geometry, a length that differs, a row count that does not fit, bad rows,
+        `src is self` or a shared buffer."""
+        rows = admit.rows_tensor(rows)
+        self.check_admit(src, rows.shape[0])
+        rows = admit.check_rows(rows, rows.shape[0], self.B, self.k_res.device, check)
+        admit.run(self._admit_slabs(src), rows, self.B)
+        self._void_checkpoints()          # a row holds another request now: no rollback across an admission
         return self
 
     # ------------------------------------------------------------------ checkpoint / rollback (DESIGN.md section 13)
@@ -311,6 +352,11 @@ class KiviLayerCache(KiviCacheBase):
         # fp16 V window: R (+1 transient) live tokens inside a 2R+1 buffer, compacted every R steps
         self.v_res = torch.empty((batch, num_kv_heads, 2 * R + 1, head_dim), dtype=dtype, device=dev)
 
+    _BUFFERS = ("k_code", "k_scale", "k_mn", "k_res", "v_code", "v_scale", "v_mn", "v_res")
+
+    def _admit_geometry(self) -> tuple:
+        return super()._admit_geometry() + (self.page_tokens,)
+
     @staticmethod
     def _paged(shape, dtype, device) -> torch.Tensor:
         B, h, P, D, W = shape
@@ -378,6 +424,37 @@ class KiviLayerCache(KiviCacheBase):
             rowb = self.D * 2
             b0, b1 = _span(self.v_res_start * rowb, (self.v_res_start + self.v_res_len) * rowb, self.v_res.shape[2] * rowb)
             out.append(slab(self.v_res, b0, [(h, self.v_res.stride(1) * 2)], b1 - b0))
+        return out
+
+    def _admit_slabs(self, src: "KiviLayerCache"):
+        """Everything in use of a row of `src` (same geometry and lengths; its own capacity and window start) -> this cache's buffers:
+        the K pages up to k_quant_len (whole pages as one slab with the page index as a level, each side with its own page stride;
+        then the partly filled page), the fp16 K residual, the V triple up to v_quant_len, the window from the source's
+        [v_res_start, + v_res_len) to this cache's."""
+        from .reorder import _span
+        g, P, kf, h, D = self.cfg.group_size, self.page_tokens, 32 // self.cfg.k_bits, self.nh_kv, self.D
+        out = []
+        full, part = divmod(self.k_quant_len, P)
+        for x, y, per in ((self.k_code, src.k_code, kf), (self.k_scale, src.k_scale, g), (self.k_mn, src.k_mn, g)):
+            es = x.element_size()
+            inner = [(h, x.stride(1) * es, y.stride(1) * es), (D, x.stride(3) * es, y.stride(3) * es)]
+            if full:
+                out.append(admit.slab(x, 0, y, 0, [(full, x.stride(2) * es, y.stride(2) * es)] + inner, x.shape[4] * es))
+            if part:
+                b0, b1 = _span(0, -(-part // per) * es, x.shape[4] * es)
+                out.append(admit.slab(x, full * x.stride(2) * es, y, full * y.stride(2) * es, inner, b1 - b0))
+        rowb = D * 2
+        if self.k_res_len:
+            out.append(admit.slab(self.k_res, 0, src.k_res, 0, [(h, self.k_res.stride(1) * 2, src.k_res.stride(1) * 2)],
+                                  self.k_res_len * rowb))
+        if self.v_quant_len:
+            for x, y in ((self.v_code, src.v_code), (self.v_scale, src.v_scale), (self.v_mn, src.v_mn)):
+                es, tokb = x.element_size(), x.shape[3] * x.element_size()
+                b0, b1 = _span(0, self.v_quant_len * tokb, min(x.shape[2], y.shape[2]) * tokb)
+                out.append(admit.slab(x, 0, y, 0, [(h, x.stride(1) * es, y.stride(1) * es)], b1 - b0))
+        if self.v_res_len:
+            out.append(admit.slab(self.v_res, self.v_res_start * rowb, src.v_res, src.v_res_start * rowb,
+                                  [(h, self.v_res.stride(1) * 2, src.v_res.stride(1) * 2)], self.v_res_len * rowb))
         return out
 
     def _checkpoint_slabs(self, state=None):

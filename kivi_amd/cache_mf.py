@@ -24,7 +24,7 @@ import math
 
 import torch
 
-from . import _lib, _tuning
+from . import _lib, _tuning, admit
 from ._lib import check_mask_size, mask_arg, out_arg, rows16
 from .cache import KiviCacheBase, KiviConfig, KiviLayerCache
 from .quant import matmul, mfma, new_pack
@@ -87,6 +87,8 @@ class KiviLayerCacheMF(KiviCacheBase):
         self.ring = True
         self.v_res = torch.empty((batch, num_kv_heads, R + 1, head_dim), dtype=dtype, device=device)
         self.flags = 0            # _lib.GQA_FORCE_SPLIT / GQA_FORCE_ROW (tests, tuning)
+
+    _BUFFERS = ("kt", "vt", "k_res", "v_res")
 
     # ------------------------------------------------------------------ capacity
     def reserve(self, max_len: int) -> None:
@@ -158,6 +160,50 @@ class KiviLayerCacheMF(KiviCacheBase):
         if self.k_res_len:
             out.append(slab(self.k_res, 0, [(h, self.k_res.stride(1) * 2)], self.k_res_len * self.D * 2))
         out.append(slab(self.v_res, 0, [(h, self.v_res.stride(1) * 2)], self.v_res.shape[2] * self.D * 2))
+        return out
+
+    # ------------------------------------------------------------------ continuous batching
+    def _admit_slabs(self, src: "KiviLayerCacheMF"):
+        """Everything in use of a row of `src` (same geometry and lengths; its own super-block count and ring phase) -> this cache's
+        buffers.  The stores move in whole 32-token blocks as in _reorder_slabs(0) -- whole super-blocks as one slab with the
+        super-block index as a level, then the blocks in use of the last one with their scale / zero-point pieces; a partly filled V
+        block arrives with the source's clean tail -- every stride taken from each side's own store; the range words are replaced;
+        the fp16 K residual up to its length; the live window tokens rotated from the source's ring phase to this cache's in at
+        most three contiguous segments (token t: source row (s_src + t) mod rows -> row (s_dst + t) mod rows).  The ring row that
+        holds no live token is not written."""
+        h = self.nh_kv
+        W = mfma.sb_words(self.cfg.k_bits)
+        S0, BW = (W - 2048) * 4, (W - 2048) // 16 * 4          # byte offset of the scale region, bytes of codes per block
+        out = []
+        for st, sy, n_tok, is_k in ((self.kt, src.kt, self.k_quant_len, True), (self.vt, src.vt, self.v_quant_len, False)):
+            heads = (h, st.stride(1) * 4, sy.stride(1) * 4)
+            dss, sss = st.stride(2) * 4, sy.stride(2) * 4
+            full, hi = divmod(-(-n_tok // 32), 16)               # whole super-blocks, blocks in use of the next one
+            if full:
+                out.append(admit.slab(st, 0, sy, 0, [(full, dss, sss), heads], W * 4))
+            if hi:
+                d0, s0 = full * dss, full * sss
+                out.append(admit.slab(st, d0, sy, s0, [heads], hi * BW))
+                if is_k:
+                    for half in (0, 1):
+                        ghi = min(hi, 8 * half + 8) - 8 * half
+                        if ghi > 0:
+                            out.append(admit.slab(st, d0 + S0 + half * 2048, sy, s0 + S0 + half * 2048,
+                                                  [heads, (2, 4096, 4096), (16, 128, 128)], ghi * 16))
+                else:
+                    out.append(admit.slab(st, d0 + S0, sy, s0 + S0, [heads, (2, 4096, 4096)], hi * 256))
+            out.append(admit.slab(mfma.range_flags(st), 0, mfma.range_flags(sy), 0, [], h * 4))
+        rowb = self.D * 2
+        if self.k_res_len:
+            out.append(admit.slab(self.k_res, 0, src.k_res, 0, [(h, self.k_res.stride(1) * 2, src.k_res.stride(1) * 2)],
+                                  self.k_res_len * rowb))
+        rows, t = self.v_res.shape[2], 0
+        ring = [(h, self.v_res.stride(1) * 2, src.v_res.stride(1) * 2)]
+        while t < self.v_res_len:                                # a segment ends where either side wraps (or the window does)
+            d, s = (self.v_res_start + t) % rows, (src.v_res_start + t) % rows
+            n = min(self.v_res_len - t, rows - d, rows - s)
+            out.append(admit.slab(self.v_res, d * rowb, src.v_res, s * rowb, ring, n * rowb))
+            t += n
         return out
 
     def _checkpoint_slabs(self, state=None):

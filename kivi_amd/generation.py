@@ -10,11 +10,16 @@ import torch
 _MIN16 = torch.finfo(torch.float16).min
 
 
-def left_pad(seqs, pad_token_id: int = 0, device=None):
+def left_pad(seqs, pad_token_id: int = 0, device=None, length: Optional[int] = None):
     """A list of token id sequences -> (ids (B, T), mask (B, T)) left-padded to the longest one (HF's tokenizer with
-    padding_side="left"): mask is 1 on real tokens, 0 on the `pad_token_id` fillers."""
+    padding_side="left"): mask is 1 on real tokens, 0 on the `pad_token_id` fillers.  `length`: pad to T = length instead (an
+    admission into living caches pads to their length); ValueError when a sequence is longer."""
     seqs = [torch.as_tensor(s, dtype=torch.long).flatten() for s in seqs]
     T = max(len(s) for s in seqs)
+    if length is not None:
+        if isinstance(length, bool) or not isinstance(length, int) or length < T:
+            raise ValueError(f"length={length!r}: the longest sequence has {T} tokens, it cannot be left-padded to that")
+        T = length
     ids = torch.full((len(seqs), T), pad_token_id, dtype=torch.long)
     mask = torch.zeros((len(seqs), T), dtype=torch.long)
     for i, s in enumerate(seqs):

@@ -8,7 +8,8 @@ Parameter names follow the Hugging Face checkpoints (model.embed_tokens, model.l
 attention block is plain torch (rocBLAS / hipBLASLt GEMMs).  The reference patches k_bits / v_bits / group_size / residual_length
 onto the HF config (README.md:72-75); the same four fields are read here.
 What a generate call is made of -- left padding, the sampler of the call, the prompt pass and its fork, the eager step, the decode
-loop -- is kivi_amd/generation.py; beam search is kivi_amd/beam.py, the graphed decode step kivi_amd/graph.py (DecodeGraphs).
+loop -- is kivi_amd/generation.py; beam search is kivi_amd/beam.py, the graphed decode step kivi_amd/graph.py (DecodeGraphs), the
+scheduler of continuous batching kivi_amd/serving.py (over admit_() here and kivi_amd/admit.py).
 """
 from __future__ import annotations
 
@@ -22,6 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import admit
 from .attention import KiviLayerCacheMF, LlamaAttention_KIVI
 from .beam import beam_search
 from .generation import (EagerStepper, _PaddedBatch, decode_loop, left_pad, padding_key_row, padding_position_ids,  # noqa: F401
@@ -201,6 +203,41 @@ class LlamaForCausalLM_KIVI(nn.Module):
         for c, k in zip(caches, ck.layers):
             c.check_restore(k)
         return [c.restore_(k).as_tuple() for c, k in zip(caches, ck.layers)]
+
+    # ------------------------------------------------------------------ continuous batching
+    @torch.no_grad()
+    def admit_(self, past_key_values, rows, input_ids: torch.LongTensor, attention_mask: torch.Tensor):
+        """New requests take over rows of living caches: -> (prompt logits (n, 1, vocab), fresh tuples of the living caches).
+        `past_key_values`: the tuples of forward() / generate() over caches of B rows at kv length L.  `input_ids` (n, L) and HF's 2D
+        `attention_mask` (n, L): the n new prompts left-padded to exactly L (left_pad(..., length=L); a prompt of L tokens has no
+        pad).  `rows`: n distinct rows in [0, B).  The prompts run as an ordinary prompt pass of n rows,
+        forward(input_ids, padding_mask=attention_mask) -- the flash classes refuse padded prompts there as ever -- and every layer's
+        temporary cache is put into the rows in place (KiviCacheBase.admit_): the other rows, every buffer address and the lengths
+        stay, so captured decode graphs over the living caches remain valid; the temporary caches die with the call.  ValueError
+        before any forward pass for plain 9-tuples, input_ids of another length than L, a mask of another shape, n > B, bad rows."""
+        caches = self._layer_caches(past_key_values, "admit_")
+        L, B = caches[0].kv_seq_len, caches[0].B
+        if input_ids.dim() != 2 or input_ids.shape[1] != L:
+            raise ValueError(f"admit_: input_ids must be (n, L) with L = {L}, the kv length of the living caches (left-pad the prompts "
+                             f"to it), got {tuple(input_ids.shape)}")
+        n = input_ids.shape[0]
+        if attention_mask is None or attention_mask.dim() != 2 or tuple(attention_mask.shape) != (n, L):
+            raise ValueError(f"admit_: the 2D attention mask should be of size {(n, L)}, but is "
+                             f"{None if attention_mask is None else tuple(attention_mask.shape)}")
+        if not 1 <= n <= B:
+            raise ValueError(f"admit_: {n} prompts for living caches of {B} rows")
+        rows = admit.check_rows(rows, n, B, caches[0].k_res.device)
+        logits, fresh = self.forward(input_ids, padding_mask=attention_mask)
+        for c, t in zip(caches, fresh):
+            c.admit_(rows, t.layer, check=False)
+        return logits, [c.as_tuple() for c in caches]
+
+    def generate_continuous(self, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
+                            pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False):
+        """Continuous batching over a queue of requests (kivi_amd/serving.py: generate_continuous): a batch of `batch_size` rows whose
+        finished rows are taken over by the waiting prompts.  -> the generated tokens of every request, in request order."""
+        from .serving import generate_continuous
+        return generate_continuous(self, prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, graphed)
 
     # ------------------------------------------------------------------ scoring given tokens (DESIGN.md section 14)
     _HEAD_SLAB = 4096            # rows of hidden states per lm_head call of score(): logits exist for one slab at a time

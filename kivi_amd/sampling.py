@@ -194,20 +194,23 @@ class RowSampler:
         from the records.  (The leading string keeps it apart from every Sampler.key().)"""
         return ("rows", self.B, self.records.data_ptr(), self.draw_index.data_ptr())
 
-    def set_row(self, b: int, params: SamplingParams, stream: int = 0) -> None:
-        """A new request takes over row b: its record is rewritten and its draw index zeroed, by asynchronous copies on the current
-        stream (ordered after the calls already enqueued there); no other row is touched and nothing has to be captured again."""
+    def set_row(self, b: int, params: SamplingParams, stream: int = 0, draw_index: int = 0) -> None:
+        """A new request takes over row b: its record is rewritten and its draw index set to `draw_index` (default 0; a scheduler
+        that has drawn the request's first tokens elsewhere passes how many), by asynchronous copies on the current stream (ordered
+        after the calls already enqueued there); no other row is touched and nothing has to be captured again."""
         if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < self.B:
             raise ValueError(f"row {b!r} outside [0, {self.B})")
         if not isinstance(params, SamplingParams):
             raise ValueError("params has to be a SamplingParams")
         stream = _check_stream(stream)
+        if isinstance(draw_index, bool) or not isinstance(draw_index, int) or not 0 <= draw_index < 2 ** 63:
+            raise ValueError(f"draw_index has to be an integer in [0, 2^63), got {draw_index!r}")
         p = self._bind(params)
         rec = _record(p, stream)
         if self.records.is_cuda:
             rec = rec.pin_memory()
         self.records[b].copy_(rec, non_blocking=True)
-        self.draw_index[b: b + 1].zero_()
+        self.draw_index[b: b + 1].fill_(draw_index)
         self.params[b], self.streams[b] = p, stream
 
     def reset(self) -> None:

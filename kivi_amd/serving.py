@@ -1,0 +1,144 @@
+"""Continuous batching over a queue of requests: `generate_continuous`, the scheduler above
+LlamaForCausalLM_KIVI.admit_.
+
+generate() decodes a batch until its slowest row has finished; a row that is done keeps feeding pad tokens, and a waiting request
+is served only by a new prompt pass over a new batch.  Here a finished row is taken over by the next waiting request between two
+steps: its prompt, left-padded to the living caches' length, runs as a prompt pass of its own and is put into the row in place
+(kivi_cache_admit); the other rows, every buffer and every captured graph stay as they are.
+
+The policy is fixed (tests restate it):
+  * B = min(batch_size, number of requests); the first B requests form the initial batch, left-padded to L0, the longest prompt of
+    ALL requests of the call -- every later admission (at a length >= L0) then fits.
+  * Every iteration picks a token for every row from the logits the row has; a live row records it.  A row is finished when the
+    token is `eos_token_id` or the request holds its `max_new_tokens` (the one synchronisation of a step: the tokens are read).
+  * Finished rows take the next waiting requests, lowest row first and in FIFO order, through ONE admit_ at the current length.
+    An admitted request's first token is picked from its prompt logits and replaces the row's token before the step; should that
+    token already finish the request, the row is free again and the admission repeats at the same length.
+  * Rows with nothing to do feed `pad_token_id`.  The call ends when every request is done: no step runs after the last pick.
+  * Token i of a request is draw i of its own seed with Philox stream 0, whichever row and step it lands on:
+    the first token is drawn by a RowSampler of the admitted rows alone, then the batch's RowSampler row is bound with
+    set_row(..., draw_index=1).
+"""
+from __future__ import annotations
+
+from typing import List, Optional
+
+import torch
+
+from .generation import left_pad, padding_key_row
+from .sampling import RowSampler, SamplingParams
+
+
+def _positive_int(x) -> bool:
+    return isinstance(x, int) and not isinstance(x, bool) and x >= 1
+
+
+def check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, vocab_size: Optional[int] = None):
+    """-> (prompts as 1-D int64 CPU tensors, max_new_tokens per request, bound SamplingParams per request or None); ValueError for
+    anything generate_continuous cannot serve (no device work)."""
+    if not isinstance(prompts, (list, tuple)) or not prompts:
+        raise ValueError("prompts has to be a non-empty list of token id sequences")
+    seqs = [torch.as_tensor(p, dtype=torch.long).flatten().cpu() for p in prompts]
+    N = len(seqs)
+    for r, s in enumerate(seqs):
+        if not s.numel():
+            raise ValueError(f"prompt {r} is empty")
+        if vocab_size is not None and (int(s.min()) < 0 or int(s.max()) >= vocab_size):
+            raise ValueError(f"prompt {r} holds token ids outside the vocabulary [0, {vocab_size})")
+    if not _positive_int(batch_size):
+        raise ValueError(f"batch_size has to be a positive integer, got {batch_size!r}")
+    if _positive_int(max_new_tokens):
+        limits = [max_new_tokens] * N
+    elif isinstance(max_new_tokens, (list, tuple)) and all(_positive_int(m) for m in max_new_tokens):
+        limits = list(max_new_tokens)
+        if len(limits) != N:
+            raise ValueError(f"{len(limits)} max_new_tokens for {N} requests")
+    else:
+        raise ValueError(f"max_new_tokens has to be a positive integer or one per request, got {max_new_tokens!r}")
+    if eos_token_id is not None and pad_token_id is None:
+        raise ValueError("eos_token_id needs a pad_token_id for the rows that have nothing to do")
+    if sampling is None:
+        params = None
+    else:
+        if isinstance(sampling, SamplingParams):
+            sampling = [sampling] * N
+        elif not isinstance(sampling, (list, tuple)) or not all(isinstance(p, SamplingParams) for p in sampling):
+            raise ValueError("sampling has to be None (greedy), a SamplingParams, or a list with one SamplingParams per request")
+        if len(sampling) != N:
+            raise ValueError(f"{len(sampling)} SamplingParams for {N} requests")
+        params = [RowSampler._bind(p) for p in sampling]          # one seed per request, whichever row it lands on
+    return seqs, limits, params
+
+
+@torch.no_grad()
+def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
+                        pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False) -> List[torch.Tensor]:
+    """`prompts`: a list of token id sequences, possibly more than `batch_size`; `max_new_tokens`: an int or one per request;
+    `sampling`: None (greedy), one SamplingParams, or one per request.  -> the generated tokens of every request as 1-D int64
+    tensors, in request order, ending with `eos_token_id` where it was produced.  The policy: the module docstring.
+    `graphed=True`: the steps go through decode_graphed(..., attention_mask=, sampling=) over the same living caches; the 2D mask
+    with the replaced rows is passed again after an admission and the captured step is replayed, not captured again (unless the
+    mask buffer has to grow, or the first pad of the call arrives with an admission).  Same tokens as graphed=False."""
+    prompts, limits, params = check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling,
+                                              model.config.vocab_size)
+    pad = 0 if pad_token_id is None else pad_token_id
+    N, device = len(prompts), model.lm_head.weight.device
+    B = min(batch_size, N)
+    L = max(p.numel() for p in prompts)
+
+    ids, mask = left_pad(prompts[:B], pad, device, length=L)
+    logits, pasts = model.forward(ids, padding_mask=mask)
+    sampler = None if params is None else RowSampler(params[:B], device)
+
+    def pick(lg, rows_sampler):
+        return lg.argmax(-1) if rows_sampler is None else rows_sampler(lg)
+
+    tok = pick(logits, sampler)
+    mask2d = torch.ones((B, 2 * L + 64), dtype=torch.long, device=device)      # column t: 1 = cache token t of the row is real
+    mask2d[:, :L] = mask
+    owner: List[Optional[int]] = list(range(B))                                # the request of every row (None: nothing to do)
+    out: List[List[int]] = [[] for _ in range(N)]
+    waiting = B
+
+    def record(b: int, t: int) -> None:
+        r = owner[b]
+        out[r].append(t)
+        if len(out[r]) >= limits[r] or (eos_token_id is not None and t == eos_token_id):
+            owner[b] = None
+
+    while True:
+        for b, t in enumerate(tok.view(-1).tolist()):                          # the one synchronisation of a step
+            if owner[b] is not None:
+                record(b, t)
+        while waiting < N and None in owner:
+            rows = [b for b in range(B) if owner[b] is None][: N - waiting]
+            reqs = list(range(waiting, waiting + len(rows)))
+            waiting += len(rows)
+            new_ids, new_mask = left_pad([prompts[r] for r in reqs], pad, device, length=L)
+            lg, pasts = model.admit_(pasts, rows, new_ids, new_mask)
+            mask2d[rows, :L] = new_mask
+            first = pick(lg, None if params is None else RowSampler([params[r] for r in reqs], device))     # draw 0 of each
+            tok[rows] = first
+            for b, r, t in zip(rows, reqs, first.view(-1).tolist()):
+                owner[b] = r
+                if sampler is not None:
+                    sampler.set_row(b, params[r], draw_index=1)
+                record(b, t)
+        if all(r is None for r in owner):
+            break
+        idle = [b for b in range(B) if owner[b] is None]
+        if idle:
+            tok[idle] = pad
+        if L + 1 > mask2d.shape[1]:
+            mask2d = torch.cat([mask2d, torch.ones_like(mask2d)], dim=1)
+        m = mask2d[:, : L + 1]                                                 # the fed token is real in every row
+        if graphed:
+            model.decode_graphed(tok, pasts, L, 1, attention_mask=m, sampling=sampler)
+            tok = model.graphs.tok.clone()
+        else:
+            logits, pasts = model._forward(tok, pasts, padding_key_row(m), m.sum(-1, keepdim=True) - 1, True, True)
+            tok = pick(logits, sampler)
+        L += 1
+    if graphed and model.graphs is not None:
+        model.graphs.end()           # the caches of this call die with it: so does the graph captured over them
+    return [torch.tensor(o, dtype=torch.long, device=device) for o in out]
