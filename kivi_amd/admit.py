@@ -12,6 +12,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from . import slabs as _slabs
 
 
 def slab(dst: torch.Tensor, dst_off: int, src: torch.Tensor, src_off: int, levels, run: int):
@@ -56,32 +57,16 @@ def check_rows(rows, n: int, B: int, device, check_values: bool = True) -> torch
     return rows
 
 
-def live(slabs):
-    return [s for s in slabs if s[7] > 0 and all(c > 0 for c in s[6])]
+live = _slabs.live
 
 
 def run(slabs, rows: torch.Tensor, B: int) -> None:
     """One kivi_cache_admit call per KIVI_REORDER_MAX_SLABS slabs (their destinations are disjoint, so the calls are independent)."""
-    slabs = live(slabs)
-    lib = _lib.load()
-    stream = _lib.stream_ptr(rows)
-    for i in range(0, len(slabs), _lib.REORDER_MAX_SLABS):
-        part = slabs[i: i + _lib.REORDER_MAX_SLABS]
-        arr = (_lib.AdmitSlab * len(part))()
-        for d, (db, drs, dst, sb, srs, sst, cnt, nbytes) in zip(arr, part):
-            d.dst_base, d.dst_row_stride, d.src_base, d.src_row_stride, d.run = db, drs, sb, srs, nbytes
-            for k in range(3):
-                d.dst_stride[k], d.src_stride[k], d.n[k] = dst[k], sst[k], cnt[k]
-        _lib.check(lib.kivi_cache_admit(arr, len(part), rows.shape[0], _lib.ptr(rows), rows.element_size(), B, stream),
-                   "kivi_cache_admit")
+    for arr in _slabs.arrays(slabs):
+        _lib.check(_lib.load().kivi_cache_admit(arr, len(arr), rows.shape[0], _lib.ptr(rows), rows.element_size(), B,
+                                                _lib.stream_ptr(rows)), "kivi_cache_admit")
 
 
 def moved_bytes(slabs, rows: int) -> int:
     """Bytes read + written when `rows` rows are admitted (the algorithmic traffic of an admission)."""
-    per_row = 0
-    for s in slabs:
-        n = s[7]
-        for c in s[6]:
-            n *= c
-        per_row += n
-    return 2 * rows * per_row
+    return 2 * rows * sum(map(_slabs.row_bytes, slabs))

@@ -20,6 +20,7 @@ state machine and calls over 10240-word super-blocks (kivi_mfma_layout.h, "KT4 /
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 
 import torch
@@ -64,6 +65,35 @@ def _scratch(device, B: int, nh: int, nh_kv: int, pitch: int, nseg: int, slices:
         ws = torch.zeros(need, dtype=torch.uint8, device=device)   # arrival counters start at zero; the kernel resets them
         d["ws"] = ws
     return sc, st, ws
+
+
+@functools.lru_cache(maxsize=256)
+def _store_pieces(W: int, j0: int, j1: int, is_k: bool):
+    """The pieces in use of a packed store of W-word super-blocks from block j0 to block j1, blocks of 32 tokens, 16 to a super-block
+    (kivi_mfma_layout.h), as (first super-block, super-blocks, byte offset in the super-block, inner levels [(count, byte
+    stride)] below the head level, run bytes).  Whole super-blocks come as one run with their count (otherwise the count is 0); of
+    a partial one: the codes of block j at words [j BW, (j + 1) BW); the V scales / zero points of block j at halves j * 128 of
+    their regions; the K scales / zero points of group j at halves (j >> 3) * 1024 + (c, kb) * 64 + (j & 7) * 8 (16 pieces of
+    16 bytes per block).  Cached: a decoding cache asks for the same walk until it crosses a block."""
+    S0, BW = (W - 2048) * 4, (W - 2048) // 16 * 4              # byte offset of the scale region, bytes of codes per block
+    out, s = [], j0 // 16
+    while s * 16 < j1 and j0 < j1:
+        lo, hi = max(j0, 16 * s) - 16 * s, min(j1, 16 * s + 16) - 16 * s
+        if lo == 0 and hi == 16:
+            n = j1 // 16 - s
+            out.append((s, n, 0, (), W * 4))
+            s += n
+            continue
+        out.append((s, 0, lo * BW, (), (hi - lo) * BW))
+        if is_k:
+            for half in (0, 1):
+                glo, ghi = max(lo, 8 * half), min(hi, 8 * half + 8)
+                if glo < ghi:
+                    out.append((s, 0, S0 + (half * 1024 + (glo & 7) * 8) * 2, ((2, 4096), (16, 128)), (ghi - glo) * 16))
+        else:
+            out.append((s, 0, S0 + lo * 256, ((2, 4096),), (hi - lo) * 256))
+        s += 1
+    return tuple(out)
 
 
 class KiviLayerCacheMF(KiviCacheBase):
@@ -125,37 +155,15 @@ class KiviLayerCacheMF(KiviCacheBase):
 
     # ------------------------------------------------------------------ beam search
     def _reorder_slabs(self, from_token: int):
-        """Super-blocks of 16 blocks of 32 tokens (kivi_mfma_layout.h): codes of block j at words [j BW, (j + 1) BW); V scales /
-        zero points of block j at halves j * 128 of their regions; K scales / zero points of group j at halves
-        (j >> 3) * 1024 + (c, kb) * 64 + (j & 7) * 8 (16 pieces of 16 bytes per block).  Whole super-blocks move as one run."""
+        """The blocks of both stores from from_token's on (K groups / V tokens), the range words, the fp16 K residual up to its
+        length, the whole fp16 V ring."""
         from .reorder import slab
-        h = self.nh_kv
-        W = mfma.sb_words(self.cfg.k_bits)
-        S0, BW = (W - 2048) * 4, (W - 2048) // 16 * 4          # byte offset of the scale region, bytes of codes per block
+        h, W = self.nh_kv, mfma.sb_words(self.cfg.k_bits)
         out = []
         for st, n_tok, is_k in ((self.kt, self.k_quant_len, True), (self.vt, self.v_quant_len, False)):
             ss, sh = st.stride(2) * 4, st.stride(1) * 4
-            j0, j1 = from_token // 32, -(-n_tok // 32)           # blocks [j0, j1): K groups / V tokens from from_token on
-            s = j0 // 16
-            while s * 16 < j1 and j0 < j1:
-                lo, hi = max(j0, 16 * s) - 16 * s, min(j1, 16 * s + 16) - 16 * s
-                if lo == 0 and hi == 16:
-                    e = s
-                    while (e + 2) * 16 <= j1:
-                        e += 1
-                    out.append(slab(st, s * ss, [(e - s + 1, ss), (h, sh)], W * 4))
-                    s = e + 1
-                    continue
-                out.append(slab(st, s * ss + lo * BW, [(h, sh)], (hi - lo) * BW))
-                if is_k:
-                    for half in (0, 1):
-                        glo, ghi = max(lo, 8 * half), min(hi, 8 * half + 8)
-                        if glo < ghi:
-                            out.append(slab(st, s * ss + S0 + (half * 1024 + (glo & 7) * 8) * 2, [(h, sh), (2, 4096), (16, 128)],
-                                            (ghi - glo) * 16))
-                else:
-                    out.append(slab(st, s * ss + S0 + lo * 256, [(h, sh), (2, 4096)], (hi - lo) * 256))
-                s += 1
+            for s, n, off, inner, run in _store_pieces(W, from_token // 32, -(-n_tok // 32), is_k):
+                out.append(slab(st, s * ss + off, [(n, ss)] * (n > 0) + [(h, sh), *inner], run))
             out.append(slab(mfma.range_flags(st), 0, [], h * 4))
         if self.k_res_len:
             out.append(slab(self.k_res, 0, [(h, self.k_res.stride(1) * 2)], self.k_res_len * self.D * 2))
@@ -165,33 +173,19 @@ class KiviLayerCacheMF(KiviCacheBase):
     # ------------------------------------------------------------------ continuous batching
     def _admit_slabs(self, src: "KiviLayerCacheMF"):
         """Everything in use of a row of `src` (same geometry and lengths; its own super-block count and ring phase) -> this cache's
-        buffers.  The stores move in whole 32-token blocks as in _reorder_slabs(0) -- whole super-blocks as one slab with the
-        super-block index as a level, then the blocks in use of the last one with their scale / zero-point pieces; a partly filled V
-        block arrives with the source's clean tail -- every stride taken from each side's own store; the range words are replaced;
-        the fp16 K residual up to its length; the live window tokens rotated from the source's ring phase to this cache's in at
-        most three contiguous segments (token t: source row (s_src + t) mod rows -> row (s_dst + t) mod rows).  The ring row that
-        holds no live token is not written."""
-        h = self.nh_kv
-        W = mfma.sb_words(self.cfg.k_bits)
-        S0, BW = (W - 2048) * 4, (W - 2048) // 16 * 4          # byte offset of the scale region, bytes of codes per block
+        buffers.  The stores move as the pieces of _reorder_slabs(0), every super-block and head stride taken from each side's own
+        store (a partly filled V block arrives with the source's clean tail); the range words are replaced; the fp16 K residual up
+        to its length; the live window tokens rotated from the source's ring phase to this cache's in at most three contiguous
+        segments (token t: source row (s_src + t) mod rows -> row (s_dst + t) mod rows).  The ring row that holds no live token is
+        not written."""
+        h, W = self.nh_kv, mfma.sb_words(self.cfg.k_bits)
         out = []
         for st, sy, n_tok, is_k in ((self.kt, src.kt, self.k_quant_len, True), (self.vt, src.vt, self.v_quant_len, False)):
             heads = (h, st.stride(1) * 4, sy.stride(1) * 4)
             dss, sss = st.stride(2) * 4, sy.stride(2) * 4
-            full, hi = divmod(-(-n_tok // 32), 16)               # whole super-blocks, blocks in use of the next one
-            if full:
-                out.append(admit.slab(st, 0, sy, 0, [(full, dss, sss), heads], W * 4))
-            if hi:
-                d0, s0 = full * dss, full * sss
-                out.append(admit.slab(st, d0, sy, s0, [heads], hi * BW))
-                if is_k:
-                    for half in (0, 1):
-                        ghi = min(hi, 8 * half + 8) - 8 * half
-                        if ghi > 0:
-                            out.append(admit.slab(st, d0 + S0 + half * 2048, sy, s0 + S0 + half * 2048,
-                                                  [heads, (2, 4096, 4096), (16, 128, 128)], ghi * 16))
-                else:
-                    out.append(admit.slab(st, d0 + S0, sy, s0 + S0, [heads, (2, 4096, 4096)], hi * 256))
+            for s, n, off, inner, run in _store_pieces(W, 0, -(-n_tok // 32), is_k):
+                out.append(admit.slab(st, s * dss + off, sy, s * sss + off,
+                                      [(n, dss, sss)] * (n > 0) + [heads] + [(c, b, b) for c, b in inner], run))
             out.append(admit.slab(mfma.range_flags(st), 0, mfma.range_flags(sy), 0, [], h * 4))
         rowb = self.D * 2
         if self.k_res_len:

@@ -15,6 +15,7 @@ from typing import List, Tuple
 import torch
 
 from . import _lib
+from . import slabs as _slabs
 
 LENGTHS = ("k_quant_len", "k_res_len", "v_quant_len", "v_res_start", "v_res_len", "kv_seq_len")
 FLAGS = ("_attend_unfusable", "_softmax_unfusable", "_fused_unsupported")
@@ -22,28 +23,17 @@ FLAGS = ("_attend_unfusable", "_softmax_unfusable", "_fused_unsupported")
 
 def row_bytes(slabs) -> int:
     """Bytes the slabs of one row take in a snapshot buffer (every slab starts on a 16-byte boundary)."""
-    total = 0
-    for _, _, levels, nbytes in slabs:
-        for c, _ in levels:
-            nbytes *= c
-        total += -(-nbytes // 16) * 16
-    return total
+    return sum(-(-_slabs.row_bytes(s) // 16) * 16 for s in slabs)
 
 
 def run(slabs, B: int, buf: torch.Tensor, direction: int) -> None:
     """One kivi_cache_snapshot launch: gather the slabs of every row into `buf` (B, row bytes) uint8 (direction 0) or scatter them
     back (1)."""
-    slabs = [s for s in slabs if s[3] > 0 and all(n > 0 for n, _ in s[2])]
-    if not slabs:
-        return
-    assert len(slabs) <= _lib.REORDER_MAX_SLABS
-    arr = (_lib.ReorderSlab * len(slabs))()
-    for d, (base, rs, levels, nbytes) in zip(arr, slabs):
-        d.base, d.row_stride, d.run = base, rs, nbytes
-        for k, (n, st) in enumerate(levels):
-            d.n[k], d.stride[k] = n, st
-    _lib.check(_lib.load().kivi_cache_snapshot(arr, len(slabs), B, _lib.ptr(buf), buf.stride(0), direction, _lib.stream_ptr(buf)),
-               "kivi_cache_snapshot")
+    arrs = _slabs.arrays(slabs)
+    assert len(arrs) <= 1
+    for arr in arrs:
+        _lib.check(_lib.load().kivi_cache_snapshot(arr, len(arr), B, _lib.ptr(buf), buf.stride(0), direction, _lib.stream_ptr(buf)),
+                   "kivi_cache_snapshot")
 
 
 @dataclass

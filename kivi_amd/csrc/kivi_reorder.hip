@@ -2,32 +2,25 @@
 // names (include/kivi_hip.h, kivi_cache_reorder).  The caller describes WHAT moves -- for beam search only what was written after
 // the fork point, so the traffic of a step scales with the generated tokens, not with the context.
 //
-// One launch.  A workgroup owns (row group, chunk of one slab): the chunk is UC units (16 bytes, or 4 for slabs that are only
-// word-aligned) at the same offsets in every row of the group.  It reads idx of its group (an index outside the group is read as
-// the identity: such a row is left as it is, nothing outside the group is ever touched), marks the rows that some other row
-// sources, loads those rows' chunk into LDS, waits at a barrier and writes the rows whose idx differs from their own index.  Every
-// byte is read at most once and written at most once; identity rows that nobody sources are neither read nor written.  Chunks
-// of different workgroups are disjoint, so the reorder is in place without scratch memory or a second pass.
+// One launch over the slab walk of kivi_slab.h (units, chunks, the host preparation, the offsets of a unit).  This kernel's own is
+// the exchange through LDS.  A workgroup owns (row group, chunk of one slab): the chunk is UC units at the same offsets in every
+// row of the group.  It reads idx of its group (an index outside the group is read as the identity: such a row is left as it is,
+// nothing outside the group is ever touched), marks the rows that some other row sources, loads those rows' chunk into LDS, waits
+// at a barrier and writes the rows whose idx differs from their own index.  Every byte is read at most once and written at most
+// once; identity rows that nobody sources are neither read nor written.  Chunks of different workgroups are disjoint, so the
+// reorder is in place without scratch memory or a second pass.
 #include "kivi_common.h"
+#include "kivi_slab.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kLdsBytes = 65536;         // LDS per workgroup: group * UC 16-byte slots + 8 bytes of bookkeeping per row
 
-struct RSlab {
-    char* base;
-    int64_t rs, s0, s1, s2;
-    uint32_t n1, n2, upr;                // level counts 1 and 2, units per run
-    uint32_t units;                      // units per row (n0 * n1 * n2 * upr)
-    uint32_t chunk0;                     // first chunk (blockIdx.x) of this slab
-    uint32_t unit;                       // 16 or 4 bytes
-};
-
 struct RArgs {
-    RSlab s[KIVI_REORDER_MAX_SLABS];
+    KiviSlabs<1> slabs;
     const void* idx;
-    int ns, idx64, group, uc;
+    int idx64, group, uc;
 };
 
 __global__ __launch_bounds__(kThreads) void reorder_rows_kernel(const RArgs a) {
@@ -36,12 +29,8 @@ __global__ __launch_bounds__(kThreads) void reorder_rows_kernel(const RArgs a) {
     int* src = reinterpret_cast<int*>(lds + G * uc);
     int* need = src + G;
     const int64_t g0 = (int64_t)blockIdx.y * G;
-
-    // the slab of this chunk: the last one whose first chunk is <= blockIdx.x (constant indices: the descriptors stay in kernarg)
-    RSlab S = a.s[0];
-#pragma unroll
-    for (int i = 1; i < KIVI_REORDER_MAX_SLABS; ++i)
-        if (i < a.ns && blockIdx.x >= a.s[i].chunk0) S = a.s[i];
+    KiviSlab<1> S;
+    KIVI_SLAB_OF_CHUNK(S, a.slabs, blockIdx.x);
 
     for (int b = tid; b < G; b += kThreads) {
         const int64_t v = a.idx64 ? reinterpret_cast<const int64_t*>(a.idx)[g0 + b] : (int64_t)reinterpret_cast<const int*>(a.idx)[g0 + b];
@@ -57,29 +46,23 @@ __global__ __launch_bounds__(kThreads) void reorder_rows_kernel(const RArgs a) {
     const int k = tid & (uc - 1), rstep = kThreads / uc;
     const uint32_t u = (blockIdx.x - S.chunk0) * (uint32_t)uc + (uint32_t)k;
     const bool live = u < S.units;
+    const KiviSlabSide& e = S.side[0];
     int64_t off = 0;
-    if (live) {
-        uint32_t piece = u / S.upr;
-        const uint32_t w = u - piece * S.upr;
-        const uint32_t i2 = piece % S.n2;
-        piece /= S.n2;
-        const uint32_t i1 = piece % S.n1, i0 = piece / S.n1;
-        off = (int64_t)i0 * S.s0 + (int64_t)i1 * S.s1 + (int64_t)i2 * S.s2 + (int64_t)w * S.unit;
-    }
-    char* base = S.base + g0 * S.rs + off;
+    if (live) kivi_slab_offsets(S, u, S.unit, &off);
+    char* base = e.base + g0 * e.rs + off;
     if (S.unit == 16) {
         for (int r = tid / uc; r < G; r += rstep)
-            if (live && need[r]) lds[r * uc + k] = *reinterpret_cast<const u32x4*>(base + r * S.rs);
+            if (live && need[r]) lds[r * uc + k] = *reinterpret_cast<const u32x4*>(base + r * e.rs);
         __syncthreads();
         for (int b = tid / uc; b < G; b += rstep)
-            if (live && src[b] != b) *reinterpret_cast<u32x4*>(base + b * S.rs) = lds[src[b] * uc + k];
+            if (live && src[b] != b) *reinterpret_cast<u32x4*>(base + b * e.rs) = lds[src[b] * uc + k];
     } else {
         uint32_t* l32 = reinterpret_cast<uint32_t*>(lds);
         for (int r = tid / uc; r < G; r += rstep)
-            if (live && need[r]) l32[r * uc + k] = *reinterpret_cast<const uint32_t*>(base + r * S.rs);
+            if (live && need[r]) l32[r * uc + k] = *reinterpret_cast<const uint32_t*>(base + r * e.rs);
         __syncthreads();
         for (int b = tid / uc; b < G; b += rstep)
-            if (live && src[b] != b) *reinterpret_cast<uint32_t*>(base + b * S.rs) = l32[src[b] * uc + k];
+            if (live && src[b] != b) *reinterpret_cast<uint32_t*>(base + b * e.rs) = l32[src[b] * uc + k];
     }
 }
 
@@ -102,38 +85,7 @@ extern "C" int kivi_cache_reorder(const kivi_reorder_slab* slabs, int n_slabs, i
     a.group = group;
     a.uc = uc;
     int64_t chunks = 0;
-    for (int i = 0; i < n_slabs; ++i) {
-        const kivi_reorder_slab& s = slabs[i];
-        KIVI_REQUIRE(s.n[0] >= 0 && s.n[1] >= 0 && s.n[2] >= 0 && s.run >= 0, KIVI_EINVAL, "kivi_cache_reorder: slab %d: negative count", i);
-        if (s.n[0] == 0 || s.n[1] == 0 || s.n[2] == 0 || s.run == 0) continue;       // nothing to move
-        const uint64_t bits = (uint64_t)(uintptr_t)s.base | (uint64_t)s.row_stride | (uint64_t)s.stride[0] | (uint64_t)s.stride[1] |
-                              (uint64_t)s.stride[2] | (uint64_t)s.run;
-        KIVI_REQUIRE(s.base && bits % 4 == 0, KIVI_EINVAL,
-                     "kivi_cache_reorder: slab %d: null base, or base / strides / run not multiples of 4 bytes", i);
-        const uint32_t unit = bits % 16 == 0 ? 16 : 4;
-        const int64_t upr = s.run / unit;
-        int64_t units = 1;
-        bool fits = true;
-        for (int64_t f : {s.n[0], s.n[1], s.n[2], upr}) {
-            fits = fits && f < (1LL << 31) && units * f < (1LL << 31);
-            units = fits ? units * f : 1;
-        }
-        KIVI_REQUIRE(fits, KIVI_EINVAL, "kivi_cache_reorder: slab %d: 2^31 units per row or more", i);
-        RSlab& d = a.s[a.ns++];
-        d.base = (char*)s.base;
-        d.rs = s.row_stride;
-        d.s0 = s.stride[0];
-        d.s1 = s.stride[1];
-        d.s2 = s.stride[2];
-        d.n1 = (uint32_t)s.n[1];
-        d.n2 = (uint32_t)s.n[2];
-        d.upr = (uint32_t)upr;
-        d.units = (uint32_t)units;
-        d.chunk0 = (uint32_t)chunks;
-        d.unit = unit;
-        chunks += (units + uc - 1) / uc;
-        KIVI_REQUIRE(chunks < (1LL << 31), KIVI_EINVAL, "kivi_cache_reorder: grid too large");
-    }
+    if (const int rc = kivi_prepare_slabs("kivi_cache_reorder", KIVI_EINVAL, slabs, n_slabs, uc, &a.slabs, &chunks)) return rc;
     if (chunks == 0) return 0;
     const size_t lds = (size_t)group * uc * 16 + (size_t)group * 8;
     KIVI_LAUNCH_LDS(reorder_rows_kernel, dim3((unsigned)chunks, (unsigned)(B / group)), dim3(kThreads), lds, (hipStream_t)stream, a);

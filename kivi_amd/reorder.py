@@ -9,11 +9,10 @@ copy would write.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
+from . import slabs as _slabs
 
 
 def _span(lo: int, hi: int, size: int):
@@ -50,26 +49,11 @@ def check_idx(idx: torch.Tensor, B: int, group: int, device, check_values: bool 
 
 def run(slabs, B: int, group: int, idx: torch.Tensor) -> None:
     """One kivi_cache_reorder call per KIVI_REORDER_MAX_SLABS slabs (they are disjoint, so the calls are independent)."""
-    slabs = [s for s in slabs if s[3] > 0 and all(n > 0 for n, _ in s[2])]
-    lib = _lib.load()
-    stream = _lib.stream_ptr(idx)
-    for i in range(0, len(slabs), _lib.REORDER_MAX_SLABS):
-        part = slabs[i: i + _lib.REORDER_MAX_SLABS]
-        arr = (_lib.ReorderSlab * len(part))()
-        for d, (base, rs, levels, nbytes) in zip(arr, part):
-            d.base, d.row_stride, d.run = base, rs, nbytes
-            for k, (n, st) in enumerate(levels):
-                d.n[k], d.stride[k] = n, st
-        _lib.check(lib.kivi_cache_reorder(arr, len(part), B, group, _lib.ptr(idx), idx.element_size(), stream),
+    for arr in _slabs.arrays(slabs):
+        _lib.check(_lib.load().kivi_cache_reorder(arr, len(arr), B, group, _lib.ptr(idx), idx.element_size(), _lib.stream_ptr(idx)),
                    "kivi_cache_reorder")
 
 
 def moved_bytes(slabs, rows: int) -> int:
     """Bytes read + written when `rows` rows move (the algorithmic traffic of a reorder)."""
-    per_row = 0
-    for _, _, levels, nbytes in slabs:
-        n = nbytes
-        for c, _ in levels:
-            n *= c
-        per_row += n
-    return 2 * rows * per_row
+    return 2 * rows * sum(map(_slabs.row_bytes, slabs))

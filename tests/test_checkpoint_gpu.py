@@ -155,6 +155,57 @@ def test_restore_leaves_the_packed_stores_alone(shape):
         assert not mfma.range_flags(st).any() and not torch.equal(after[main:], before[i][main:])
 
 
+def _slab_views(layer, slabs, rows):
+    """Byte copies of the layer's allocations, and torch views (rows, n0, n1, n2, run) into them of what the slabs name."""
+    mems = [(t.untyped_storage().data_ptr(), _flat(t)) for t in (layer.kt, layer.vt, layer.k_res, layer.v_res)]
+    views = []
+    for base, rs, levels, run in slabs:
+        p0, mem = next((p, m) for p, m in mems if p <= base < p + m.numel())
+        views.append(torch.as_strided(mem, (rows, *[n for n, _ in levels], run), (rs, *[st for _, st in levels], 1), base - p0))
+    return [m for _, m in mems], views
+
+
+@pytest.mark.parametrize("from_token", [200, 0])
+def test_snapshot_of_levelled_slabs(from_token):
+    """checkpoint() hands kivi_cache_snapshot flat slabs only (residual, window, range words).  Here the entry point gets what a
+    reorder of a matrix-pipe cache of 530 tokens moves (B = 2, 2 kv heads).  From token 200: the 3-level K scale pieces, the
+    2-level V scale runs, the range words (word-wide), flat slabs of a full chunk and a partial one (codes, window).  From token 0:
+    the whole super-blocks under a head level, full chunks of a slab that is not flat.  The gathered buffer is what torch reads at
+    the slabs' addresses, in the buffer-row format; scattered into a cache with other strides, the cache's allocations change in
+    those bytes and nowhere else."""
+    from kivi_amd import checkpoint
+    from kivi_amd.attention import KiviConfig, make_layer_cache
+    rows, T = 2, 530
+
+    def cache(cap, seed):
+        lc = make_layer_cache(KiviConfig(2, 2, 32, 32), rows, NH_KV, 128, cap, "cuda", num_heads=NH_KV)
+        lc.prefill(make_kv(seed, rows, NH_KV, T, 128).cuda(), make_kv(seed + 1, rows, NH_KV, T, 128).cuda())
+        return lc
+    src, dst = cache(T + 8, 1), cache(2100, 3)
+    slabs, into = src._reorder_slabs(from_token), dst._reorder_slabs(from_token)
+    shape = [([n for n, _ in s[2]], s[3]) for s in slabs]
+    assert shape == [([n for n, _ in s[2]], s[3]) for s in into] and src.kt.stride(0) != dst.kt.stride(0)
+    units = [(n, n[0] * n[1] * n[2] * run // 16) for n, run in shape if run % 16 == 0]
+    assert any(run % 16 for _, run in shape) and any(n[1:] == [1, 1] and 1024 < u < 2048 for n, u in units)      # word-wide; flat
+    assert any(min(n) > 1 for n, _ in units) if from_token else any(n[1] > 1 and u >= 1024 for n, u in units)
+    before, views = _slab_views(src, slabs, rows)
+    pieces = [v.reshape(rows, -1) for v in views]
+    buf = torch.zeros((rows, checkpoint.row_bytes(slabs)), dtype=torch.uint8, device="cuda")
+    checkpoint.run(slabs, rows, buf, 0)
+    assert torch.equal(buf, torch.cat([torch.nn.functional.pad(x, (0, -x.shape[1] % 16)) for x in pieces], 1))
+    want, views = _slab_views(dst, into, rows)                 # copies from before the scatter: the slabs' bytes are replaced
+    off = 0
+    for v, x in zip(views, pieces):
+        v.copy_(x.reshape(v.shape))
+        assert torch.equal(buf[:, off: off + x.shape[1]], x)
+        off += -(-x.shape[1] // 16) * 16
+    checkpoint.run(into, rows, buf, 1)
+    for t, w in zip((dst.kt, dst.vt, dst.k_res, dst.v_res), want):
+        assert torch.equal(_flat(t), w)
+    for t, b in zip((src.kt, src.vt, src.k_res, src.v_res), before):
+        assert torch.equal(_flat(t), b)                        # the source was only read
+
+
 @pytest.mark.parametrize("shape", [LAYOUTS[1], LAYOUTS[5]], ids=[IDS[1], IDS[5]])
 def test_two_checkpoints_and_staleness(shape):
     ratio, R, D = shape[2], shape[4], shape[5]
