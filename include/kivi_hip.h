@@ -29,6 +29,8 @@
  *                               cache: kivi_kt_pack, kivi_vt_pack, kivi_vt_pack_at, kivi_kt_relayout, kivi_vt_relayout
  *               beam search:    kivi_cache_reorder (in-place row reorder of either cache layout, from a fork point on)
  *               admission:      kivi_cache_admit (rows of one cache into chosen rows of another, living one: continuous batching)
+ *               rebase:         kivi_mf_store_shift (the blocks of a packed store moved towards token 0 in place: a living cache
+ *                               drops its leading tokens)
  *               rollback:       kivi_cache_snapshot (the fp16 residual / window and range words of a cache into a flat buffer and
  *                               back: checkpoint and restore of either cache layout)
  *               sampling:       kivi_sample (temperature / top-k / top-p / min-p draw of one token per row, Philox RNG state on
@@ -588,6 +590,24 @@ typedef struct kivi_admit_slab {
 } kivi_admit_slab;
 int kivi_cache_admit(const kivi_admit_slab* slabs, int n_slabs, int n_rows, const void* rows, int rows_bytes, int B,
                      kivi_stream_t stream);
+/*
+ * kivi_mf_store_shift: the 32-token blocks of ONE packed store of the matrix-pipe layout (KT: is_k != 0, or VT; 2- or 4-bit
+ * super-blocks) moved shift_blocks blocks towards token 0, in place, for all B rows and nh_kv heads (rebase of a living cache,
+ * DESIGN.md section 17): block j <- block j + shift_blocks for j in [0, n_blocks - shift_blocks), then blocks
+ * [n_blocks - shift_blocks, n_blocks) zeroed ("never written slots are zero" holds afterwards).  n_blocks: the blocks in use before
+ * the call.  A block is its code words plus its scale and zero-point pieces, wherever its super-block keeps them; a partly filled
+ * last V block moves whole.  Every code, scale and zero point keeps its bits.  store / st_sb / st_sh / st_ss (words) / range: as
+ * for kivi_kt_pack.  The RANGE WORDS are recomputed, not kept: the caller zeroes the store's B * nh_kv words on the same stream
+ * before the call, and the launch marks them from the scales it moves -- the words of a store written from the kept tokens alone
+ * (nothing kept: zero).  One launch, no LDS, no scratch, no second copy of the store: a thread owns one 16-byte unit position of a
+ * block for one (row, head) over the whole block range, so every byte is touched by one thread only, in program order, destination
+ * below source (kivi_amd/csrc/kivi_shift.hip).
+ * Before anything is enqueued: KIVI_EINVAL for bits not 2 or 4, B outside [1, 65535], nh_kv < 1, n_blocks < 0, shift_blocks outside
+ * [0, n_blocks], a null store or range, strides too small for n_blocks; KIVI_EALIGN for a base or stride that is not a multiple of
+ * 16 bytes.  shift_blocks == 0 or n_blocks == 0: nothing is enqueued, returns 0.
+ */
+int kivi_mf_store_shift(void* store, int64_t st_sb, int64_t st_sh, int64_t st_ss, void* range, int bits, int is_k, int B, int nh_kv,
+                        int64_t n_blocks, int64_t shift_blocks, kivi_stream_t stream);
 /*
  * kivi_sample: one token per row drawn from (B, V) logits the way transformers' do_sample path does:
  * s = float(logit) / temperature; keep s >= the top_k-th largest s (ties kept; top_k = 0 or >= V: off); renormalise over those and

@@ -33,7 +33,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from . import _lib, _tuning, admit, checkpoint, reorder
+from . import _lib, _tuning, admit, checkpoint, rebase, reorder
 from ._lib import KiviUnsupported, check_mask_size, mask_arg, out_arg, unit_rows
 from .quant import fused, matmul, new_pack
 
@@ -113,7 +113,7 @@ class KiviPerformanceWarning(UserWarning):
 class KiviCacheBase:
     """What the two layouts of a layer's cache (KiviLayerCache here, KiviLayerCacheMF in cache_mf.py) share: the geometry, the six
     lengths of the state machine, the scratch of a decode step, and everything that follows from them alone.  A layout adds its
-    buffers (`_BUFFERS`, `reserve`, `_own_buffers`, `_reorder_slabs`, `_checkpoint_slabs`, `_admit_slabs`, `prefill`), the readers of the reference layout
+    buffers (`_BUFFERS`, `reserve`, `_own_buffers`, `_reorder_slabs`, `_checkpoint_slabs`, `_admit_slabs`, `_rebase_buffers`, `prefill`), the readers of the reference layout
     (`k_quant_reference_layout`, `v_quant_views`, `v_res_view`) and its steps (`decode_step`, `extend`)."""
 
     def __init__(self, cfg: KiviConfig, batch: int, num_kv_heads: int, head_dim: int, max_len: int, dtype):
@@ -232,6 +232,43 @@ class KiviCacheBase:
         self._void_checkpoints()          # a row holds another request now: no rollback across an admission
         return self
 
+    # ------------------------------------------------------------------ rebase
+    @property
+    def rebase_quantum(self) -> int:
+        """The drops rebase_ takes are multiples of this: lcm(residual_length, 32)."""
+        return rebase.quantum(self.cfg.residual_length)
+
+    @property
+    def rebase_limit(self) -> int:
+        """The largest drop rebase_ takes now: only packed tokens leave, and K and V lose the same ones."""
+        return min(self.k_quant_len, self.v_quant_len)
+
+    def check_rebase(self, drop) -> None:
+        """Raise ValueError when rebase_(drop) would refuse (nothing runs on a device)."""
+        rebase.check_drop(drop, self.rebase_quantum, self.rebase_limit)
+
+    def rebase_(self, drop: int):
+        """The first `drop` tokens of every row leave the cache, in place: token t becomes token t - drop.  For rows whose first
+        `drop` tokens are masked (leading pads) every later step computes what it would have computed over a
+        cache built from the kept tokens alone, and the cache IS that cache: 9-tuple members and range words are bit-identical to
+        it.  `drop`: a multiple of `rebase_quantum`, at most `rebase_limit`.  k_quant_len, v_quant_len and kv_seq_len fall by `drop`;
+        the fp16 K residual, the fp16 V window and their lengths (v_res_start too) are untouched; capacity, data pointers and the
+        fusion flags stay, the native descriptor's state array is brought in line.  Checkpoints issued so far become stale, as
+        after a reorder; tuples issued before are stale: take as_tuple() again.  `drop == 0` does nothing and voids nothing.
+        ValueError before anything runs on a device for a drop that is not an int, is negative, is not a multiple of the quantum
+        or lies above the limit."""
+        self.check_rebase(drop)
+        if drop == 0:
+            return self
+        self._rebase_buffers(drop)
+        self.k_quant_len -= drop
+        self.v_quant_len -= drop
+        self.kv_seq_len -= drop
+        if self._native is not None:
+            self._store_state(self._native[1])
+        self._void_checkpoints()          # the packed stores no longer hold what a checkpoint continues
+        return self
+
     # ------------------------------------------------------------------ checkpoint / rollback (DESIGN.md section 13)
     def _forget_checkpoints(self) -> None:
         """A cache of its own (new, cloned, index_selected): no checkpoint issued so far belongs to it."""
@@ -270,13 +307,15 @@ class KiviCacheBase:
             raise ValueError(f"the checkpoint comes from another geometry or layout: {ck.geometry}, this cache is {self._geometry()}")
         if ck.owner is not self._ck_owner:
             raise ValueError("the checkpoint comes from another cache (a clone or index_select starts without checkpoints)")
-        if ck.kv_seq_len > self.kv_seq_len:
-            raise ValueError(f"the checkpoint was taken at kv length {ck.kv_seq_len}, beyond the cache's {self.kv_seq_len}")
-        for serial, low in self._ck_lows:
-            if serial >= ck.serial and low < ck.kv_seq_len:
-                what = "reordered or prefilled again" if low < 0 else f"restored to kv length {low}"
-                raise ValueError(f"stale checkpoint: taken at kv length {ck.kv_seq_len}, the cache has since been {what}, so the "
-                                 f"packed stores beyond that point no longer hold what the checkpoint continues")
+        # a voided checkpoint is stale whatever the lengths (a rebase shortens the cache: "beyond" would name the symptom)
+        for voided in (True, False):
+            for serial, low in self._ck_lows:
+                if serial >= ck.serial and low < ck.kv_seq_len and (low < 0) == voided:
+                    what = "reordered, admitted into, rebased or prefilled again" if low < 0 else f"restored to kv length {low}"
+                    raise ValueError(f"stale checkpoint: taken at kv length {ck.kv_seq_len}, the cache has since been {what}, so the "
+                                     f"packed stores beyond that point no longer hold what the checkpoint continues")
+            if voided and ck.kv_seq_len > self.kv_seq_len:
+                raise ValueError(f"the checkpoint was taken at kv length {ck.kv_seq_len}, beyond the cache's {self.kv_seq_len}")
 
     def restore_(self, ck):
         """Back to the state checkpoint() saw, exactly (the 9-tuple, the range words and every later step are bit-identical to a
@@ -456,6 +495,29 @@ class KiviLayerCache(KiviCacheBase):
             out.append(admit.slab(self.v_res, self.v_res_start * rowb, src.v_res, src.v_res_start * rowb,
                                   [(h, self.v_res.stride(1) * 2, src.v_res.stride(1) * 2)], self.v_res_len * rowb))
         return out
+
+    def _rebase_buffers(self, drop: int) -> None:
+        """The packed K and V from token `drop` on -> token 0, into the same buffers (the UNTUNED path, as extend: torch ops on the
+        GPU).  Source and destination overlap, so the part that moves is cloned first: K through the reference layout (the pages
+        gathered, sliced on whole words -- `drop` is a multiple of 32 tokens -- and written back page by page), the V triple row
+        by row.  What lies beyond the new lengths is not touched: nothing reads it."""
+        kf, g = 32 // self.cfg.k_bits, self.cfg.group_size
+        if self.k_quant_len > drop:
+            kc, ks, km = self.k_quant_reference_layout()
+            self._write_k_pages(kc[..., drop // kf:].clone(), ks[..., drop // g:].clone(), km[..., drop // g:].clone())
+        if self.v_quant_len > drop:
+            for x in (self.v_code, self.v_scale, self.v_mn):
+                x[:, :, : self.v_quant_len - drop].copy_(x[:, :, drop: self.v_quant_len].clone())
+
+    def _write_k_pages(self, kc: torch.Tensor, ks: torch.Tensor, km: torch.Tensor) -> None:
+        """Packed K in the reference layout (B, nh_kv, D, T / ...) -> the pages, from token 0."""
+        kf, g, P = 32 // self.cfg.k_bits, self.cfg.group_size, self.page_tokens
+        T = kc.shape[-1] * kf
+        for p in range((T + P - 1) // P):
+            n = min(P, T - p * P)
+            self.k_code[:, :, p, :, : n // kf].copy_(kc[..., p * P // kf: (p * P + n) // kf])
+            self.k_scale[:, :, p, :, : n // g].copy_(ks[..., p * P // g: (p * P + n) // g])
+            self.k_mn[:, :, p, :, : n // g].copy_(km[..., p * P // g: (p * P + n) // g])
 
     def _checkpoint_slabs(self, state=None):
         """What steps overwrite in place, at the lengths `state` (default: the current ones): the live rows of the fp16 K residual and
@@ -860,14 +922,9 @@ class KiviLayerCache(KiviCacheBase):
         ref = vfull if vfull is not None else kfull
         B, nh_kv, _, D = ref.shape
         self = cls(cfg, B, nh_kv, D, max_len, ref.device, ref.dtype)
-        kf, g, P = 32 // cfg.k_bits, cfg.group_size, self.page_tokens
         if kc is not None:
-            self.k_quant_len = kc.shape[-1] * kf
-            for p in range((self.k_quant_len + P - 1) // P):
-                n = min(P, self.k_quant_len - p * P)
-                self.k_code[:, :, p, :, : n // kf].copy_(kc[..., p * P // kf: (p * P + n) // kf])
-                self.k_scale[:, :, p, :, : n // g].copy_(ks[..., p * P // g: (p * P + n) // g])
-                self.k_mn[:, :, p, :, : n // g].copy_(km[..., p * P // g: (p * P + n) // g])
+            self.k_quant_len = kc.shape[-1] * (32 // cfg.k_bits)
+            self._write_k_pages(kc, ks, km)
         if vc is not None:
             self.v_quant_len = vc.shape[2]
             self.v_code[:, :, : self.v_quant_len].copy_(vc)

@@ -25,7 +25,7 @@ import math
 
 import torch
 
-from . import _lib, _tuning, admit
+from . import _lib, _tuning, admit, rebase
 from ._lib import check_mask_size, mask_arg, out_arg, rows16
 from .cache import KiviCacheBase, KiviConfig, KiviLayerCache
 from .quant import matmul, mfma, new_pack
@@ -199,6 +199,14 @@ class KiviLayerCacheMF(KiviCacheBase):
             out.append(admit.slab(self.v_res, d * rowb, src.v_res, s * rowb, ring, n * rowb))
             t += n
         return out
+
+    # ------------------------------------------------------------------ rebase
+    def _rebase_buffers(self, drop: int) -> None:
+        """Both stores `drop` / 32 blocks towards token 0, in place: one kivi_mf_store_shift per store over the blocks in use (K
+        groups; V tokens, a partly filled last block whole), the vacated blocks zeroed, the range words recomputed from the
+        scales kept."""
+        for st, n_tok, is_k, bits in ((self.kt, self.k_quant_len, True, self.cfg.k_bits), (self.vt, self.v_quant_len, False, self.cfg.v_bits)):
+            rebase.shift_store(st, bits, is_k, -(-n_tok // 32), drop // 32)
 
     def _checkpoint_slabs(self, state=None):
         """What steps overwrite in place: the fp16 K residual up to its length (`state`: the lengths to use, default the current ones),

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import glob
 import json
+import math
 import os
 from types import SimpleNamespace
 from typing import List, Optional
@@ -233,11 +234,35 @@ class LlamaForCausalLM_KIVI(nn.Module):
         return logits, [c.as_tuple() for c in caches]
 
     def generate_continuous(self, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
-                            pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False):
+                            pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False, compact: Optional[int] = None):
         """Continuous batching over a queue of requests (kivi_amd/serving.py: generate_continuous): a batch of `batch_size` rows whose
-        finished rows are taken over by the waiting prompts.  -> the generated tokens of every request, in request order."""
+        finished rows are taken over by the waiting prompts.  -> the generated tokens of every request, in request order.
+        `compact`: None, or the fewest leading tokens worth dropping from the living caches between two steps (rebase_)."""
         from .serving import generate_continuous
-        return generate_continuous(self, prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, graphed)
+        return generate_continuous(self, prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, graphed, compact)
+
+    # ------------------------------------------------------------------ rebase (DESIGN.md section 17)
+    @classmethod
+    def rebase_quantum(cls, past_key_values) -> int:
+        """The drops rebase_ takes are multiples of this (every layer's KiviCacheBase.rebase_quantum: lcm(residual_length, 32))."""
+        return math.lcm(*(c.rebase_quantum for c in cls._layer_caches(past_key_values, "rebase_quantum")))
+
+    @classmethod
+    def rebase_limit(cls, past_key_values) -> int:
+        """The largest drop rebase_ takes now (the smallest KiviCacheBase.rebase_limit of the layers)."""
+        return min(c.rebase_limit for c in cls._layer_caches(past_key_values, "rebase_limit"))
+
+    @classmethod
+    def rebase_(cls, past_key_values, drop: int) -> List:
+        """The first `drop` tokens of every row leave every layer's living cache, in place (KiviCacheBase.rebase_): what a batch
+        whose rows all start with at least `drop` pads does to stop paying for them.  Returns fresh tuples of the same caches; go
+        on with a 2D mask without its first `drop` columns (positions come from the mask: they do not change).  ValueError before
+        any cache is touched for plain 9-tuples or a drop some layer refuses (not an int, negative, not a multiple of
+        rebase_quantum, above rebase_limit)."""
+        caches = cls._layer_caches(past_key_values, "rebase_")
+        for c in caches:
+            c.check_rebase(drop)
+        return [c.rebase_(drop).as_tuple() for c in caches]
 
     # ------------------------------------------------------------------ scoring given tokens (DESIGN.md section 14)
     _HEAD_SLAB = 4096            # rows of hidden states per lm_head call of score(): logits exist for one slab at a time

@@ -14,6 +14,11 @@ The policy is fixed (tests restate it):
   * Finished rows take the next waiting requests, lowest row first and in FIFO order, through ONE admit_ at the current length.
     An admitted request's first token is picked from its prompt logits and replaces the row's token before the step; should that
     token already finish the request, the row is free again and the admission repeats at the same length.
+  * `compact=n` (None: never): after the tokens were recorded and before the admissions,
+    room = min(leading pads of the live rows (no live row: L), L - the longest waiting prompt (none: 0), rebase_limit) and
+    drop = room rounded down to rebase_quantum; if drop >= n, model.rebase_ drops the first `drop` tokens of every row, the 2D mask
+    loses its first `drop` columns and L falls by `drop`.  The leading pads are kept on the host: admission length - prompt
+    length - the drops since.
   * Rows with nothing to do feed `pad_token_id`.  The call ends when every request is done: no step runs after the last pick.
   * Token i of a request is draw i of its own seed with Philox stream 0, whichever row and step it lands on:
     the first token is drawn by a RowSampler of the admitted rows alone, then the batch's RowSampler row is bound with
@@ -33,9 +38,12 @@ def _positive_int(x) -> bool:
     return isinstance(x, int) and not isinstance(x, bool) and x >= 1
 
 
-def check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, vocab_size: Optional[int] = None):
+def check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, vocab_size: Optional[int] = None,
+                    compact: Optional[int] = None):
     """-> (prompts as 1-D int64 CPU tensors, max_new_tokens per request, bound SamplingParams per request or None); ValueError for
     anything generate_continuous cannot serve (no device work)."""
+    if compact is not None and not _positive_int(compact):
+        raise ValueError(f"compact has to be None or a positive integer (the fewest tokens worth reclaiming), got {compact!r}")
     if not isinstance(prompts, (list, tuple)) or not prompts:
         raise ValueError("prompts has to be a non-empty list of token id sequences")
     seqs = [torch.as_tensor(p, dtype=torch.long).flatten().cpu() for p in prompts]
@@ -70,17 +78,29 @@ def check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token
     return seqs, limits, params
 
 
+def compact_drop(leads, L: int, longest_waiting: int, limit: int, quantum: int) -> int:
+    """The tokens to drop from the front of every row of living caches at length L: `leads`, the leading pads of the LIVE rows (none:
+    the whole length counts); `longest_waiting`, the longest prompt still in the queue (0: none), which has to fit into the new
+    length; `limit` and `quantum`, what the caches take (rebase_limit, rebase_quantum)."""
+    room = min(min(leads, default=L), L - longest_waiting, limit)
+    return max(room, 0) // quantum * quantum
+
+
 @torch.no_grad()
 def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
-                        pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False) -> List[torch.Tensor]:
+                        pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False,
+                        compact: Optional[int] = None) -> List[torch.Tensor]:
     """`prompts`: a list of token id sequences, possibly more than `batch_size`; `max_new_tokens`: an int or one per request;
     `sampling`: None (greedy), one SamplingParams, or one per request.  -> the generated tokens of every request as 1-D int64
     tensors, in request order, ending with `eos_token_id` where it was produced.  The policy: the module docstring.
     `graphed=True`: the steps go through decode_graphed(..., attention_mask=, sampling=) over the same living caches; the 2D mask
     with the replaced rows is passed again after an admission and the captured step is replayed, not captured again (unless the
-    mask buffer has to grow, or the first pad of the call arrives with an admission).  Same tokens as graphed=False."""
+    mask buffer has to grow, or the first pad of the call arrives with an admission).  Same tokens as graphed=False.
+    `compact`: None -- the caches' length only grows --, or the fewest tokens worth reclaiming: at the top of every iteration the
+    leading tokens no live row and no waiting prompt needs are dropped from the living caches (model.rebase_), if there are at least
+    that many."""
     prompts, limits, params = check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling,
-                                              model.config.vocab_size)
+                                              model.config.vocab_size, compact)
     pad = 0 if pad_token_id is None else pad_token_id
     N, device = len(prompts), model.lm_head.weight.device
     B = min(batch_size, N)
@@ -97,6 +117,7 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
     mask2d = torch.ones((B, 2 * L + 64), dtype=torch.long, device=device)      # column t: 1 = cache token t of the row is real
     mask2d[:, :L] = mask
     owner: List[Optional[int]] = list(range(B))                                # the request of every row (None: nothing to do)
+    lead = [L - prompts[r].numel() for r in range(B)]                          # leading pads of every row (host side, no device read)
     out: List[List[int]] = [[] for _ in range(N)]
     waiting = B
 
@@ -110,6 +131,15 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
         for b, t in enumerate(tok.view(-1).tolist()):                          # the one synchronisation of a step
             if owner[b] is not None:
                 record(b, t)
+        if compact is not None:
+            drop = compact_drop([lead[b] for b in range(B) if owner[b] is not None], L,
+                                max((prompts[r].numel() for r in range(waiting, N)), default=0),
+                                model.rebase_limit(pasts), model.rebase_quantum(pasts))
+            if drop >= compact:
+                pasts = model.rebase_(pasts, drop)
+                mask2d = torch.cat([mask2d[:, drop:], torch.ones_like(mask2d[:, :drop])], dim=1)
+                L -= drop
+                lead = [n - drop for n in lead]
         while waiting < N and None in owner:
             rows = [b for b in range(B) if owner[b] is None][: N - waiting]
             reqs = list(range(waiting, waiting + len(rows)))
@@ -121,6 +151,7 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
             tok[rows] = first
             for b, r, t in zip(rows, reqs, first.view(-1).tolist()):
                 owner[b] = r
+                lead[b] = L - prompts[r].numel()
                 if sampler is not None:
                     sampler.set_row(b, params[r], draw_index=1)
                 record(b, t)

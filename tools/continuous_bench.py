@@ -1,7 +1,7 @@
 """End to end: generate_continuous against static waves on a Llama-shaped model with random weights (the recipe of
 examples/mem_spd_test.py: Llama-2-7B architecture, k = v = 2 bit, g = 32, R = 32; the tokens mean nothing, time does).
 
-    python tools/continuous_bench.py [--requests 96] [--batch 32] [--reps 3]
+    python tools/continuous_bench.py [--requests 96] [--batch 32] [--reps 3] [--compact N [N ...]]
 
 Requests: prompt lengths uniform in [32, 160]; output lengths 8 + floor(Exp(mean 96)), capped at 512 -- a skewed distribution (the
 median is ~75 tokens, the longest of a wave of 32 is typically beyond 300); numpy seed 0.  No EOS: every request runs to its length.
@@ -9,7 +9,11 @@ median is ~75 tokens, the longest of a wave of 32 is typically beyond 300); nump
   continuous     generate_continuous(batch_size=batch), eager and graphed: finished rows take the waiting requests.
 Tokens per second count the tokens the requests asked for, over the wall time of the whole queue (host clock around work that ends
 in a device synchronise).  One warm-up of every mode, then `reps` repetitions with the modes alternating; the spread is printed.
-The admission share is measured in a run of its own: the wall time inside admit_ (synchronised on both sides) over the total."""
+The admission share is measured in a run of its own: the wall time inside admit_ (synchronised on both sides) over the total.
+`--compact N [N ...]`: the modes are generate_continuous with compact=None -- the behaviour without it, the
+comparison -- and with compact=N for every N given, eager and graphed, alternating; no static waves.  Per mode also the decode steps,
+the kv length at the end and the number of rebases (host-side counters around model methods, no synchronisation); the share of time
+in rebase_ comes from a synchronised run of its own per N, like the admission share."""
 import argparse
 import json
 import os
@@ -33,6 +37,8 @@ def main():
     ap.add_argument("--heads", type=int, default=32)
     ap.add_argument("--intermediate", type=int, default=11008)
     ap.add_argument("--vocab", type=int, default=32000)
+    ap.add_argument("--compact", type=int, nargs="+", default=None, metavar="N",
+                    help="compare generate_continuous(compact=None) with compact=N for every N (no static waves)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     cfg = SimpleNamespace(hidden_size=args.hidden, num_attention_heads=args.heads, num_key_value_heads=args.heads,
@@ -63,13 +69,15 @@ def main():
             steps += n
         return steps
 
-    def continuous(graphed):
-        out = model.generate_continuous(prompts, limits, B, graphed=graphed)
+    def continuous(graphed, compact=None):
+        out = model.generate_continuous(prompts, limits, B, graphed=graphed, compact=compact)
         assert [o.numel() for o in out] == limits
         return None
 
     modes = [("static waves (generate)", static_waves), ("continuous, eager", lambda: continuous(False)),
              ("continuous, graphed", lambda: continuous(True))]
+    if args.compact:
+        return compact_modes(args, model, continuous, asked)
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -112,6 +120,74 @@ def main():
         ts = times[name]
         res[name] = {"seconds": [round(t, 3) for t in ts], "median_seconds": round(sorted(ts)[len(ts) // 2], 3),
                      "tokens_per_s": round(asked / sorted(ts)[len(ts) // 2], 1)}
+    print(json.dumps(res))
+
+
+def compact_modes(args, model, continuous, asked):
+    """--compact: compact=None against compact=N, eager and graphed (see the module docstring)."""
+    seen = {"steps": 0, "rebases": 0, "dropped": 0, "last": 0}
+    forward_, graphed_, rebase_ = model._forward, model.decode_graphed, model.rebase_
+
+    def forward(ids, past=None, *a, **k):
+        if past is not None:
+            seen["steps"] += 1
+            seen["last"] = past[0].layer.kv_seq_len + 1
+        return forward_(ids, past, *a, **k)
+
+    def decode_graphed(tok, past, position, steps, *a, **k):
+        seen["steps"] += steps
+        seen["last"] = past[0].layer.kv_seq_len + steps
+        return graphed_(tok, past, position, steps, *a, **k)
+
+    def rebase(past, drop):
+        seen["rebases"] += 1
+        seen["dropped"] += drop
+        return rebase_(past, drop)
+    model._forward, model.decode_graphed, model.rebase_ = forward, decode_graphed, rebase
+    modes = [(f"{'graphed' if g else 'eager'}, compact={c}", g, c) for c in [None] + list(args.compact) for g in (False, True)]
+    runs = {name: [] for name, _, _ in modes}
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.time()
+        fn()
+        torch.cuda.synchronize()
+        return time.time() - t0
+    for rep in range(args.reps + 1):                       # repetition 0 warms every mode up
+        for name, g, c in modes:
+            seen.update(steps=0, rebases=0, dropped=0, last=0)
+            t = timed(lambda: continuous(g, c))
+            if rep:
+                runs[name].append((t, dict(seen)))
+    res = {"requests": args.requests, "batch": args.batch, "tokens_asked_for": asked, "repetitions": args.reps, "layers": args.layers}
+    for name, _, _ in modes:
+        ts = sorted(t for t, _ in runs[name])
+        med, counters = ts[len(ts) // 2], runs[name][0][1]
+        res[name] = {"seconds": [round(t, 3) for t, _ in runs[name]], "median_seconds": round(med, 3), "tokens_per_s": round(asked / med, 1),
+                     "spread": round((ts[-1] - ts[0]) / med, 3), "steps": counters["steps"], "final_kv_length": counters["last"],
+                     "rebases": counters["rebases"], "tokens_dropped": counters["dropped"]}
+    # the share of rebase_ (and admit_), in synchronised runs of their own
+    admit_ = model.admit_
+    for c in args.compact:
+        spent = {"rebase": 0.0, "admit": 0.0}
+
+        def synced(fn, key):
+            def run(*a, **k):
+                torch.cuda.synchronize()
+                t0 = time.time()
+                out = fn(*a, **k)
+                torch.cuda.synchronize()
+                spent[key] += time.time() - t0
+                return out
+            return run
+        model.rebase_, model.admit_ = synced(rebase, "rebase"), synced(admit_, "admit")
+        seen.update(steps=0, rebases=0, dropped=0, last=0)
+        total = timed(lambda: continuous(False, c))
+        model.rebase_, model.admit_ = rebase, admit_
+        res[f"instrumented eager, compact={c}"] = {"total_seconds": round(total, 3), "rebases": seen["rebases"],
+                                                   "rebase_seconds": round(spent["rebase"], 4), "rebase_share": round(spent["rebase"] / total, 5),
+                                                   "admit_seconds": round(spent["admit"], 3), "admit_share": round(spent["admit"] / total, 4)}
+    model._forward, model.decode_graphed, model.rebase_ = forward_, graphed_, rebase_
     print(json.dumps(res))
 
 
