@@ -28,7 +28,9 @@
  *                               2-bit with nh / nh_kv in {1, 4, 8} or 4-bit with nh / nh_kv in {1, 4}), with the packers of that
  *                               cache: kivi_kt_pack, kivi_vt_pack, kivi_vt_pack_at, kivi_kt_relayout, kivi_vt_relayout
  *               beam search:    kivi_cache_reorder (in-place row reorder of either cache layout, from a fork point on)
- *               admission:      kivi_cache_admit (rows of one cache into chosen rows of another, living one: continuous batching)
+ *               admission:      kivi_cache_admit (rows of one cache into chosen rows of another, living one: continuous batching),
+ *                               kivi_mf_store_admit (a packed store into chosen rows of another at a block offset, the lead zeroed:
+ *                               a short prompt admitted without the pads)
  *               rebase:         kivi_mf_store_shift (the blocks of a packed store moved towards token 0 in place: a living cache
  *                               drops its leading tokens)
  *               rollback:       kivi_cache_snapshot (the fp16 residual / window and range words of a cache into a flat buffer and
@@ -608,6 +610,31 @@ int kivi_cache_admit(const kivi_admit_slab* slabs, int n_slabs, int n_rows, cons
  */
 int kivi_mf_store_shift(void* store, int64_t st_sb, int64_t st_sh, int64_t st_ss, void* range, int bits, int is_k, int B, int nh_kv,
                         int64_t n_blocks, int64_t shift_blocks, kivi_stream_t stream);
+/*
+ * kivi_mf_store_admit: ONE packed store of the matrix-pipe layout (KT: is_k != 0, or VT; 2- or 4-bit super-blocks) of a SOURCE cache
+ * into chosen rows of a DESTINATION cache, shift_blocks 32-token blocks further from token 0 (the admission of a short prompt at an
+ * offset).  For i < n_rows, every kv head and every block j < n_blocks (the blocks in use of the source):
+ *   destination row rows[i], block j + shift_blocks <- source row i, block j   (its code words, scale and zero-point pieces, wherever
+ *                                                      each side's super-block keeps them; a partly filled last V block moves whole)
+ *   destination row rows[i], blocks [0, shift_blocks) <- 0
+ *   destination range word of (rows[i], head)         <- the source's word of (i, head): replaced, not OR-ed -- zero blocks hold no
+ *                                                      scale and add no mark, so the source's word is the row's
+ * Every code, scale and zero point keeps its bits.  dst / dst_sb / dst_sh / dst_ss (words) / dst_range and the src_ five: as for
+ * kivi_kt_pack, each side with its own strides; the range words of a side are rows x nh_kv contiguous int32.  The two stores are
+ * different allocations.  `rows`: n_rows int32 (rows_bytes 4) or int64 (8) indices in DEVICE memory, read on the device; they must be
+ * distinct; a value outside [0, B) leaves that source row unused -- nothing outside the destination's B rows is ever written (the
+ * rule of kivi_cache_admit).  The source holds at least n_rows rows.  One launch of n_rows * nh_kv * (n_blocks + shift_blocks) *
+ * (units of a block) threads, one 16-byte unit each (kivi_amd/csrc/kivi_admit_shift.h has the map): no LDS, no scratch, no atomics.
+ * shift_blocks == 0 is legal: the plain move of the blocks and the range words.
+ * Before anything is enqueued: KIVI_EINVAL for bits not 2 or 4, B outside [1, 65535], n_rows outside [1, B], rows_bytes not 4 or 8, a
+ * null or misaligned rows, nh_kv < 1, a negative block count, n_blocks + shift_blocks >= 2^31, a null store or range pointer on
+ * either side, strides of the destination too small for n_blocks + shift_blocks blocks or of the source for n_blocks, a grid of
+ * 2^31 threads or more; KIVI_EALIGN for a base or stride that is not a multiple of 16 bytes (range words: of 4).
+ * n_blocks == 0 and shift_blocks == 0: nothing is enqueued, returns 0.
+ */
+int kivi_mf_store_admit(void* dst, int64_t dst_sb, int64_t dst_sh, int64_t dst_ss, void* dst_range, const void* src, int64_t src_sb,
+                        int64_t src_sh, int64_t src_ss, const void* src_range, int bits, int is_k, int n_rows, const void* rows,
+                        int rows_bytes, int B, int nh_kv, int64_t n_blocks, int64_t shift_blocks, kivi_stream_t stream);
 /*
  * kivi_sample: one token per row drawn from (B, V) logits the way transformers' do_sample path does:
  * s = float(logit) / temperature; keep s >= the top_k-th largest s (ties kept; top_k = 0 or >= V: off); renormalise over those and

@@ -189,6 +189,8 @@ SIGNATURES = {
     "kivi_cache_snapshot": (_i32, [ctypes.POINTER(ReorderSlab), _i32, _i32, _vp, ctypes.c_size_t, _i32, _vp]),
     "kivi_cache_admit": (_i32, [ctypes.POINTER(AdmitSlab), _i32, _i32, _vp, _i32, _i32, _vp]),
     "kivi_mf_store_shift": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _vp]),
+    "kivi_mf_store_admit": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i64,
+                                   _i64, _vp]),
     "kivi_sample": (_i32, [_vp, _i32, _i64, _i32, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float, _vp, _vp, _i64, _vp]),
     "kivi_sample_rows": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "kivi_token_logprob": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),

@@ -113,7 +113,7 @@ class KiviPerformanceWarning(UserWarning):
 class KiviCacheBase:
     """What the two layouts of a layer's cache (KiviLayerCache here, KiviLayerCacheMF in cache_mf.py) share: the geometry, the six
     lengths of the state machine, the scratch of a decode step, and everything that follows from them alone.  A layout adds its
-    buffers (`_BUFFERS`, `reserve`, `_own_buffers`, `_reorder_slabs`, `_checkpoint_slabs`, `_admit_slabs`, `_rebase_buffers`, `prefill`), the readers of the reference layout
+    buffers (`_BUFFERS`, `reserve`, `_own_buffers`, `_reorder_slabs`, `_checkpoint_slabs`, `_admit_slabs`, `_admit_offset`, `_rebase_buffers`, `prefill`), the readers of the reference layout
     (`k_quant_reference_layout`, `v_quant_views`, `v_res_view`) and its steps (`decode_step`, `extend`)."""
 
     def __init__(self, cfg: KiviConfig, batch: int, num_kv_heads: int, head_dim: int, max_len: int, dtype):
@@ -197,24 +197,31 @@ class KiviCacheBase:
         window stands."""
         return tuple(x for i, x in enumerate(self._geometry()) if i != 1)
 
-    def check_admit(self, src, n: int) -> None:
-        """Raise ValueError when `src` cannot be admitted into `n` rows of this cache (nothing runs on a device)."""
+    def check_admit(self, src, n: int, offset: int = 0) -> None:
+        """Raise ValueError when `src` cannot be admitted into `n` rows of this cache at token `offset` (nothing runs on a device)."""
         if src is self:
             raise ValueError("admit_: the source is the destination cache itself")
         if not isinstance(src, KiviCacheBase) or src._admit_geometry() != self._admit_geometry():
             theirs = src._admit_geometry() if isinstance(src, KiviCacheBase) else type(src).__name__
             raise ValueError(f"admit_: the source is of another class or geometry: {theirs}, this cache is {self._admit_geometry()}")
+        admit.check_offset(offset, self.rebase_quantum, self.kv_seq_len, self.cfg.residual_length)
         for name in ("kv_seq_len", "k_quant_len", "k_res_len", "v_quant_len", "v_res_len"):
-            if getattr(src, name) != getattr(self, name):
-                raise ValueError(f"admit_: {name} differs: the source is at {getattr(src, name)}, this cache at {getattr(self, name)} "
-                                 f"(a prompt is admitted left-padded to the living cache's length)")
+            if not offset:
+                if getattr(src, name) != getattr(self, name):
+                    raise ValueError(f"admit_: {name} differs: the source is at {getattr(src, name)}, this cache at {getattr(self, name)} "
+                                     f"(a prompt is admitted left-padded to the living cache's length)")
+                continue
+            want = getattr(self, name) - (0 if name.endswith("res_len") else offset)
+            if getattr(src, name) != want:
+                raise ValueError(f"admit_: {name} does not fit offset={offset}: the source is at {getattr(src, name)}, this cache at "
+                                 f"{getattr(self, name)}, so the source has to be at {want} (a prompt pass over kv_seq_len - offset tokens)")
         if src.B != n:
             raise ValueError(f"admit_: the source holds {src.B} rows, {n} rows were named")
         mine = {getattr(self, b).untyped_storage().data_ptr() for b in self._BUFFERS}
         if any(getattr(src, b).untyped_storage().data_ptr() in mine for b in src._BUFFERS):
             raise ValueError("admit_: the source shares a buffer with this cache (admit from a cache of its own, e.g. a clone)")
 
-    def admit_(self, rows, src, check: bool = True):
+    def admit_(self, rows, src, check: bool = True, offset: int = 0):
         """Row rows[i] of this cache <- row i of `src`, in place (kivi_cache_admit): a new request takes over the row of a finished
         one.  `src`: a cache of the same class and geometry -- batch size, capacity and v_res_start may differ -- of len(rows) rows at
         the same six lengths (a prompt pass over the prompts left-padded to this cache's length), sharing no buffer with this one.
@@ -224,11 +231,19 @@ class KiviCacheBase:
         source's window positions to this cache's.  Lengths, data pointers, the native descriptor, the scratch rows and the fusion
         flags stay: captured graphs remain valid.  Checkpoints issued so far become stale, as after a reorder.  ValueError before
         anything runs on a device for another class or geometry, a length that differs, a row count that does not fit, bad rows,
-        `src is self` or a shared buffer."""
+        `src is self` or a shared buffer.
+        `offset` > 0: `src` is `offset` tokens SHORTER -- a prompt pass over kv_seq_len - offset >= residual_length
+        tokens, its packed lengths `offset` below this cache's, the fp16 residual and window lengths the same -- and lands in tokens
+        [offset, kv_seq_len) of the rows; tokens [0, offset) of the packed K and V become zero blocks, which the caller masks (the rows'
+        2D mask starts with `offset` zeros).  `offset` is a multiple of `rebase_quantum`, so every K group, block, code, scale and
+        zero point keeps its bits: the rows are what rebase_(offset) turns back into `src` (`_admit_offset`)."""
         rows = admit.rows_tensor(rows)
-        self.check_admit(src, rows.shape[0])
+        self.check_admit(src, rows.shape[0], offset)
         rows = admit.check_rows(rows, rows.shape[0], self.B, self.k_res.device, check)
-        admit.run(self._admit_slabs(src), rows, self.B)
+        if offset:
+            self._admit_offset(rows, src, offset)
+        else:
+            admit.run(self._admit_slabs(src), rows, self.B)
         self._void_checkpoints()          # a row holds another request now: no rollback across an admission
         return self
 
@@ -495,6 +510,42 @@ class KiviLayerCache(KiviCacheBase):
             out.append(admit.slab(self.v_res, self.v_res_start * rowb, src.v_res, src.v_res_start * rowb,
                                   [(h, self.v_res.stride(1) * 2, src.v_res.stride(1) * 2)], self.v_res_len * rowb))
         return out
+
+    def _admit_offset(self, rows: torch.Tensor, src: "KiviLayerCache", offset: int) -> None:
+        """Admission at token `offset` (the UNTUNED path, as _rebase_buffers: torch ops on the tensors' device --
+        an offset of 32 tokens is 2 bytes of fp16 K scales, below the 4-byte units of kivi_cache_admit).  The source's packed K in
+        the reference layout behind `offset` tokens of zeros, written page by page (the shift crosses pages); the V triple behind
+        `offset` zero rows; the fp16 K residual; the window from the source's [v_res_start, + v_res_len) to this cache's.  `rows`
+        is only used on the device: an index outside [0, B) leaves its source row unused (it is redirected to the first good row
+        WITH that row's source, a second write of the same bytes; with no good row, to row 0 with row 0's own bytes)."""
+        kf, g, P = 32 // self.cfg.k_bits, self.cfg.group_size, self.page_tokens
+        rows = rows.long()
+        ok = (rows >= 0) & (rows < self.B)
+        pick = torch.where(ok, torch.arange(rows.shape[0], device=rows.device), ok.int().argmax())     # the source row of every entry
+        ok = ok.index_select(0, pick)
+        tgt = torch.where(ok, rows.index_select(0, pick), torch.zeros_like(rows))
+
+        def put(dst, val):                         # dst (B, ...) view <- val (n, ...) at the rows
+            val = val.index_select(0, pick)
+            dst.index_copy_(0, tgt, torch.where(ok.view(-1, *[1] * (val.dim() - 1)), val, dst.index_select(0, tgt)))
+
+        def lead(x, dim, n):                       # n zeros in front of x along dim
+            shape = list(x.shape)
+            shape[dim] = n
+            return torch.cat([x.new_zeros(shape), x], dim)
+        kq = self.k_quant_len
+        for x, y, per in zip((self.k_code, self.k_scale, self.k_mn), src.k_quant_reference_layout(), (kf, g, g)):
+            y = lead(y, 3, offset // per)
+            for p in range((kq + P - 1) // P):
+                n = min(P, kq - p * P)
+                put(x[:, :, p, :, : n // per], y[..., p * P // per: (p * P + n) // per])
+        if self.k_res_len:
+            put(self.k_res[:, :, : self.k_res_len], src.k_res[:, :, : self.k_res_len])
+        for x, y in zip((self.v_code, self.v_scale, self.v_mn), (src.v_code, src.v_scale, src.v_mn)):
+            put(x[:, :, : self.v_quant_len], lead(y[:, :, : src.v_quant_len], 2, offset))
+        if self.v_res_len:
+            put(self.v_res[:, :, self.v_res_start: self.v_res_start + self.v_res_len],
+                src.v_res[:, :, src.v_res_start: src.v_res_start + self.v_res_len])
 
     def _rebase_buffers(self, drop: int) -> None:
         """The packed K and V from token `drop` on -> token 0, into the same buffers (the UNTUNED path, as extend: torch ops on the

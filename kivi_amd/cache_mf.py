@@ -187,7 +187,12 @@ class KiviLayerCacheMF(KiviCacheBase):
                 out.append(admit.slab(st, s * dss + off, sy, s * sss + off,
                                       [(n, dss, sss)] * (n > 0) + [heads] + [(c, b, b) for c, b in inner], run))
             out.append(admit.slab(mfma.range_flags(st), 0, mfma.range_flags(sy), 0, [], h * 4))
-        rowb = self.D * 2
+        return out + self._admit_fp16_slabs(src)
+
+    def _admit_fp16_slabs(self, src: "KiviLayerCacheMF"):
+        """The fp16 part of an admission (the same at any offset: these tokens are the newest): the K residual up to its length, the
+        live window tokens rotated from the source's ring phase to this cache's."""
+        h, rowb, out = self.nh_kv, self.D * 2, []
         if self.k_res_len:
             out.append(admit.slab(self.k_res, 0, src.k_res, 0, [(h, self.k_res.stride(1) * 2, src.k_res.stride(1) * 2)],
                                   self.k_res_len * rowb))
@@ -199,6 +204,15 @@ class KiviLayerCacheMF(KiviCacheBase):
             out.append(admit.slab(self.v_res, d * rowb, src.v_res, s * rowb, ring, n * rowb))
             t += n
         return out
+
+    def _admit_offset(self, rows: torch.Tensor, src: "KiviLayerCacheMF", offset: int) -> None:
+        """Admission at token `offset`: one kivi_mf_store_admit per store -- the source's blocks in use land
+        `offset` / 32 blocks further up, the blocks under the offset are zeroed, the range words replaced -- then the fp16 K residual
+        and the ring-rotated window through kivi_cache_admit, as at offset 0."""
+        for st, sy, n_tok, is_k, bits in ((self.kt, src.kt, src.k_quant_len, True, self.cfg.k_bits),
+                                          (self.vt, src.vt, src.v_quant_len, False, self.cfg.v_bits)):
+            admit.admit_store(st, sy, rows, bits, is_k, -(-n_tok // 32), offset // 32)
+        admit.run(self._admit_fp16_slabs(src), rows, self.B)
 
     # ------------------------------------------------------------------ rebase (DESIGN.md section 17)
     def _rebase_buffers(self, drop: int) -> None:

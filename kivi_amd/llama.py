@@ -207,7 +207,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     # ------------------------------------------------------------------ continuous batching
     @torch.no_grad()
-    def admit_(self, past_key_values, rows, input_ids: torch.LongTensor, attention_mask: torch.Tensor):
+    def admit_(self, past_key_values, rows, input_ids: torch.LongTensor, attention_mask: torch.Tensor, offset: int = 0):
         """New requests take over rows of living caches: -> (prompt logits (n, 1, vocab), fresh tuples of the living caches).
         `past_key_values`: the tuples of forward() / generate() over caches of B rows at kv length L.  `input_ids` (n, L) and HF's 2D
         `attention_mask` (n, L): the n new prompts left-padded to exactly L (left_pad(..., length=L); a prompt of L tokens has no
@@ -215,31 +215,47 @@ class LlamaForCausalLM_KIVI(nn.Module):
         forward(input_ids, padding_mask=attention_mask) -- the flash classes refuse padded prompts there as ever -- and every layer's
         temporary cache is put into the rows in place (KiviCacheBase.admit_): the other rows, every buffer address and the lengths
         stay, so captured decode graphs over the living caches remain valid; the temporary caches die with the call.  ValueError
-        before any forward pass for plain 9-tuples, input_ids of another length than L, a mask of another shape, n > B, bad rows."""
+        before any forward pass for plain 9-tuples, input_ids of another length than L, a mask of another shape, n > B, bad rows.
+        `offset` > 0: `input_ids` and `attention_mask` are (n, L - offset) -- the prompts left-padded to the SHORT
+        length -- and the prompt pass costs O(L - offset), not O(L).  Positions come from the mask, so they are those of the L-padded
+        pass; the result lands in tokens [offset, L) of the rows, tokens [0, offset) become zero blocks.  The caller's 2D mask for
+        the rows is cat(zeros(offset), attention_mask): the lead is masked like any pad.  `offset`: an int, a multiple of
+        rebase_quantum(past_key_values), with L - offset >= residual_length; anything else is a ValueError before the forward pass.
+        The admitted rows are NOT bit-identical to an admission at offset 0 (serving.py has the reasons)."""
         caches = self._layer_caches(past_key_values, "admit_")
         L, B = caches[0].kv_seq_len, caches[0].B
-        if input_ids.dim() != 2 or input_ids.shape[1] != L:
+        if offset != 0 or not isinstance(offset, int) or isinstance(offset, bool):
+            for c in caches:
+                admit.check_offset(offset, c.rebase_quantum, c.kv_seq_len, c.cfg.residual_length)
+            if input_ids.dim() != 2 or input_ids.shape[1] != L - offset:
+                raise ValueError(f"admit_: input_ids must be (n, L - offset) with L = {L} the kv length of the living caches and offset = "
+                                 f"{offset} (left-pad the prompts to {L - offset}), got {tuple(input_ids.shape)}")
+        elif input_ids.dim() != 2 or input_ids.shape[1] != L:
             raise ValueError(f"admit_: input_ids must be (n, L) with L = {L}, the kv length of the living caches (left-pad the prompts "
                              f"to it), got {tuple(input_ids.shape)}")
         n = input_ids.shape[0]
-        if attention_mask is None or attention_mask.dim() != 2 or tuple(attention_mask.shape) != (n, L):
-            raise ValueError(f"admit_: the 2D attention mask should be of size {(n, L)}, but is "
+        if attention_mask is None or attention_mask.dim() != 2 or tuple(attention_mask.shape) != (n, L - offset):
+            raise ValueError(f"admit_: the 2D attention mask should be of size {(n, L - offset)}, but is "
                              f"{None if attention_mask is None else tuple(attention_mask.shape)}")
         if not 1 <= n <= B:
             raise ValueError(f"admit_: {n} prompts for living caches of {B} rows")
         rows = admit.check_rows(rows, n, B, caches[0].k_res.device)
         logits, fresh = self.forward(input_ids, padding_mask=attention_mask)
         for c, t in zip(caches, fresh):
-            c.admit_(rows, t.layer, check=False)
+            c.admit_(rows, t.layer, check=False, offset=offset)
         return logits, [c.as_tuple() for c in caches]
 
     def generate_continuous(self, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
-                            pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False, compact: Optional[int] = None):
+                            pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False, compact: Optional[int] = None,
+                            short_admissions: bool = False):
         """Continuous batching over a queue of requests (kivi_amd/serving.py: generate_continuous): a batch of `batch_size` rows whose
         finished rows are taken over by the waiting prompts.  -> the generated tokens of every request, in request order.
-        `compact`: None, or the fewest leading tokens worth dropping from the living caches between two steps (rebase_)."""
+        `compact`: None, or the fewest leading tokens worth dropping from the living caches between two steps (rebase_).
+        `short_admissions`: admit at an offset, the prompt pass over about the prompt's length instead of the caches' (DESIGN.md
+        section 19; tokens may differ from the default)."""
         from .serving import generate_continuous
-        return generate_continuous(self, prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, graphed, compact)
+        return generate_continuous(self, prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, graphed, compact,
+                                   short_admissions)
 
     # ------------------------------------------------------------------ rebase (DESIGN.md section 17)
     @classmethod

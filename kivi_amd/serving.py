@@ -19,6 +19,15 @@ The policy is fixed (tests restate it):
     drop = room rounded down to rebase_quantum; if drop >= n, model.rebase_ drops the first `drop` tokens of every row, the 2D mask
     loses its first `drop` columns and L falls by `drop`.  The leading pads are kept on the host: admission length - prompt
     length - the drops since.
+  * `short_admissions=True` (default False): an admission runs its prompt pass at a short length instead of L.
+    off = admission_offset(L, the longest prompt of the group admitted together, residual_length, rebase_quantum): the prompts are
+    left-padded to L - off, model.admit_(..., offset=off) puts them into tokens [off, L) of the rows and zeroes the blocks below, the
+    rows' 2D mask is off zeros followed by the short mask.  Still ONE admit_ per group; the leading pads kept on the host are
+    L - prompt length as before, so `compact=` works unchanged; no buffer or length changes, so the graphed mode replays the captured
+    step.  An offset-admitted row is NOT bit-identical to an L-padded one: the K groups that mix pads and real tokens quantise
+    other pad values (the pads' hidden states depend on how many pads precede them), and the prompt's SDPA runs at another length
+    (another reduction order).  Both are the differences two L-padded admissions at different L already have; tokens can differ
+    from short_admissions=False, which is why the default stays off.
   * Rows with nothing to do feed `pad_token_id`.  The call ends when every request is done: no step runs after the last pick.
   * Token i of a request is draw i of its own seed with Philox stream 0, whichever row and step it lands on:
     the first token is drawn by a RowSampler of the admitted rows alone, then the batch's RowSampler row is bound with
@@ -39,11 +48,13 @@ def _positive_int(x) -> bool:
 
 
 def check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, vocab_size: Optional[int] = None,
-                    compact: Optional[int] = None):
+                    compact: Optional[int] = None, short_admissions: bool = False):
     """-> (prompts as 1-D int64 CPU tensors, max_new_tokens per request, bound SamplingParams per request or None); ValueError for
     anything generate_continuous cannot serve (no device work)."""
     if compact is not None and not _positive_int(compact):
         raise ValueError(f"compact has to be None or a positive integer (the fewest tokens worth reclaiming), got {compact!r}")
+    if not isinstance(short_admissions, bool):
+        raise ValueError(f"short_admissions has to be a bool (admit at an offset, DESIGN.md section 19), got {short_admissions!r}")
     if not isinstance(prompts, (list, tuple)) or not prompts:
         raise ValueError("prompts has to be a non-empty list of token id sequences")
     seqs = [torch.as_tensor(p, dtype=torch.long).flatten().cpu() for p in prompts]
@@ -86,10 +97,17 @@ def compact_drop(leads, L: int, longest_waiting: int, limit: int, quantum: int) 
     return max(room, 0) // quantum * quantum
 
 
+def admission_offset(L: int, longest_prompt: int, R: int, quantum: int) -> int:
+    """The offset of an admission into living caches at length L (host arithmetic): the prompt pass runs over L - offset tokens,
+    which has to hold the longest prompt of the group admitted together and at least R = residual_length tokens; the offset is a
+    multiple of `quantum` (rebase_quantum).  0: the admission runs at L, as without short_admissions."""
+    return max(L - max(longest_prompt, R), 0) // quantum * quantum
+
+
 @torch.no_grad()
 def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
                         pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False,
-                        compact: Optional[int] = None) -> List[torch.Tensor]:
+                        compact: Optional[int] = None, short_admissions: bool = False) -> List[torch.Tensor]:
     """`prompts`: a list of token id sequences, possibly more than `batch_size`; `max_new_tokens`: an int or one per request;
     `sampling`: None (greedy), one SamplingParams, or one per request.  -> the generated tokens of every request as 1-D int64
     tensors, in request order, ending with `eos_token_id` where it was produced.  The policy: the module docstring.
@@ -98,9 +116,11 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
     mask buffer has to grow, or the first pad of the call arrives with an admission).  Same tokens as graphed=False.
     `compact`: None -- the caches' length only grows --, or the fewest tokens worth reclaiming: at the top of every iteration the
     leading tokens no live row and no waiting prompt needs are dropped from the living caches (model.rebase_), if there are at least
-    that many."""
+    that many.
+    `short_admissions`: False -- every admission is a prompt pass at the caches' length --, or True: at about the prompts' length,
+    admitted at an offset (the module docstring; tokens can differ from False)."""
     prompts, limits, params = check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling,
-                                              model.config.vocab_size, compact)
+                                              model.config.vocab_size, compact, short_admissions)
     pad = 0 if pad_token_id is None else pad_token_id
     N, device = len(prompts), model.lm_head.weight.device
     B = min(batch_size, N)
@@ -144,9 +164,15 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
             rows = [b for b in range(B) if owner[b] is None][: N - waiting]
             reqs = list(range(waiting, waiting + len(rows)))
             waiting += len(rows)
-            new_ids, new_mask = left_pad([prompts[r] for r in reqs], pad, device, length=L)
-            lg, pasts = model.admit_(pasts, rows, new_ids, new_mask)
-            mask2d[rows, :L] = new_mask
+            off = 0
+            if short_admissions:
+                off = admission_offset(L, max(prompts[r].numel() for r in reqs), pasts[0].layer.cfg.residual_length,
+                                       model.rebase_quantum(pasts))
+            new_ids, new_mask = left_pad([prompts[r] for r in reqs], pad, device, length=L - off)
+            lg, pasts = model.admit_(pasts, rows, new_ids, new_mask, offset=off)
+            if off:
+                mask2d[rows, :off] = 0                                             # the zeroed lead is masked like any pad
+            mask2d[rows, off:L] = new_mask
             first = pick(lg, None if params is None else RowSampler([params[r] for r in reqs], device))     # draw 0 of each
             tok[rows] = first
             for b, r, t in zip(rows, reqs, first.view(-1).tolist()):

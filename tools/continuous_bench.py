@@ -1,7 +1,7 @@
 """End to end: generate_continuous against static waves on a Llama-shaped model with random weights (the recipe of
 examples/mem_spd_test.py: Llama-2-7B architecture, k = v = 2 bit, g = 32, R = 32; the tokens mean nothing, time does).
 
-    python tools/continuous_bench.py [--requests 96] [--batch 32] [--reps 3] [--compact N [N ...]]
+    python tools/continuous_bench.py [--requests 96] [--batch 32] [--reps 3] [--compact N [N ...] | --short]
 
 Requests: prompt lengths uniform in [32, 160]; output lengths 8 + floor(Exp(mean 96)), capped at 512 -- a skewed distribution (the
 median is ~75 tokens, the longest of a wave of 32 is typically beyond 300); numpy seed 0.  No EOS: every request runs to its length.
@@ -13,7 +13,11 @@ The admission share is measured in a run of its own: the wall time inside admit_
 `--compact N [N ...]`: the modes are generate_continuous with compact=None -- the behaviour without it, the
 comparison -- and with compact=N for every N given, eager and graphed, alternating; no static waves.  Per mode also the decode steps,
 the kv length at the end and the number of rebases (host-side counters around model methods, no synchronisation); the share of time
-in rebase_ comes from a synchronised run of its own per N, like the admission share."""
+in rebase_ comes from a synchronised run of its own per N, like the admission share.
+`--short`: generate_continuous with short_admissions=False -- the behaviour without it, the comparison -- and
+True, eager and graphed, alternating; no static waves.  Per mode also the admissions, the tokens their prompt passes ran over and
+the offsets (host-side counters around admit_); the admission share of each form comes from a synchronised eager run of its own.
+The two forms may pick other tokens; every request runs to its length, so the work is the same."""
 import argparse
 import json
 import os
@@ -39,6 +43,8 @@ def main():
     ap.add_argument("--vocab", type=int, default=32000)
     ap.add_argument("--compact", type=int, nargs="+", default=None, metavar="N",
                     help="compare generate_continuous(compact=None) with compact=N for every N (no static waves)")
+    ap.add_argument("--short", action="store_true",
+                    help="compare generate_continuous(short_admissions=False) with True (no static waves)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     cfg = SimpleNamespace(hidden_size=args.hidden, num_attention_heads=args.heads, num_key_value_heads=args.heads,
@@ -69,8 +75,8 @@ def main():
             steps += n
         return steps
 
-    def continuous(graphed, compact=None):
-        out = model.generate_continuous(prompts, limits, B, graphed=graphed, compact=compact)
+    def continuous(graphed, compact=None, short=False):
+        out = model.generate_continuous(prompts, limits, B, graphed=graphed, compact=compact, short_admissions=short)
         assert [o.numel() for o in out] == limits
         return None
 
@@ -78,6 +84,8 @@ def main():
              ("continuous, graphed", lambda: continuous(True))]
     if args.compact:
         return compact_modes(args, model, continuous, asked)
+    if args.short:
+        return short_modes(args, model, continuous, asked)
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -188,6 +196,59 @@ def compact_modes(args, model, continuous, asked):
                                                    "rebase_seconds": round(spent["rebase"], 4), "rebase_share": round(spent["rebase"] / total, 5),
                                                    "admit_seconds": round(spent["admit"], 3), "admit_share": round(spent["admit"] / total, 4)}
     model._forward, model.decode_graphed, model.rebase_ = forward_, graphed_, rebase_
+    print(json.dumps(res))
+
+
+def short_modes(args, model, continuous, asked):
+    """--short: short_admissions=False against True, eager and graphed (see the module docstring)."""
+    seen = {"admissions": 0, "pass_tokens": 0, "offset_tokens": 0, "rows": 0}
+    admit_ = model.admit_
+
+    def counted(past, rows, ids, mask, offset=0):
+        seen["admissions"] += 1
+        seen["rows"] += ids.shape[0]
+        seen["pass_tokens"] += ids.shape[0] * ids.shape[1]
+        seen["offset_tokens"] += ids.shape[0] * offset
+        return admit_(past, rows, ids, mask, offset=offset)
+    model.admit_ = counted
+    modes = [(f"{'graphed' if g else 'eager'}, short_admissions={s}", g, s) for s in (False, True) for g in (False, True)]
+    runs = {name: [] for name, _, _ in modes}
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.time()
+        fn()
+        torch.cuda.synchronize()
+        return time.time() - t0
+    for rep in range(args.reps + 1):                       # repetition 0 warms every mode up
+        for name, g, s in modes:
+            seen.update(admissions=0, pass_tokens=0, offset_tokens=0, rows=0)
+            t = timed(lambda: continuous(g, None, s))
+            if rep:
+                runs[name].append((t, dict(seen)))
+    res = {"requests": args.requests, "batch": args.batch, "tokens_asked_for": asked, "repetitions": args.reps, "layers": args.layers}
+    for name, _, _ in modes:
+        ts = sorted(t for t, _ in runs[name])
+        med, counters = ts[len(ts) // 2], runs[name][0][1]
+        res[name] = {"seconds": [round(t, 3) for t, _ in runs[name]], "median_seconds": round(med, 3), "tokens_per_s": round(asked / med, 1),
+                     "spread": round((ts[-1] - ts[0]) / med, 3), "admissions": counters["admissions"], "rows_admitted": counters["rows"],
+                     "prompt_pass_tokens": counters["pass_tokens"], "tokens_under_offsets": counters["offset_tokens"]}
+    for s in (False, True):                                # the share of admit_, in synchronised runs of their own
+        spent = [0.0]
+
+        def synced(*a, **k):
+            torch.cuda.synchronize()
+            t0 = time.time()
+            out = counted(*a, **k)
+            torch.cuda.synchronize()
+            spent[0] += time.time() - t0
+            return out
+        model.admit_ = synced
+        total = timed(lambda: continuous(False, None, s))
+        model.admit_ = counted
+        res[f"instrumented eager, short_admissions={s}"] = {"total_seconds": round(total, 3), "admit_seconds": round(spent[0], 3),
+                                                            "admit_share": round(spent[0] / total, 4)}
+    model.admit_ = admit_
     print(json.dumps(res))
 
 
