@@ -39,6 +39,7 @@
  *                               the device), kivi_sample_rows (the same draw with per-row parameters, seeds, streams and
  *                               greedy rows read from device memory)
  *               scoring:        kivi_token_logprob (log-probability and rank of one given token per row of logits)
+ *               prompt pass:    kivi_prefill_attention (causal grouped-query attention over fp16 q / k / v with leading pads)
  *   BUILDING BLOCKS (what the layer steps are composed of; exported for tests, tools and callers that keep their own cache
  *               bookkeeping -- same contracts, but no stability promise beyond the ABI version):  kivi_gemv_k_paged,
  *               kivi_decode_scores, kivi_softmax_scaled, kivi_decode_output, kivi_decode_softmax_output, kivi_decode_attend,
@@ -712,6 +713,27 @@ int kivi_sample_rows(const void* logits, int logits_bits, int64_t row_stride, in
 int kivi_token_logprob(const void* logits, int logits_bits, int64_t row_stride, int64_t N, int V, const int64_t* targets,
                        int64_t target_stride, int64_t ignore_index, float* out_logprob, float* out_lse, int32_t* out_rank,
                        kivi_stream_t stream);
+/*
+ * kivi_prefill_attention: the attention of a prompt pass over fp16 q / k / v -- causal, grouped-query, with leading pads per batch
+ * row (the reference's prompt pass, models/llama_kivi.py:401-452, without the repeat_kv copies and without a
+ * (B, 1, T, T) mask).  q and out are (B, nh, T, D), k and v (B, nh_kv, T, D) fp16, each by its strides (batch, head, token) in
+ * elements, channel stride 1: the transposed views of (B, T, heads, D) projections go in as they are, and out may be laid out
+ * (B, T, nh * D).  Query head h reads kv head h / (nh / nh_kv) (quant/csrc/gemv_cuda.cu:361-365).
+ *   lead   device memory, one int32 per batch row: the number of leading masked tokens, clamped to [0, T] on the device and never
+ *          read on the host; null: no pads
+ *   for a query i >= lead[b]:  out[b, h, i, :] = softmax_j(scale * q_i . k_j) v_j over the keys j in [lead[b], i]
+ *   for a query i <  lead[b] (a pad): exact zeros
+ * Arithmetic: q k^T on v_mfma_f32_16x16x32_f16 with fp32 accumulation; scale and an online softmax in fp32 (exp2); the
+ * probabilities rounded to fp16 for the product with v (fp32 accumulation); one division by the fp32 sum and one rounding to fp16 at
+ * the end.  Inputs are finite by contract.  One launch, no workspace, every output element written once.
+ * KIVI_EINVAL (nothing enqueued) for D != 128; B, nh, nh_kv or T < 1; nh not a multiple of nh_kv; nh / nh_kv outside {1, 2, 4, 8};
+ * a null q / k / v / out; a scale that is not finite and positive; a grid of 2^31 blocks or more (B * nh * ceil(T / 128)).
+ * KIVI_EALIGN for a base pointer or a stride that is not a multiple of 16 bytes, or lead off 4 bytes.
+ */
+int kivi_prefill_attention(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_st, const void* k, int64_t k_sb, int64_t k_sh,
+                           int64_t k_st, const void* v, int64_t v_sb, int64_t v_sh, int64_t v_st, void* out, int64_t o_sb,
+                           int64_t o_sh, int64_t o_st, const int32_t* lead, int B, int nh, int nh_kv, int T, int D, float scale,
+                           kivi_stream_t stream);
 /* geometry class of a step (-1: bad arguments): the super-block counts of both stores and whether the step flushes a value; the
  * launch plan (one launch / S slices / two launches) is a function of the class and of constants of the call (shape, bits, flags) */
 int64_t kivi_mf_step_key(const kivi_mf_step* step, int B, int nh, int nh_kv, int residual_length, int flags);

@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _tuning
+from . import prefill as _prefill
 from .cache import KiviCacheTuple, KiviConfig, KiviLayerCache, KiviPerformanceWarning  # noqa: F401
 from .cache_mf import KiviLayerCacheMF, make_layer_cache, supported as _mf_supported
 
@@ -57,13 +58,26 @@ def kivi_attention_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, lay
 
 
 def kivi_attention_prefill(query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
-                           layer: KiviLayerCache, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Prompt pass (:401-452): attention over fp16 q/k/v (torch SDPA, outside the quantised hot path), then split K/V
-    into the quantised prefix and the fp16 residual.
+                           layer: KiviLayerCache, attention_mask: Optional[torch.Tensor] = None, lead: Optional[torch.Tensor] = None,
+                           kernel: bool = False) -> torch.Tensor:
+    """Prompt pass (:401-452): attention over fp16 q/k/v, then split K/V into the quantised prefix and the fp16 residual.
 
     `attention_mask` None: causal -- the flash class, whose mask argument is hard-wired to None (:420-423).  Given
     (additive, (bsz, 1, q_len, kv_len), causal structure included, as HF builds it): the eager class's
-    `attn_weights + attention_mask` (:228-237), e.g. for left-padded batches; a wrong shape raises like the reference."""
+    `attn_weights + attention_mask` (:228-237), e.g. for left-padded batches; a wrong shape raises like the reference.
+
+    `kernel=False`: torch SDPA over K / V repeated per query head.  `kernel=True`: kivi_prefill_attention --
+    causal, grouped queries mapped inside the kernel, `lead` (B,) int32 leading pads per row (a query attends to the keys from its
+    row's lead on, the pads' own outputs are exact zeros) -- on GPU fp16 tensors of head_dim 128 with nh / nh_kv in {1, 2, 4, 8}, the
+    torch restatement of the same contract otherwise (kivi_amd/prefill.py).  The kernel knows causal + lead only: an
+    `attention_mask` given together with `kernel=True` takes the masked SDPA path unchanged.  `layer.prefill` sees the same
+    tensors in every form."""
+    if kernel and attention_mask is None:
+        attn_output = _prefill.attention(query_states, key_states, value_states, lead)
+        layer.prefill(key_states, value_states)
+        return attn_output
+    if lead is not None:
+        raise ValueError("kivi_attention_prefill: `lead` belongs to kernel=True without an attention_mask")
     B, nh, T, D = query_states.shape
     rep = nh // layer.nh_kv
     k, v = key_states, value_states
@@ -138,7 +152,9 @@ class LlamaAttention_KIVI(nn.Module):
     (attn_output, None, past_key_value) with past_key_value the 9-tuple of :454-455.
     """
 
-    # the eager class adds `attention_mask` to the prompt pass's scores (:228-237); the flash subclass does not (:420-423)
+    # the eager class adds `attention_mask` to the prompt pass's scores (:228-237); the flash subclass does not (:420-423).
+    # config.kivi_prefill_kernel (off by default): the prompt pass runs kivi_prefill_attention, and a left-padded one arrives as a
+    # PromptLead in place of the mask -- every class then serves it (DESIGN.md section 20)
     _prefill_uses_mask = True
 
     def __init__(self, config, layer_idx: Optional[int] = None):
@@ -153,6 +169,7 @@ class LlamaAttention_KIVI(nn.Module):
         self.max_position_embeddings = getattr(config, "max_position_embeddings", 4096)
         self.rope_theta = getattr(config, "rope_theta", 10000.0)
         self.kivi = KiviConfig(config.k_bits, config.v_bits, config.group_size, config.residual_length)
+        self.prefill_kernel = bool(getattr(config, "kivi_prefill_kernel", False))
         self.k_bits, self.v_bits = config.k_bits, config.v_bits
         self.group_size, self.residual_length = config.group_size, config.residual_length
         if self.head_dim * self.num_heads != self.hidden_size and getattr(config, "head_dim", None) is None:
@@ -211,7 +228,13 @@ class LlamaAttention_KIVI(nn.Module):
         else:
             layer = make_layer_cache(self.kivi, bsz, self.num_key_value_heads, self.head_dim, self._capacity(q_len),
                                      hidden_states.device, q.dtype, num_heads=self.num_heads)
-            attn_output = kivi_attention_prefill(q, k, v, layer, attention_mask if self._prefill_uses_mask else None)
+            mask = attention_mask if self._prefill_uses_mask else None
+            if isinstance(attention_mask, _prefill.PromptLead):
+                attn_output = kivi_attention_prefill(q, k, v, layer, None, lead=attention_mask.lead, kernel=True)
+            elif self.prefill_kernel:
+                attn_output = kivi_attention_prefill(q, k, v, layer, mask, kernel=True)
+            else:                                          # the option is off: the call as it always was
+                attn_output = kivi_attention_prefill(q, k, v, layer, mask)
         past = layer.as_tuple() if use_cache else None                                     # :454-455
         attn_output = attn_output.transpose(1, 2).reshape(bsz, q_len, self.num_heads * self.head_dim)
         return self.o_proj(attn_output), None, past

@@ -7,7 +7,10 @@ from typing import Callable, Optional
 
 import torch
 
+from .prefill import PromptLead
+
 _MIN16 = torch.finfo(torch.float16).min
+PADS_LEFT = 2     # what LlamaForCausalLM_KIVI._padded answers for a padded prompt pass that runs the prefill kernel (True otherwise)
 
 
 def left_pad(seqs, pad_token_id: int = 0, device=None, length: Optional[int] = None):
@@ -56,12 +59,16 @@ class _PaddedBatch:
     """What a left-padded batch adds to the passes of one call, derived once from HF's 2D mask (B, past_len + T): `mask` and
     `position_ids` of the pass over the T new tokens (the prompt's 4D causal + padding mask; with a history, the key row expanded
     over the chunk), then per decode step a view of the key row one column longer (new tokens are real) and the advancing
-    position.  `beams`: the decode steps run on every row repeated that often (the prompt pass does not)."""
+    position.  `beams`: the decode steps run on every row repeated that often (the prompt pass does not).  `lead`: the prompt pass
+    (no history) runs the prefill kernel -- its `mask` is a PromptLead, the leading pads of every row, and no 4D mask is built."""
 
-    def __init__(self, mask2d: torch.Tensor, past_len: int, T: int, max_new_tokens: int = 0, beams: int = 1):
+    def __init__(self, mask2d: torch.Tensor, past_len: int, T: int, max_new_tokens: int = 0, beams: int = 1, lead: bool = False):
         n = past_len + T
         row = padding_key_row(mask2d, n + max_new_tokens)
-        self.mask = padding_prompt_mask(mask2d) if past_len == 0 else row[..., :n].expand(-1, -1, T, -1)
+        if past_len == 0:
+            self.mask = PromptLead(mask2d) if lead else padding_prompt_mask(mask2d)
+        else:
+            self.mask = row[..., :n].expand(-1, -1, T, -1)
         self.position_ids = padding_position_ids(mask2d, T)
         if max_new_tokens:
             pos = mask2d.long().sum(-1, keepdim=True)                  # (B, 1): position of the next token
@@ -124,8 +131,9 @@ class EagerStepper:
         if n > 1 and past_key_values is not None:
             past_key_values = [p.layer.clone().as_tuple() for p in past_key_values]
         self.model, self.padded, self.group, self.fork = model, None, n, past_len + T
-        if attention_mask is not None and model._padded(attention_mask, B, past_len + T, past_len):
-            self.padded = _PaddedBatch(attention_mask, past_len, T, max_new_tokens, n)
+        padded = attention_mask is not None and model._padded(attention_mask, B, past_len + T, past_len)
+        if padded:
+            self.padded = _PaddedBatch(attention_mask, past_len, T, max_new_tokens, n, lead=padded == PADS_LEFT)
             logits, pasts = model._forward(input_ids, past_key_values, self.padded.mask, self.padded.position_ids, True, True)
         else:
             logits, pasts = model.forward(input_ids, past_key_values)

@@ -27,15 +27,17 @@ import torch.nn.functional as F
 from . import admit
 from .attention import KiviLayerCacheMF, LlamaAttention_KIVI
 from .beam import beam_search
-from .generation import (EagerStepper, _PaddedBatch, decode_loop, left_pad, padding_key_row, padding_position_ids,  # noqa: F401
-                         padding_prompt_mask, resolve_sampler)
+from .generation import (PADS_LEFT, EagerStepper, _PaddedBatch, decode_loop, left_pad, padding_key_row,  # noqa: F401
+                         padding_position_ids, padding_prompt_mask, resolve_sampler)
 from .graph import DecodeGraphs
+from .prefill import left_padded
 from .sampling import RowSampler
 
 
 def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32, residual_length: int = 32,
-                max_cache_len: Optional[int] = None) -> SimpleNamespace:
-    """HF config.json fields (+ the four KIVI fields) -> the namespace the modules read."""
+                max_cache_len: Optional[int] = None, prefill_kernel: bool = False) -> SimpleNamespace:
+    """HF config.json fields (+ the four KIVI fields) -> the namespace the modules read.  `prefill_kernel`: the prompt pass's
+    attention runs kivi_prefill_attention, and every attention class serves left-padded prompts."""
     hidden, heads = d["hidden_size"], d["num_attention_heads"]
     return SimpleNamespace(
         hidden_size=hidden, num_attention_heads=heads, num_key_value_heads=d.get("num_key_value_heads", heads),
@@ -46,7 +48,8 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
         tie_word_embeddings=d.get("tie_word_embeddings", False),
         k_bits=d.get("k_bits", k_bits), v_bits=d.get("v_bits", v_bits), group_size=d.get("group_size", group_size),
         residual_length=d.get("residual_length", residual_length),
-        kivi_max_cache_len=max_cache_len)   # opt-in reservation; by default the cache starts prompt-sized and doubles
+        kivi_max_cache_len=max_cache_len,   # opt-in reservation; by default the cache starts prompt-sized and doubles
+        kivi_prefill_kernel=bool(prefill_kernel))
 
 
 class RMSNorm(nn.Module):
@@ -122,9 +125,10 @@ class LlamaForCausalLM_KIVI(nn.Module):
         if attention_mask is not None:
             raise ValueError("pass either the 4D additive attention_mask or the 2D padding_mask, not both")
         past_len = self._past_len(past_key_values)
-        if not self._padded(padding_mask, input_ids.shape[0], past_len + input_ids.shape[1], past_len):
+        padded = self._padded(padding_mask, input_ids.shape[0], past_len + input_ids.shape[1], past_len)
+        if not padded:
             return self._forward(input_ids, past_key_values, None, None, last_token_only, False)
-        pb = _PaddedBatch(padding_mask, past_len, input_ids.shape[1])
+        pb = _PaddedBatch(padding_mask, past_len, input_ids.shape[1], lead=padded == PADS_LEFT)
         return self._forward(input_ids, past_key_values, pb.mask, pb.position_ids, last_token_only, True)
 
     def _forward(self, input_ids, past_key_values, attention_mask, position_ids, last_token_only, mask_prompt):
@@ -147,18 +151,33 @@ class LlamaForCausalLM_KIVI(nn.Module):
     def _past_len(past_key_values) -> int:
         return int(past_key_values[0][-1]) if past_key_values and past_key_values[0] is not None else 0
 
-    def _padded(self, mask: torch.Tensor, B: int, length: int, past_len: int, has_pad: Optional[bool] = None) -> bool:
-        """Validate a 2D padding mask; True when it holds a pad (False: the caller takes the unmasked path, no mask is built).
-        `has_pad`: what the caller already knows about the mask (spares the synchronisation)."""
+    def _padded(self, mask: torch.Tensor, B: int, length: int, past_len: int, has_pad: Optional[bool] = None,
+                left: Optional[bool] = None):
+        """Validate a 2D padding mask; true when it holds a pad (False: the caller takes the unmasked path, no mask is built).
+        `has_pad`, `left`: what the caller already knows about the mask (spares the synchronisation).
+        With config.kivi_prefill_kernel a padded prompt pass (no history) whose mask is left-padded -- zeros, then ones, in every row,
+        looked at in the same synchronisation -- answers PADS_LEFT: the pass runs on the leading pad counts (_PaddedBatch(lead=True)),
+        on every attention class.  Any other mask takes the masked path of the eager classes and is refused by the flash classes."""
         if mask.dim() != 2 or tuple(mask.shape) != (B, length):
             raise ValueError(f"the 2D attention / padding mask should be of size {(B, length)} (history + new tokens), "
                              f"but is {tuple(mask.shape)}")
-        if has_pad is None:
+        kernel = past_len == 0 and bool(getattr(self.config, "kivi_prefill_kernel", False))
+        if kernel and (has_pad is None or left is None):
+            full, left = torch.stack([(mask != 0).all(), left_padded(mask)]).tolist()
+            has_pad = not full
+        elif has_pad is None:
             has_pad = not bool((mask != 0).all())
         if not has_pad:
             return False
+        if kernel and left:
+            return PADS_LEFT
         if past_len == 0 and not all(layer.self_attn._prefill_uses_mask for layer in self.model.layers):
-            raise ValueError(f"{type(self.model.layers[0].self_attn).__name__}: the prompt pass of this attention class ignores "
+            name = type(self.model.layers[0].self_attn).__name__
+            if kernel:
+                raise ValueError(f"{name}: the mask is not left-padded (zeros, then ones, in every row). The prefill kernel serves "
+                                 f"leading pads only, and the prompt pass of this attention class ignores every other mask "
+                                 f"(llama_kivi.py:420-423); use the eager class")
+            raise ValueError(f"{name}: the prompt pass of this attention class ignores "
                              f"masks (llama_kivi.py:420-423), so padded prompts cannot be run; use the eager class")
         return True
 
@@ -340,14 +359,17 @@ class LlamaForCausalLM_KIVI(nn.Module):
         plan = self._score_plan(input_ids, first_chunk, chunk_size)
         B, T = input_ids.shape
         facts = list(torch.aminmax(input_ids))
+        past_len = self._past_len(past_key_values)
         if attention_mask is not None:
             facts.append((attention_mask == 0).any().to(input_ids.device, torch.long))
+            if past_len == 0 and getattr(self.config, "kivi_prefill_kernel", False):
+                facts.append(left_padded(attention_mask).to(input_ids.device, torch.long))
         lo, hi, *has_pad = (int(v) for v in torch.stack(facts).tolist())
         if lo < 0 or hi >= self.config.vocab_size:
             raise ValueError(f"input_ids hold token ids in [{lo}, {hi}], outside the vocabulary [0, {self.config.vocab_size})")
-        past_len = self._past_len(past_key_values)
         valid = torch.ones((B, T - 1), dtype=torch.bool, device=input_ids.device)
-        padded = attention_mask is not None and self._padded(attention_mask, B, past_len + T, past_len, bool(has_pad[0]))
+        padded = attention_mask is not None and self._padded(attention_mask, B, past_len + T, past_len, bool(has_pad[0]),
+                                                             bool(has_pad[1]) if len(has_pad) > 1 else None)
         if padded:
             real = attention_mask[:, past_len:] != 0
             valid = real[:, 1:] & real[:, :-1]
@@ -358,7 +380,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
         pasts = past_key_values
         for a, b in plan:
             if padded:
-                pb = _PaddedBatch(attention_mask[:, : past_len + b], past_len + a, b - a)
+                pb = _PaddedBatch(attention_mask[:, : past_len + b], past_len + a, b - a, lead=padded == PADS_LEFT)
                 x, pasts = self._hidden(input_ids[:, a:b], pasts, pb.mask, pb.position_ids, True)
             else:
                 x, pasts = self._hidden(input_ids[:, a:b], pasts, None, None, False)
@@ -506,7 +528,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
     @classmethod
     def from_pretrained(cls, path: str, device="cuda", dtype=torch.float16, **kivi):
         """`path`: a local HF checkpoint directory (config.json + *.safetensors).  `kivi`: k_bits, v_bits, group_size,
-        residual_length, max_cache_len."""
+        residual_length, max_cache_len, prefill_kernel."""
         from safetensors.torch import load_file
         cfg = make_config(json.load(open(os.path.join(path, "config.json"))), **kivi)
         with torch.device(device):
