@@ -429,6 +429,27 @@ typedef struct {
     const void* dyn_step;                              /* device kivi_mf_step or null (lengths from the fields above) */
 } kivi_gqa_decode_args;
 int kivi_gqa_decode(const kivi_gqa_decode_args* args, kivi_stream_t stream);
+/*
+ * The same step with a per-row LEAD (additive; kivi_gqa_decode is this call with lead = NULL).  `lead`: DEVICE memory, B int32, 4-byte
+ * aligned (KIVI_EALIGN otherwise, before anything is enqueued).  The host never reads it, so the call can be captured and the values
+ * rewritten between replays, like *dyn_step.  lead[b] = p is a promise of the caller about batch row b:
+ *   - its additive mask holds the fp16 minimum (-65504) at keys [0, p) -- leading pads, the front of a rebased or admitted row;
+ *   - key n - 1, the new token, is unmasked (so no row is fully masked).
+ * The mask is still passed and still applied to every key the kernels read: the lead is a licence to SKIP, it never replaces the
+ * mask.  The device clamps p to [0, Tq] for the packed keys and to [0, Tv] for the packed values; NULL promises nothing and the
+ * launches are exactly those of kivi_gqa_decode.  A lead that promises more than the mask masks is the caller's error: the results
+ * are as if those keys were masked.
+ * Honoured by the one-launch forms with a block per row (nh == nh_kv, 2 and 4 bits; nh / nh_kv = 4 at 2 and 4 bits and 8 at 2 bits,
+ * unsliced: kivi_mf_launch_plan == 1): no whole 512-token super-block of packed K or V under the lead is loaded or multiplied (the V
+ * stream skips at its 32-token blocks and its live blocks are dealt to the waves again), the score slots of skipped keys hold exactly
+ * -65504 (what KIVI_GQA_DUMP_SCORES shows there); the fp16 residual, the window, the appends and the flushes are never skipped.  A
+ * masked key's probability is an exact zero, so the skip changes no term of the step: only the grouping of the fp32 partial sums of
+ * the sV product moves with the waves' ranges.
+ * Accepted and IGNORED -- bit for bit the call without it, the mask alone keeps them correct -- by the sliced one-launch forms, the
+ * two-launch form, kivi_decode_layer (hook-state layout: it has no such argument) and kivi_mf_extend_layer.  The lead never enters
+ * kivi_mf_launch_plan: an eager step and a replayed one still take the same form.
+ */
+int kivi_gqa_decode_lead(const kivi_gqa_decode_args* args, const int32_t* lead, kivi_stream_t stream);
 /* the launch plan kivi_gqa_decode follows for a step of this geometry: 0 = two launches, S >= 1 = one launch with every row cut
  * into S slices (1: a block per row); -1: bad arguments.  dyn != 0: the plan of the step's whole geometry class (dyn_step). */
 int kivi_mf_launch_plan(int B, int nh, int nh_kv, int64_t Tq, int k_res_len, int residual_length, int flags, int bits, int dyn);
@@ -486,6 +507,11 @@ typedef struct {
 int kivi_mf_decode_layer(const kivi_mf_layer_desc* layer, int64_t* state, const void* q, int64_t q_sb, int64_t q_sh, int nh,
                          const void* knew, int64_t kn_sb, int64_t kn_sh, const void* vnew, int64_t vn_sb, int64_t vn_sh,
                          const void* mask, int64_t mask_sb, void* out, int64_t out_sb, int64_t out_sh, kivi_stream_t stream);
+/* with a per-row lead (kivi_gqa_decode_lead: B int32 of device memory or NULL; NULL = kivi_mf_decode_layer) */
+int kivi_mf_decode_layer_lead(const kivi_mf_layer_desc* layer, int64_t* state, const void* q, int64_t q_sb, int64_t q_sh, int nh,
+                              const void* knew, int64_t kn_sb, int64_t kn_sh, const void* vnew, int64_t vn_sb, int64_t vn_sh,
+                              const void* mask, int64_t mask_sb, void* out, int64_t out_sb, int64_t out_sh, const int32_t* lead,
+                              kivi_stream_t stream);
 
 /*
  * The attend phase of the same step with device-resident lengths, for hipGraph capture (see kivi_mf_step above): launches
@@ -499,6 +525,11 @@ int kivi_mf_decode_layer_dyn(const kivi_mf_layer_desc* layer, const kivi_mf_step
                              int64_t q_sb, int64_t q_sh, int nh, const void* knew, int64_t kn_sb, int64_t kn_sh, const void* vnew,
                              int64_t vn_sb, int64_t vn_sh, const void* mask, int64_t mask_sb, void* out, int64_t out_sb,
                              int64_t out_sh, kivi_stream_t stream);
+/* with a per-row lead (kivi_gqa_decode_lead): the buffer must stay where it is across replays, its values may change between them */
+int kivi_mf_decode_layer_dyn_lead(const kivi_mf_layer_desc* layer, const kivi_mf_step* host_step, const void* dev_step, const void* q,
+                                  int64_t q_sb, int64_t q_sh, int nh, const void* knew, int64_t kn_sb, int64_t kn_sh, const void* vnew,
+                                  int64_t vn_sb, int64_t vn_sh, const void* mask, int64_t mask_sb, void* out, int64_t out_sb,
+                                  int64_t out_sh, const int32_t* lead, kivi_stream_t stream);
 /*
  * kivi_mf_extend_layer: Q >= 1 new tokens of one layer at once over a cache in the KT / VT layouts (same descriptor, same state
  * array as kivi_mf_decode_layer; the ring window flag is required).  q (B, nh, Q, D), knew / vnew (B, nh_kv, Q, D) fp16 (RoPE

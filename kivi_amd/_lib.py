@@ -177,11 +177,17 @@ SIGNATURES = {
     "kivi_gqa_output": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i32,
                                _i32, _vp, _i64, _vp]),
     "kivi_gqa_decode": (_i32, [ctypes.POINTER(GqaDecodeArgs), _vp]),
+    "kivi_gqa_decode_lead": (_i32, [ctypes.POINTER(GqaDecodeArgs), _vp, _vp]),
     "kivi_mf_launch_plan": (_i32, [_i32, _i32, _i32, _i64, _i32, _i32, _i32, _i32, _i32]),
     "kivi_mf_decode_layer": (_i32, [ctypes.POINTER(MfLayerDesc), ctypes.POINTER(_i64), _vp, _i64, _i64, _i32, _vp, _i64, _i64,
                                     _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp]),
     "kivi_mf_decode_layer_dyn": (_i32, [ctypes.POINTER(MfLayerDesc), ctypes.POINTER(MfStep), _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64,
                                         _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp]),
+    # (the same two with a per-row lead -- B int32 of device memory or null -- before the stream)
+    "kivi_mf_decode_layer_lead": (_i32, [ctypes.POINTER(MfLayerDesc), ctypes.POINTER(_i64), _vp, _i64, _i64, _i32, _vp, _i64, _i64,
+                                         _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "kivi_mf_decode_layer_dyn_lead": (_i32, [ctypes.POINTER(MfLayerDesc), ctypes.POINTER(MfStep), _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64,
+                                             _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "kivi_mf_extend_layer": (_i32, [ctypes.POINTER(MfLayerDesc), ctypes.POINTER(_i64), _i32, _vp, _i64, _i64, _i64, _i32, _vp, _i64,
                                     _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "kivi_vt_pack_at": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i32, _i32, _i64, _i32, _i32, _i32, _vp]),
@@ -304,6 +310,14 @@ def mask_arg(attention_mask, B: int, kv_len: int, wider: bool = False):
         check_mask_size(attention_mask, (B, 1, 1, kv_len))
     assert attention_mask.dtype == torch.float16 and attention_mask.stride(3) == 1
     return attention_mask.data_ptr(), attention_mask.stride(0)
+
+
+def lead_arg(lead, B: int):
+    """Pointer of a decode step's per-row lead: (B,) int32 on the device, contiguous; None without one."""
+    if lead is None:
+        return None
+    assert lead.dtype == torch.int32 and tuple(lead.shape) == (B,) and lead.is_contiguous() and lead.is_cuda
+    return lead.data_ptr()
 
 
 def out_arg(out, shape: tuple, device) -> torch.Tensor:

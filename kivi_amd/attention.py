@@ -19,6 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _tuning
+from . import generation as _generation
 from . import prefill as _prefill
 from .cache import KiviCacheTuple, KiviConfig, KiviLayerCache, KiviPerformanceWarning  # noqa: F401
 from .cache_mf import KiviLayerCacheMF, make_layer_cache, supported as _mf_supported
@@ -33,13 +34,20 @@ _NATIVE_STEP = _tuning.knob("KIVI_NATIVE_STEP", "1") != "0"   # tuning sessions:
 
 def kivi_attention_decode(query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
                           layer: KiviLayerCache, attention_mask: Optional[torch.Tensor] = None,
-                          fused_kernels: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          fused_kernels: bool = True, out: Optional[torch.Tensor] = None,
+                          lead: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One decode step for one layer.  query (B, nh, 1, D), key/value (B, nh_kv, 1, D), RoPE already applied.
     Mutates `layer` in place and returns attn_output (B, nh, 1, D) fp16 (before the o_proj transpose).
     `fused_kernels=False` forces the reference-style composition (one launch per reference op).
-    `out`: optional preallocated (B, nh, 1, D) fp16 result buffer (static buffers of graph-captured callers)."""
+    `out`: optional preallocated (B, nh, 1, D) fp16 result buffer (static buffers of graph-captured callers).
+    `lead`: (B,) int32 on the device -- the caller's promise that `attention_mask` masks keys [0, lead[b]) of
+    row b (and not the new token).  The one-launch row kernels of the matrix-pipe layout then skip the packed K and V under it; every
+    other form and the hook-state layout ignore it.  None: the call as it always was."""
     layer.ensure_room(1)     # the reference's tuple grows without bound; the in-place cache doubles when it is full
-    res = layer.decode_step(query_states, key_states, value_states, attention_mask, out, fused_kernels)
+    if lead is None:
+        res = layer.decode_step(query_states, key_states, value_states, attention_mask, out, fused_kernels)
+    else:
+        res = layer.decode_step(query_states, key_states, value_states, attention_mask, out, fused_kernels, lead=lead)
     if out is not None and res is not out:
         out.copy_(res)
         return out
@@ -221,7 +229,12 @@ class LlamaAttention_KIVI(nn.Module):
                 layer = KiviLayerCacheMF.from_tuple(self.kivi, past_key_value, self._capacity(past_len + q_len), self.num_heads)
             else:  # a plain reference-style tuple: adopt it once
                 layer = KiviLayerCache.from_tuple(self.kivi, past_key_value, self._capacity(past_len + q_len))
-            if q_len > 1:
+            if isinstance(attention_mask, _generation.DecodeLead):   # config.kivi_decode_lead: the key row travels with its lead
+                if q_len > 1:                                        # (an extend ignores the lead)
+                    attn_output = kivi_attention_extend(q, k, v, layer, attention_mask.mask.expand(-1, -1, q_len, -1))
+                else:
+                    attn_output = kivi_attention_decode(q, k, v, layer, attention_mask.mask, lead=attention_mask.lead)
+            elif q_len > 1:
                 attn_output = kivi_attention_extend(q, k, v, layer, attention_mask)
             else:
                 attn_output = kivi_attention_decode(q, k, v, layer, attention_mask)

@@ -706,8 +706,9 @@ class KiviLayerCache(KiviCacheBase):
     # ------------------------------------------------------------------ decode step (llama_kivi.py:314-399)
     def decode_step(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
                     attention_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                    fused_kernels: bool = True) -> torch.Tensor:
-        """One new token: query (B, nh, 1, D), key / value (B, nh_kv, 1, D), RoPE applied -> (B, nh, 1, D) fp16 (`out` when the
+                    fused_kernels: bool = True, lead: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`lead` is accepted and ignored: this layout's kernels have no skip, the mask alone serves them.
+        One new token: query (B, nh, 1, D), key / value (B, nh_kv, 1, D), RoPE applied -> (B, nh, 1, D) fp16 (`out` when the
         one-call step ran, a new tensor otherwise).  The most fused form the shape has a kernel for: one library call, the fused
         launches with the bookkeeping in Python, or -- also with `fused_kernels=False` -- the reference's op sequence composed
         from the fused GEMVs and torch ops."""

@@ -26,7 +26,7 @@ import math
 import torch
 
 from . import _lib, _tuning, admit, rebase
-from ._lib import check_mask_size, mask_arg, out_arg, rows16
+from ._lib import check_mask_size, lead_arg, mask_arg, out_arg, rows16
 from .cache import KiviCacheBase, KiviConfig, KiviLayerCache
 from .quant import matmul, mfma, new_pack
 
@@ -333,9 +333,11 @@ class KiviLayerCacheMF(KiviCacheBase):
         return self.flags | (_lib.GQA_WINDOW_RING if self.ring else 0)
 
     def decode_step(self, query_states: torch.Tensor, key_states: torch.Tensor, value_states: torch.Tensor,
-                    attention_mask: torch.Tensor = None, out: torch.Tensor = None, fused_kernels: bool = True) -> torch.Tensor:
+                    attention_mask: torch.Tensor = None, out: torch.Tensor = None, fused_kernels: bool = True,
+                    lead: torch.Tensor = None) -> torch.Tensor:
         """One new token in ONE library call (kivi_mf_decode_layer); `fused_kernels` is the other layout's switch (this one has no
-        composed form)."""
+        composed form).  `lead`: (B,) int32 on the device, the leading keys of every row that `attention_mask`
+        masks -- the step goes through kivi_mf_decode_layer_lead, whose block-per-row forms skip them."""
         B, nh, _, D = query_states.shape
         assert nh == self.nh and B == self.B and D == self.D
         q, k, v = rows16(query_states), rows16(key_states), rows16(value_states)
@@ -349,8 +351,12 @@ class KiviLayerCacheMF(KiviCacheBase):
             hook("pre", "k", dict(B=B, nh=nh, nh_kv=self.nh_kv, K=D, N=self.k_quant_len, bits=self.cfg.k_bits,
                                   group_size=self.cfg.group_size, v_bits=self.cfg.v_bits, Tv=self.v_quant_len,
                                   k_res=self.k_res_len + 1, v_res=self.v_res_len + 1))
-        rc = fn(ctypes.byref(d), state, q.data_ptr(), q.stride(0), q.stride(1), nh, k.data_ptr(), k.stride(0), k.stride(1),
-                v.data_ptr(), v.stride(0), v.stride(1), mask_ptr, mask_sb, out.data_ptr(), out.stride(0), out.stride(1), key[1])
+        args = (ctypes.byref(d), state, q.data_ptr(), q.stride(0), q.stride(1), nh, k.data_ptr(), k.stride(0), k.stride(1),
+                v.data_ptr(), v.stride(0), v.stride(1), mask_ptr, mask_sb, out.data_ptr(), out.stride(0), out.stride(1))
+        if lead is None:
+            rc = fn(*args, key[1])
+        else:
+            rc = _lib.load().kivi_mf_decode_layer_lead(*args, lead_arg(lead, B), key[1])
         # the library writes `state` after every phase it has enqueued: read the lengths back whether or not the call succeeded
         self._load_state(state)
         if rc:
@@ -417,9 +423,9 @@ class KiviLayerCacheMF(KiviCacheBase):
         self.kv_seq_len = self.k_quant_len + self.k_res_len
 
     def decode_step_dyn(self, query_states, key_states, value_states, hs: "_lib.MfStep", dev_step: torch.Tensor, out: torch.Tensor,
-                        attention_mask: torch.Tensor = None) -> torch.Tensor:
-        """The attend phase of one step with the lengths read from `dev_step` on the device (kivi_mf_decode_layer_dyn): what a
-        hipGraph captures.  No bookkeeping happens here -- the caller advances `hs` (kivi_mf_step_advance), flushes K when due
+                        attention_mask: torch.Tensor = None, lead: torch.Tensor = None) -> torch.Tensor:
+        """The attend phase of one step with the lengths read from `dev_step` on the device (kivi_mf_decode_layer_dyn; with `lead`, a
+        static (B,) int32 buffer the caller rewrites in place, kivi_mf_decode_layer_dyn_lead): what a hipGraph captures.  No bookkeeping happens here -- the caller advances `hs` (kivi_mf_step_advance), flushes K when due
         (flush_k) and applies the lengths (apply_step); buffers must be static across replays."""
         B, nh, _, D = query_states.shape
         assert nh == self.nh and B == self.B and D == self.D
@@ -431,9 +437,12 @@ class KiviLayerCacheMF(KiviCacheBase):
         d, _, key, _, _ = self._desc(nh, query_states.device)
         d.flags = self._flags()
         q, k, v = query_states, key_states, value_states
-        rc = _lib.load().kivi_mf_decode_layer_dyn(ctypes.byref(d), ctypes.byref(hs), dev_step.data_ptr(), q.data_ptr(), q.stride(0), q.stride(1),
-                                                  nh, k.data_ptr(), k.stride(0), k.stride(1), v.data_ptr(), v.stride(0), v.stride(1),
-                                                  mask_ptr, mask_sb, out.data_ptr(), out.stride(0), out.stride(1), key[1])
+        args = (ctypes.byref(d), ctypes.byref(hs), dev_step.data_ptr(), q.data_ptr(), q.stride(0), q.stride(1), nh, k.data_ptr(), k.stride(0),
+                k.stride(1), v.data_ptr(), v.stride(0), v.stride(1), mask_ptr, mask_sb, out.data_ptr(), out.stride(0), out.stride(1))
+        if lead is None:
+            rc = _lib.load().kivi_mf_decode_layer_dyn(*args, key[1])
+        else:
+            rc = _lib.load().kivi_mf_decode_layer_dyn_lead(*args, lead_arg(lead, B), key[1])
         _lib.check(rc, "kivi_mf_decode_layer_dyn")
         return out
 

@@ -685,7 +685,8 @@ int kivi_mf_run_k(void* k_args, int units, int bits, hipStream_t s);
 int kivi_mf_run_v(const void* v_args, int prob, int bits, hipStream_t s);
 int kivi_mf_run_row_sp(const void* p, int64_t p_sb, int64_t p_sh, int B, int nh, int nh_kv, int64_t T, const int* range, int* sp,
                        hipStream_t s);
-int kivi_mf_run_row(void* k_args, const void* v_args, int units, int64_t n_rows, int dump, int bits, int S, int res_cap, int slice_kernel, hipStream_t s);
+int kivi_mf_run_row(void* k_args, const void* v_args, int units, int64_t n_rows, int dump, int bits, int S, int res_cap, int slice_kernel, const int32_t* lead,
+                    hipStream_t s);
 
 // Launch plan of a step whose LONGEST row has n_rows keys (nsbk super-blocks of packed keys + up to res_cap + 1 fp16 ones):
 //   0      two launches (mf_k_kernel -> score rows + statistics in memory -> mf_v_kernel)
@@ -869,8 +870,13 @@ extern "C" int kivi_gqa_output(const void* probs, int64_t p_sb, int64_t p_sh, co
     return kivi_mf_run_v(&v, 1, bits, s);
 }
 
-extern "C" int kivi_gqa_decode(const kivi_gqa_decode_args* p, kivi_stream_t stream) {
+extern "C" int kivi_gqa_decode(const kivi_gqa_decode_args* p, kivi_stream_t stream) { return kivi_gqa_decode_lead(p, nullptr, stream); }
+
+// The step with a per-row lead (include/kivi_hip.h): device memory, never read here.  It does not enter the
+// launch plan; the one-launch forms with a block per row honour it (kivi_mf_run_row), every other form runs as without it.
+extern "C" int kivi_gqa_decode_lead(const kivi_gqa_decode_args* p, const int32_t* lead, kivi_stream_t stream) {
     KIVI_REQUIRE(p != nullptr, KIVI_EINVAL, "kivi_gqa_decode: null arguments");
+    KIVI_REQUIRE((uintptr_t)lead % 4 == 0, KIVI_EALIGN, "kivi_gqa_decode: lead must be 4-byte aligned");
     {   // the sticky device-side error of an EARLIER sliced launch (include/kivi_hip.h, kivi_device_error): reported once, here, before
         // anything of this step is enqueued; the counters of that launch are back at zero, so the caller may simply call again
         int eu = -1;
@@ -1000,7 +1006,7 @@ extern "C" int kivi_gqa_decode(const kivi_gqa_decode_args* p, kivi_stream_t stre
     if (plan >= 1) {
         if (plan > 1) { v.S = plan; v.nslot = plan; v.win_blocks = 0; }
         return kivi_mf_run_row(&k, &v, units, n_rows, (p->flags & KIVI_GQA_DUMP_SCORES) != 0, bits, plan, p->residual_length,
-                               ((p->flags >> 8) & 0xFF) != 0, s);
+                               ((p->flags >> 8) & 0xFF) != 0, lead, s);
     }
     int rc = skipk ? 0 : kivi_mf_run_k(&k, units, bits, s);
     if (rc) return rc;

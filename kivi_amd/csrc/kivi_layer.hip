@@ -148,7 +148,16 @@ extern "C" int kivi_mf_decode_layer(const kivi_mf_layer_desc* L, int64_t* st, co
                                     const void* knew, int64_t kn_sb, int64_t kn_sh, const void* vnew, int64_t vn_sb,
                                     int64_t vn_sh, const void* mask, int64_t mask_sb, void* out, int64_t out_sb,
                                     int64_t out_sh, kivi_stream_t stream) {
+    return kivi_mf_decode_layer_lead(L, st, q, q_sb, q_sh, nh, knew, kn_sb, kn_sh, vnew, vn_sb, vn_sh, mask, mask_sb, out, out_sb, out_sh, nullptr, stream);
+}
+
+// The same with a per-row lead (include/kivi_hip.h): handed to the attend phase, never read on the host
+extern "C" int kivi_mf_decode_layer_lead(const kivi_mf_layer_desc* L, int64_t* st, const void* q, int64_t q_sb, int64_t q_sh, int nh,
+                                         const void* knew, int64_t kn_sb, int64_t kn_sh, const void* vnew, int64_t vn_sb,
+                                         int64_t vn_sh, const void* mask, int64_t mask_sb, void* out, int64_t out_sb,
+                                         int64_t out_sh, const int32_t* lead, kivi_stream_t stream) {
     KIVI_REQUIRE(L && st && q && knew && vnew && out, KIVI_EINVAL, "kivi_mf_decode_layer: null argument");
+    KIVI_REQUIRE((uintptr_t)lead % 4 == 0, KIVI_EALIGN, "kivi_mf_decode_layer: lead must be 4-byte aligned");
     int64_t Tq = st[0], kres = st[1], Tv = st[2], wstart = st[3], vres = st[4], kv = st[5];
     const int R = L->residual_length;
     KIVI_REQUIRE(R > 0 && R % 32 == 0 && R <= 128 && Tq >= 0 && Tq % 32 == 0 && kres >= 0 && kres <= R && Tv >= 0 && wstart >= 0 &&
@@ -206,7 +215,7 @@ extern "C" int kivi_mf_decode_layer(const kivi_mf_layer_desc* L, int64_t* st, co
     const kivi_mf_step hs = {Tq, Tv, (int32_t)kres, (int32_t)vres, (int32_t)wstart, flush};
     const kivi_gqa_decode_args a = mf_decode_args(L, &hs, nullptr, q, q_sb, q_sh, nh, knew, kn_sb, kn_sh, vnew, vn_sb, vn_sh, mask, mask_sb,
                                                   out, out_sb, out_sh);
-    int rc = kivi_gqa_decode(&a, stream);
+    int rc = kivi_gqa_decode_lead(&a, lead, stream);
     if (rc) return rc;            // nothing of the step has been committed
     kres += 1;
     vres += 1;
@@ -230,7 +239,17 @@ extern "C" int kivi_mf_decode_layer_dyn(const kivi_mf_layer_desc* L, const kivi_
                                         int64_t q_sb, int64_t q_sh, int nh, const void* knew, int64_t kn_sb, int64_t kn_sh,
                                         const void* vnew, int64_t vn_sb, int64_t vn_sh, const void* mask, int64_t mask_sb, void* out,
                                         int64_t out_sb, int64_t out_sh, kivi_stream_t stream) {
+    return kivi_mf_decode_layer_dyn_lead(L, hs, dev_step, q, q_sb, q_sh, nh, knew, kn_sb, kn_sh, vnew, vn_sb, vn_sh, mask, mask_sb, out, out_sb, out_sh,
+                                         nullptr, stream);
+}
+
+// The same with a per-row lead: like the lengths it is read on the device only, so it may be rewritten between replays
+extern "C" int kivi_mf_decode_layer_dyn_lead(const kivi_mf_layer_desc* L, const kivi_mf_step* hs, const void* dev_step, const void* q,
+                                             int64_t q_sb, int64_t q_sh, int nh, const void* knew, int64_t kn_sb, int64_t kn_sh,
+                                             const void* vnew, int64_t vn_sb, int64_t vn_sh, const void* mask, int64_t mask_sb, void* out,
+                                             int64_t out_sb, int64_t out_sh, const int32_t* lead, kivi_stream_t stream) {
     KIVI_REQUIRE(L && hs && dev_step && q && knew && vnew && out, KIVI_EINVAL, "kivi_mf_decode_layer_dyn: null argument");
+    KIVI_REQUIRE((uintptr_t)lead % 4 == 0, KIVI_EALIGN, "kivi_mf_decode_layer_dyn: lead must be 4-byte aligned");
     const int R = L->residual_length;
     const int64_t kv = hs->Tq + hs->k_res_len;
     KIVI_REQUIRE(R > 0 && R % 32 == 0 && R <= 128 && hs->Tq >= 0 && hs->Tq % 32 == 0 && hs->k_res_len >= 0 && hs->k_res_len < R && hs->Tv >= 0 &&
@@ -253,7 +272,7 @@ extern "C" int kivi_mf_decode_layer_dyn(const kivi_mf_layer_desc* L, const kivi_
                  (long long)L->s_pitch);
     const kivi_gqa_decode_args a = mf_decode_args(L, hs, dev_step, q, q_sb, q_sh, nh, knew, kn_sb, kn_sh, vnew, vn_sb, vn_sh, mask, mask_sb,
                                                   out, out_sb, out_sh);
-    return kivi_gqa_decode(&a, stream);
+    return kivi_gqa_decode_lead(&a, lead, stream);
 }
 
 extern "C" int kivi_mf_step_advance(kivi_mf_step* s, int R, int64_t window_rows) {

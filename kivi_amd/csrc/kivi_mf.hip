@@ -21,6 +21,7 @@
 #include "kivi_quant.h"
 #include "kivi_gqa_roles.h"
 #include "kivi_mf_dev.h"
+#include "kivi_lead_plan.h"
 
 namespace {
 
@@ -447,8 +448,12 @@ __global__ __launch_bounds__(256) void mf_row_sp_kernel(const uint16_t* p, int64
 // OCC: waves per SIMD the register budget allows (4: 128 registers; 2: the few-rows instantiation with rings of 8 -- at most one
 // block per CU is resident anyway, so a wave may hold a half super-block of K and 8 blocks of V in flight)
 // BITS = 4 (round 6): 4-bit K / V of a multi-head model (Llama-2-7B / LongChat-7B with KIVI-4) over the 4-bit super-blocks
-template <int KRING, int VRING, int NW, bool DBG = false, bool PRIO = true, int OCC = 4, int BITS = 2>
-__global__ __launch_bounds__(NW * 64, OCC) void mf_row_kernel(const GqaKArgs ak_in, const GqaVArgs av_in, int n_pad) {
+// LEAD (kivi_lead_plan.h): lead[b] keys at the front of batch row b are masked -- the whole super-blocks of packed
+// K under it are neither read nor multiplied (their score slots hold the clamped fp16 minimum the mask would leave), the packed V
+// blocks under it are not streamed, and the live V blocks are dealt to the waves again.  A template parameter: the instantiations
+// without it compile from the paths they always had (`lead` is an unread kernel argument there).
+template <int KRING, int VRING, int NW, bool DBG = false, bool PRIO = true, int OCC = 4, int BITS = 2, bool LEAD = false>
+__global__ __launch_bounds__(NW * 64, OCC) void mf_row_kernel(const GqaKArgs ak_in, const GqaVArgs av_in, int n_pad, const int32_t* lead) {
     constexpr int NTH = NW * 64;
     GqaKArgs ak = ak_in;
     GqaVArgs av = av_in;
@@ -475,6 +480,12 @@ __global__ __launch_bounds__(NW * 64, OCC) void mf_row_kernel(const GqaKArgs ak_
     const int Tq = (int)ak.Tq, Tv = (int)av.Tv;
     const int L = ak.res_len + 1;                                  // residual keys incl. the new one
     const int n = Tq + L;                                          // row length
+    int sb_k0 = 0, vb0 = 0;                                        // LEAD: first live super-block of packed K / block of packed V (wave-uniform)
+    if constexpr (LEAD) {
+        const int ld = __builtin_amdgcn_readfirstlane(lead[b]);
+        sb_k0 = kivi_lead_k_first(ld, Tq);
+        vb0 = kivi_lead_v_first(ld, Tv);
+    }
     // range flags of the unit's stores (kivi_mfma_layout.h): where q'' / p'' are placed; read before this step's V flush can set one
     const int krsh = mf_range_shift(__builtin_amdgcn_readfirstlane(ak.range[unit])), vrsh = mf_range_shift(__builtin_amdgcn_readfirstlane(av.range[unit]));
 
@@ -496,6 +507,12 @@ __global__ __launch_bounds__(NW * 64, OCC) void mf_row_kernel(const GqaKArgs ak_
         const int last = wave + (seq.n_sb - 1) * NW;                // this wave's last super-block
         const int NG = Tq >> 5;
         seq.ng_total = seq.n_sb > 0 ? 16 * (seq.n_sb - 1) + ((NG - 16 * last) < 16 ? (NG - 16 * last) : 16) : 0;
+        if constexpr (LEAD) {                                       // the same deal over the super-blocks from sb_k0 on
+            const KiviLeadKWalk kw = kivi_lead_k_wave(sb_k0, ak.nsb, Tq, wave, NW);
+            seq.sb_first = kw.sb_first;
+            seq.n_sb = kw.n_sb;
+            seq.ng_total = kw.ng_total;
+        }
         mf_k_seq1<KRING, BITS>(rk, seq, qrow, q_lds[wave], krsh,
                          [&](int sb, int tt, float v) {
                              const uint16_t h = kivi_scaled_score(f2h_bits(v), ak.inv_scale, false, 0);
@@ -512,8 +529,13 @@ __global__ __launch_bounds__(NW * 64, OCC) void mf_row_kernel(const GqaKArgs ak_
     const rsrc_t rv = make_rsrc(mf_sb(av.vt, b, hk, 0), (uint32_t)((int64_t)av.nsb * av.vt.sb_s * 4));
     const int NB = (Tv + 31) >> 5;
     const int nbw = (NB + NW - 1) / NW;
-    const int b_lo = wave * nbw;
-    const int b_hi = (b_lo + nbw < NB) ? b_lo + nbw : NB;
+    int b_lo = wave * nbw;
+    int b_hi = (b_lo + nbw < NB) ? b_lo + nbw : NB;
+    if constexpr (LEAD) {                                           // the live blocks [vb0, NB), dealt again
+        const KiviLeadVRange vr = kivi_lead_v_wave(vb0, NB, wave, NW);
+        b_lo = vr.b_lo;
+        b_hi = vr.b_hi;
+    }
     MfVStream<1, VRING, false, BITS> vs;
     vs.prime(rv, (uint32_t)(av.vt.sb_s * 4), b_lo, b_hi);
     // ---- residual scores q . [K_full | k_new] (fp32 accumulate, one rounding: the reference's fp16 matmul, :337) + K append
@@ -541,6 +563,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void mf_row_kernel(const GqaKArgs ak_
         }
     }
     for (int j = n + (int)threadIdx.x; j < n_pad; j += NTH) row[j] = 0xFC00u;      // -inf past the row
+    if constexpr (LEAD) {                                           // the skipped super-blocks: -65504, what scaled score + mask clamps to
+        for (int j = (int)threadIdx.x * 8; j < kivi_lead_k_fill(sb_k0, Tq); j += NTH * 8) *(u32x4*)(row + j) = u32x4{0xFBFFFBFFu, 0xFBFFFBFFu, 0xFBFFFBFFu, 0xFBFFFBFFu};
+    }
     stamp(4);
     __syncthreads();
     stamp(5);
@@ -665,9 +690,12 @@ __device__ __forceinline__ void mf_probs_inplace_row(uint16_t* row, int t0, int 
 // measures FASTER than the in-stream form for a block that holds a whole row (BASELINE config 4, one box, alternating: 97.8 us
 // against 104.0-104.8: the exponentials cost the same wherever they run, and inside the streams they delay a wave's next request
 // -- profiles/r05_row4_flows.log); the in-stream form is what makes slices possible (their statistics must exist before the exchange).
-template <int KRING, int VRING, int NW, bool DBG = false, bool VHL = true, int R = 4, int BITS = 2, int OCC = 2, bool PSM = false>
-__global__ __launch_bounds__(NW * 64, OCC) void mf_row4_kernel(const GqaKArgs ak_in, const GqaVArgs av_in, int n_pad, int S) {
+// LEAD (a block per row in the phase-softmax flow only; see mf_row_kernel): the whole super-blocks of packed K and the blocks of packed V
+// under lead[b] are skipped, the live ones dealt to the four waves again; the skipped score slots of the R rows hold -65504.
+template <int KRING, int VRING, int NW, bool DBG = false, bool VHL = true, int R = 4, int BITS = 2, int OCC = 2, bool PSM = false, bool LEAD = false>
+__global__ __launch_bounds__(NW * 64, OCC) void mf_row4_kernel(const GqaKArgs ak_in, const GqaVArgs av_in, int n_pad, int S, const int32_t* lead) {
     constexpr int NTH = NW * 64;
+    static_assert(!LEAD || (PSM && NW == 4), "the lead is honoured by the unsliced four-wave phase-softmax blocks");
     // NW = 6 (round 6, a block per row only): SIX waves per block, two blocks per CU = three waves per SIMD in <= 168 registers -- the
     // LDS (four score rows of up to 9344 keys: 73 KiB) allows two blocks per CU whatever their size, so the third wave per SIMD the
     // latency-bound streams of this kernel lacked comes from wider blocks, not from more of them.
@@ -744,6 +772,12 @@ __global__ __launch_bounds__(NW * 64, OCC) void mf_row4_kernel(const GqaKArgs ak
         sb_hi = last ? ak.nsb : (hi < last_start ? hi : last_start);
     }
     const int tok0 = sb_lo * KIVI_MF_SB_TOKENS;                   // the rows are indexed by token - tok0
+    int sb_k0 = 0, vb0 = 0;                                        // LEAD (S = 1): first live super-block of packed K / block of packed V (wave-uniform)
+    if constexpr (LEAD) {
+        const int ld = __builtin_amdgcn_readfirstlane(lead[b]);
+        sb_k0 = kivi_lead_k_first(ld, Tq);
+        vb0 = kivi_lead_v_first(ld, Tv);
+    }
 
     // ---- packed qK^T: wave w walks super-blocks sb_lo + w, sb_lo + w + NW, ...; the rows hold the SCALED scores
     // fp16(fp16(s) * inv_scale) (:339; = kivi_scaled_score): two at a time -- one packed conversion, two v_fma_mix
@@ -776,6 +810,12 @@ __global__ __launch_bounds__(NW * 64, OCC) void mf_row4_kernel(const GqaKArgs ak
             seq.g_first = g0 & 15;
             seq.n_sb = g1 > g0 ? ((g1 + 15) >> 4) - seq.sb_first : 0;
             seq.ng_total = g1 > g0 ? g1 - 16 * seq.sb_first : 0;
+        }
+        if constexpr (LEAD) {                                       // the same deal over the super-blocks from sb_k0 on
+            const KiviLeadKWalk kw = kivi_lead_k_wave(sb_k0, sb_hi, Tq, wave, NW);
+            seq.sb_first = kw.sb_first;
+            seq.n_sb = kw.n_sb;
+            seq.ng_total = kw.ng_total;
         }
         // a finished super-block: [mask in place (:366-372),] (max, sum exp(x - max)) of the segment of every row
         auto seg_done = [&](int sb, int ng) {
@@ -865,8 +905,13 @@ __global__ __launch_bounds__(NW * 64, OCC) void mf_row4_kernel(const GqaKArgs ak
     int vb_hi = ((sb_hi * KIVI_MF_SB_TOKENS < Tv ? sb_hi * KIVI_MF_SB_TOKENS : Tv) + 31) >> 5;
     if (vb_hi < vb_lo) vb_hi = vb_lo;
     const int nbw = (vb_hi - vb_lo + NW - 1) / NW;
-    const int b_lo = vb_lo + wave * nbw;
-    const int b_hi = (b_lo + nbw < vb_hi) ? b_lo + nbw : vb_hi;
+    int b_lo = vb_lo + wave * nbw;
+    int b_hi = (b_lo + nbw < vb_hi) ? b_lo + nbw : vb_hi;
+    if constexpr (LEAD) {                                           // the live blocks [vb0, vb_hi), dealt again
+        const KiviLeadVRange vr = kivi_lead_v_wave(vb0, vb_hi, wave, NW);
+        b_lo = vr.b_lo;
+        b_hi = vr.b_hi;
+    }
     MfVStream<R, VRING, VHL, BITS> vs;
     vs.prime(rv, (uint32_t)(av.vt.sb_s * 4), b_lo, b_hi);
     // ---- residual scores q . [K_full | k_new] of the R heads (:337: fp32 accumulate, one rounding = the reference's fp16 matmul)
@@ -930,6 +975,12 @@ __global__ __launch_bounds__(NW * 64, OCC) void mf_row4_kernel(const GqaKArgs ak
     if constexpr (PSM) {                                           // -inf past the rows (the softmax reads whole 4-score chunks)
         const int n = Tq + L;
         for (int j = (int)threadIdx.x; j < R * (n_pad - n); j += NTH) rows[(j / (n_pad - n)) * n_pad + n + j % (n_pad - n)] = 0xFC00u;
+    }
+    if constexpr (LEAD) {                                           // the skipped super-blocks: -65504, what scaled score + mask clamps to
+#pragma unroll
+        for (int rr = 0; rr < R; rr++)
+            for (int j = (int)threadIdx.x * 8; j < kivi_lead_k_fill(sb_k0, Tq); j += NTH * 8)
+                *(u32x4*)(rows + rr * n_pad + j) = u32x4{0xFBFFFBFFu, 0xFBFFFBFFu, 0xFBFFFBFFu, 0xFBFFFBFFu};
     }
     stamp(4);
     // the fp16 window rows (and the token leaving it) are requested before the barrier and used after the statistics
@@ -1261,7 +1312,8 @@ static int mf_cu_count() {
 // n_rows: the longest row the launch must hold (= Tq + k_res_len + 1, or the bound of the step's geometry class when the lengths
 // are device-resident).  S: slices per row; res_cap: residual_length (the fp16 keys a last slice may hold); slice_kernel: nh == nh_kv
 // with S = 1 through mf_row4_kernel<R = 1> instead of mf_row_kernel (KIVI_GQA_SLICES(1): A/B).
-int kivi_mf_run_row(void* k_args, const void* v_args, int units, int64_t n_rows, int dump, int bits, int S, int res_cap, int slice_kernel, hipStream_t s) {
+int kivi_mf_run_row(void* k_args, const void* v_args, int units, int64_t n_rows, int dump, int bits, int S, int res_cap, int slice_kernel, const int32_t* lead,
+                    hipStream_t s) {
     GqaKArgs& k = *(GqaKArgs*)k_args;
     const GqaVArgs& v = *(const GqaVArgs*)v_args;
     const int64_t n = n_rows;
@@ -1303,6 +1355,7 @@ int kivi_mf_run_row(void* k_args, const void* v_args, int units, int64_t n_rows,
 #endif
         if (S == 1) { k.ticket = nullptr; k.xcount = nullptr; k.err_ws = nullptr; k.err_host = nullptr; }
         static unsigned long long opt8 = 0, opt4 = 0, opt44 = 0, opt1 = 0, opt14 = 0, opt8p = 0, opt4p = 0, opt44p = 0;
+        static unsigned long long opt8pl = 0, opt4pl = 0, opt44pl = 0, opt4o3l = 0;   // the same with the lead honoured (a block per row)
         // a block per row (S = 1): the phase-softmax flow (PSM, see mf_row4_kernel); slices: the in-stream flow
         bool psm = S == 1 && R != 1;
 #ifdef KIVI_TUNING
@@ -1313,12 +1366,13 @@ int kivi_mf_run_row(void* k_args, const void* v_args, int units, int64_t n_rows,
     do {                                                                                           \
         const int rc = mf_lds_opt_in(mf_row4_kernel<__VA_ARGS__>, &OPT, "mf_row4");                \
         if (rc) return rc;                                                                         \
-        KIVI_LAUNCH_LDS((mf_row4_kernel<__VA_ARGS__>), grid, dim3(THREADS), lds, s, k, v, n_pad, S); \
+        KIVI_LAUNCH_LDS((mf_row4_kernel<__VA_ARGS__>), grid, dim3(THREADS), lds, s, k, v, n_pad, S, lead); \
         return kivi_launch_status("mf_row4");                                                      \
     } while (0)
 #define KIVI_ROW4_LAUNCH(OPT, ...) KIVI_ROW4_LAUNCH_T(OPT, 256, __VA_ARGS__)
         if (R == 1 && bits == 4) KIVI_ROW4_LAUNCH(opt14, 2, 3, 4, false, false, 1, 4, 4);
         if (R == 1) KIVI_ROW4_LAUNCH(opt1, 2, 3, 4, false, false, 1, 2, 4);
+        if (R == 8 && psm && lead) KIVI_ROW4_LAUNCH(opt8pl, 4, 2, 4, false, false, 8, 2, 2, true, true);
         if (R == 8 && psm) KIVI_ROW4_LAUNCH(opt8p, 4, 2, 4, false, false, 8, 2, 2, true);
         if (R == 8) KIVI_ROW4_LAUNCH(opt8, 4, 2, 4, false, false, 8);
 #ifdef KIVI_TUNING
@@ -1329,6 +1383,7 @@ int kivi_mf_run_row(void* k_args, const void* v_args, int units, int64_t n_rows,
         if (bits == 4 && psm && f46 && atoi(f46) == 23) KIVI_ROW4_LAUNCH_T(opt446[1], 384, 2, 3, 6, false, true, 4, 4, 3, true);
         if (bits == 4 && psm && f46 && atoi(f46) == 43) KIVI_ROW4_LAUNCH_T(opt446[2], 384, 4, 3, 6, false, true, 4, 4, 3, true);
 #endif
+        if (bits == 4 && psm && lead) KIVI_ROW4_LAUNCH(opt44pl, 4, 3, 4, false, true, 4, 4, 2, true, true);
         if (bits == 4 && psm) KIVI_ROW4_LAUNCH(opt44p, 4, 3, 4, false, true, 4, 4, 2, true);
         if (bits == 4) KIVI_ROW4_LAUNCH(opt44, 4, 3, 4, false, true, 4, 4);
 #ifdef KIVI_TUNING
@@ -1381,8 +1436,10 @@ int kivi_mf_run_row(void* k_args, const void* v_args, int units, int64_t n_rows,
             static const char* fo3 = KIVI_TUNE_ENV("KIVI_MF_ROW4_OCC3");     // 0 / 1: never / whenever the rows fit (A/B)
             if (fo3) three = R == 4 && bits == 2 && psm && atoi(fo3) != 0;
 #endif
+            if (three && lead) KIVI_ROW4_LAUNCH(opt4o3l, 2, 2, 4, false, true, 4, 2, 3, true, true);
             if (three) KIVI_ROW4_LAUNCH(opt4o3, 2, 2, 4, false, true, 4, 2, 3, true);
         }
+        if (psm && lead) KIVI_ROW4_LAUNCH(opt4pl, 4, 3, 4, false, true, 4, 2, 2, true, true);
         if (psm) KIVI_ROW4_LAUNCH(opt4p, 4, 3, 4, false, true, 4, 2, 2, true);
 #ifdef KIVI_TUNING
         static unsigned long long opt4s3 = 0;
@@ -1404,13 +1461,13 @@ int kivi_mf_run_row(void* k_args, const void* v_args, int units, int64_t n_rows,
     static const char* fr = KIVI_TUNE_ENV("KIVI_MF_ROW_RINGS");          // "<K ring><V ring>", e.g. 42
     const int rings = fr ? atoi(fr) : 23;
     static const char* np = KIVI_TUNE_ENV("KIVI_MF_ROW_NOPRIO");         // A/B of the raised priority
-    if (v.dbg && np) { KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 4, true, false>), grid, dim3(256), lds, s, k, v, n_pad); return kivi_launch_status("mf_row"); }
-    if (v.dbg) { KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 4, true>), grid, dim3(256), lds, s, k, v, n_pad); return kivi_launch_status("mf_row"); }
-    if (np) { KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 4, false, false>), grid, dim3(256), lds, s, k, v, n_pad); return kivi_launch_status("mf_row"); }
-    if (rings == 24) { KIVI_LAUNCH_LDS((mf_row_kernel<2, 4, 4>), grid, dim3(256), lds, s, k, v, n_pad); return kivi_launch_status("mf_row"); }
-    if (rings == 22) { KIVI_LAUNCH_LDS((mf_row_kernel<2, 2, 4>), grid, dim3(256), lds, s, k, v, n_pad); return kivi_launch_status("mf_row"); }
-    if (rings == 43) { KIVI_LAUNCH_LDS((mf_row_kernel<4, 3, 4>), grid, dim3(256), lds, s, k, v, n_pad); return kivi_launch_status("mf_row"); }
-    if (rings == 42) { KIVI_LAUNCH_LDS((mf_row_kernel<4, 2, 4>), grid, dim3(256), lds, s, k, v, n_pad); return kivi_launch_status("mf_row"); }
+    if (v.dbg && np) { KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 4, true, false>), grid, dim3(256), lds, s, k, v, n_pad, lead); return kivi_launch_status("mf_row"); }
+    if (v.dbg) { KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 4, true>), grid, dim3(256), lds, s, k, v, n_pad, lead); return kivi_launch_status("mf_row"); }
+    if (np) { KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 4, false, false>), grid, dim3(256), lds, s, k, v, n_pad, lead); return kivi_launch_status("mf_row"); }
+    if (rings == 24) { KIVI_LAUNCH_LDS((mf_row_kernel<2, 4, 4>), grid, dim3(256), lds, s, k, v, n_pad, lead); return kivi_launch_status("mf_row"); }
+    if (rings == 22) { KIVI_LAUNCH_LDS((mf_row_kernel<2, 2, 4>), grid, dim3(256), lds, s, k, v, n_pad, lead); return kivi_launch_status("mf_row"); }
+    if (rings == 43) { KIVI_LAUNCH_LDS((mf_row_kernel<4, 3, 4>), grid, dim3(256), lds, s, k, v, n_pad, lead); return kivi_launch_status("mf_row"); }
+    if (rings == 42) { KIVI_LAUNCH_LDS((mf_row_kernel<4, 2, 4>), grid, dim3(256), lds, s, k, v, n_pad, lead); return kivi_launch_status("mf_row"); }
 #endif
     // few rows (under ~2 four-wave blocks per CU): eight waves per row, the row's own waves hide the latency
     static const char* f8 = KIVI_TUNE_ENV("KIVI_MF_ROW_NW8");            // tuning builds: 0 / 1 forces either
@@ -1420,14 +1477,24 @@ int kivi_mf_run_row(void* k_args, const void* v_args, int units, int64_t n_rows,
     // ring (2 KiB of K / 3 KiB of V in flight stream ~3 GB/s per wave): rings of 8 blocks, 256 registers per wave
     static const char* fdp = KIVI_TUNE_ENV("KIVI_MF_ROW_DEEP");          // tuning builds: 0 / 1 forces either
     const bool deep = fdp ? atoi(fdp) != 0 : units <= 256;
-    if (bits == 4) {                                               // 4-bit multi-head rows (round 6): a ring slot is 2 x 16 bytes -- rings of (2, 3) fit four waves per SIMD all the same
-        if (deep) KIVI_LAUNCH_LDS((mf_row_kernel<4, 4, 8, false, true, 2, 4>), grid, dim3(512), lds, s, k, v, n_pad);
-        else if (nw8) KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 8, false, true, 4, 4>), grid, dim3(512), lds, s, k, v, n_pad);
-        else KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 4, false, true, 4, 4>), grid, dim3(256), lds, s, k, v, n_pad);
+    if (lead) {                                                    // the same three forms at either width with the lead honoured
+        if (bits == 4) {
+            if (deep) KIVI_LAUNCH_LDS((mf_row_kernel<4, 4, 8, false, true, 2, 4, true>), grid, dim3(512), lds, s, k, v, n_pad, lead);
+            else if (nw8) KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 8, false, true, 4, 4, true>), grid, dim3(512), lds, s, k, v, n_pad, lead);
+            else KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 4, false, true, 4, 4, true>), grid, dim3(256), lds, s, k, v, n_pad, lead);
+        } else if (deep) KIVI_LAUNCH_LDS((mf_row_kernel<8, 8, 8, false, true, 2, 2, true>), grid, dim3(512), lds, s, k, v, n_pad, lead);
+        else if (nw8) KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 8, false, true, 4, 2, true>), grid, dim3(512), lds, s, k, v, n_pad, lead);
+        else KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 4, false, true, 4, 2, true>), grid, dim3(256), lds, s, k, v, n_pad, lead);
         return kivi_launch_status("mf_row");
     }
-    if (deep) KIVI_LAUNCH_LDS((mf_row_kernel<8, 8, 8, false, true, 2>), grid, dim3(512), lds, s, k, v, n_pad);
-    else if (nw8) KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 8>), grid, dim3(512), lds, s, k, v, n_pad);
-    else KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 4>), grid, dim3(256), lds, s, k, v, n_pad);
+    if (bits == 4) {                                               // 4-bit multi-head rows (round 6): a ring slot is 2 x 16 bytes -- rings of (2, 3) fit four waves per SIMD all the same
+        if (deep) KIVI_LAUNCH_LDS((mf_row_kernel<4, 4, 8, false, true, 2, 4>), grid, dim3(512), lds, s, k, v, n_pad, lead);
+        else if (nw8) KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 8, false, true, 4, 4>), grid, dim3(512), lds, s, k, v, n_pad, lead);
+        else KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 4, false, true, 4, 4>), grid, dim3(256), lds, s, k, v, n_pad, lead);
+        return kivi_launch_status("mf_row");
+    }
+    if (deep) KIVI_LAUNCH_LDS((mf_row_kernel<8, 8, 8, false, true, 2>), grid, dim3(512), lds, s, k, v, n_pad, lead);
+    else if (nw8) KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 8>), grid, dim3(512), lds, s, k, v, n_pad, lead);
+    else KIVI_LAUNCH_LDS((mf_row_kernel<2, 3, 4>), grid, dim3(256), lds, s, k, v, n_pad, lead);
     return kivi_launch_status("mf_row");
 }

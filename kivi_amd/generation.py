@@ -55,14 +55,39 @@ def padding_prompt_mask(mask: torch.Tensor) -> torch.Tensor:
     return causal[None, None].repeat(B, 1, 1, 1).masked_fill_((mask == 0)[:, None, None, :], _MIN16)
 
 
+def leading_pads(mask2d: torch.Tensor) -> torch.Tensor:
+    """(B,) int32 on the mask's device: the zeros at the front of every row of a 2D padding mask (0 for a row without pads) --
+    derived on the device, never read on the host."""
+    return ((mask2d != 0).cumsum(-1) == 0).sum(-1).to(torch.int32)
+
+
+class DecodeLead:
+    """What a padded decode step hands its attention modules in place of the additive key row with config.kivi_decode_lead (DESIGN.md
+    section 21): the row itself, `mask` (B, 1, 1, kv length incl. the new token), and `lead` (B,) int32, the leading keys of every
+    row that it masks.  The row kernels skip them; the mask is applied to everything they read all the same."""
+
+    def __init__(self, mask: torch.Tensor, lead: torch.Tensor):
+        self.mask, self.lead = mask, lead
+
+
+def decode_key_row(mask2d: torch.Tensor, lead: bool = False):
+    """The additive key row of a decode step over the 2D mask (B, kv length incl. the new token); `lead`: as a DecodeLead, the lead
+    derived from the same mask -- so a mask an admission or a rebase has changed brings its own."""
+    row = padding_key_row(mask2d)
+    return DecodeLead(row, leading_pads(mask2d)) if lead else row
+
+
 class _PaddedBatch:
     """What a left-padded batch adds to the passes of one call, derived once from HF's 2D mask (B, past_len + T): `mask` and
     `position_ids` of the pass over the T new tokens (the prompt's 4D causal + padding mask; with a history, the key row expanded
     over the chunk), then per decode step a view of the key row one column longer (new tokens are real) and the advancing
     position.  `beams`: the decode steps run on every row repeated that often (the prompt pass does not).  `lead`: the prompt pass
-    (no history) runs the prefill kernel -- its `mask` is a PromptLead, the leading pads of every row, and no 4D mask is built."""
+    (no history) runs the prefill kernel -- its `mask` is a PromptLead, the leading pads of every row, and no 4D mask is built.
+    `decode_lead` (config.kivi_decode_lead): every decode step gets its key row as a DecodeLead, with the leading zeros of every
+    row of the mask (repeated over beams like the row)."""
 
-    def __init__(self, mask2d: torch.Tensor, past_len: int, T: int, max_new_tokens: int = 0, beams: int = 1, lead: bool = False):
+    def __init__(self, mask2d: torch.Tensor, past_len: int, T: int, max_new_tokens: int = 0, beams: int = 1, lead: bool = False,
+                 decode_lead: bool = False):
         n = past_len + T
         row = padding_key_row(mask2d, n + max_new_tokens)
         if past_len == 0:
@@ -72,16 +97,19 @@ class _PaddedBatch:
         self.position_ids = padding_position_ids(mask2d, T)
         if max_new_tokens:
             pos = mask2d.long().sum(-1, keepdim=True)                  # (B, 1): position of the next token
+            dl = leading_pads(mask2d) if decode_lead else None
             if beams > 1:
                 row, pos = row.repeat_interleave(beams, dim=0), pos.repeat_interleave(beams, dim=0)
-            self._row, self._pos, self._len = row, pos, n
+                dl = None if dl is None else dl.repeat_interleave(beams, dim=0)
+            self._row, self._pos, self._len, self._lead = row, pos, n, dl
 
     def step(self):
         """(additive key row (B, 1, 1, kv length incl. the new token), position ids (B, 1)) of the next decode step."""
         self._len += 1
         pos = self._pos
         self._pos = pos + 1
-        return self._row[..., : self._len], pos
+        row = self._row[..., : self._len]
+        return (row if self._lead is None else DecodeLead(row, self._lead)), pos
 
 
 def resolve_sampler(device, B: int, num_return_sequences: int, num_beams: int, do_sample: bool, temperature, top_k, top_p, min_p,
@@ -133,7 +161,8 @@ class EagerStepper:
         self.model, self.padded, self.group, self.fork = model, None, n, past_len + T
         padded = attention_mask is not None and model._padded(attention_mask, B, past_len + T, past_len)
         if padded:
-            self.padded = _PaddedBatch(attention_mask, past_len, T, max_new_tokens, n, lead=padded == PADS_LEFT)
+            self.padded = _PaddedBatch(attention_mask, past_len, T, max_new_tokens, n, lead=padded == PADS_LEFT,
+                                       decode_lead=bool(getattr(model.config, "kivi_decode_lead", False)))
             logits, pasts = model._forward(input_ids, past_key_values, self.padded.mask, self.padded.position_ids, True, True)
         else:
             logits, pasts = model.forward(input_ids, past_key_values)

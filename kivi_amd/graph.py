@@ -31,7 +31,7 @@ import torch
 from . import _lib
 from .attention import _rotate_half, kivi_attention_decode, rope_cos_sin
 from .cache_mf import SB, KiviLayerCacheMF
-from .generation import _MIN16
+from .generation import _MIN16, leading_pads
 
 
 class MfStepDriver:
@@ -86,9 +86,11 @@ class MfStepDriver:
         _lib.check(self.lib.kivi_mf_step_upload(ctypes.byref(self.host), self.dev.data_ptr(), _lib.stream_ptr(self.dev)), "kivi_mf_step_upload")
         return stale
 
-    def enqueue(self, i: int, q, k, v, out, attention_mask=None):
+    def enqueue(self, i: int, q, k, v, out, attention_mask=None, lead=None):
         """The attend launches of layer i for the prepared step (eagerly, or under stream capture)."""
-        return self.caches[i].decode_step_dyn(q, k, v, self.host, self.dev, out, attention_mask)
+        if lead is None:
+            return self.caches[i].decode_step_dyn(q, k, v, self.host, self.dev, out, attention_mask)
+        return self.caches[i].decode_step_dyn(q, k, v, self.host, self.dev, out, attention_mask, lead=lead)
 
     def finish(self) -> None:
         """Bookkeeping after the step's launches were enqueued (replayed): lengths advanced, K flushed when the residual is full."""
@@ -169,12 +171,15 @@ class DecodeGraphs:
     request's KV cache alive) and serve every call over them; MfStepDriver.prepare() alone finds a capture stale.
     `padded`: cos / sin hold one position per row (`pos`), and `mask` is a static additive (B, 1, 1, pitch) fp16 buffer, pitch >= the
     cache capacity, that the attention of every step reads (its new column is 0: new tokens are real).
+    `lead` (config.kivi_decode_lead, padded only): a static (B,) int32 buffer beside the mask, refreshed in place
+    by begin() from the same 2D mask; the steps hand it to the attention (the captured ones call kivi_mf_decode_layer_dyn_lead), so a
+    changed lead replays what was captured.
     `sampler`: the last post() draws into `tok` with it instead of argmax.  The captured call holds what the sampler's key() names:
     a Sampler's parameters and state buffer, a RowSampler's row count and two buffers -- other parameter values in the same
     RowSampler (set_row, another request mix) replay the graphs that exist, another key builds them again.
     `stats`: (eager steps, captures, replays) of the whole-step form, cumulative over the calls on one set of caches."""
 
-    def __init__(self, model, B: int, device, whole: bool = False, padded: bool = False, sampler=None):
+    def __init__(self, model, B: int, device, whole: bool = False, padded: bool = False, sampler=None, lead: bool = False):
         cfg, layers = model.config, model.model.layers
         nh, nkv = cfg.num_attention_heads, cfg.num_key_value_heads
         D, dt = layers[0].self_attn.head_dim, model.lm_head.weight.dtype
@@ -190,11 +195,12 @@ class DecodeGraphs:
         self.attn = zeros(B, nh, 1, D)
         self.qkv = [(zeros(B, nh, 1, D), zeros(B, nkv, 1, D), zeros(B, nkv, 1, D)) for _ in layers]
         self.mask = self.pos = self.driver = self.graphed = self.stats = None
+        self.lead = zeros(B, dtype=torch.int32) if padded and lead else None
         if not whole:
             self._capture_layers()
 
-    def matches(self, B: int, whole: bool, padded: bool, sampler_key) -> bool:
-        return (self.B, self.whole, self.padded, self.sampler_key) == (B, whole, padded, sampler_key)
+    def matches(self, B: int, whole: bool, padded: bool, sampler_key, lead: bool = False) -> bool:
+        return (self.B, self.whole, self.padded, self.sampler_key, self.lead is not None) == (B, whole, padded, sampler_key, bool(lead))
 
     def pre(self, i: int) -> None:
         layer = self.model.model.layers[i]
@@ -241,7 +247,7 @@ class DecodeGraphs:
     def _whole_step(self) -> None:
         for i in range(len(self.qkv)):
             self.pre(i)
-            self.driver.enqueue(i, *self.qkv[i], self.attn, self.mask)
+            self.driver.enqueue(i, *self.qkv[i], self.attn, self.mask, self.lead)
             self.post(i)
 
     def _grow_mask(self, caches) -> None:
@@ -263,6 +269,8 @@ class DecodeGraphs:
             self.mask.zero_()
             self.mask[..., : attention_mask.shape[1]].masked_fill_((attention_mask == 0)[:, None, None, :], _MIN16)
             self.pos = attention_mask.long().sum(-1) - 1                 # (B,): position of `tok`
+            if self.lead is not None:
+                self.lead.copy_(leading_pads(attention_mask))            # in place: the captured step keeps its pointer
         if self.whole:
             if self.driver is not None and self.driver.serves(caches):   # the same caches again: replay what was captured instead of
                 self.driver.resync()                                     # paying an eager step and a capture of every layer again
@@ -286,7 +294,10 @@ class DecodeGraphs:
         mask = self.mask[..., : caches[0].kv_seq_len + 1] if self.padded else None
         for i, (q, k, v) in enumerate(self.qkv):
             self.pre_graphs[i].replay()
-            kivi_attention_decode(q, k, v, caches[i], attention_mask=mask, out=self.attn)
+            if self.lead is None:
+                kivi_attention_decode(q, k, v, caches[i], attention_mask=mask, out=self.attn)
+            else:
+                kivi_attention_decode(q, k, v, caches[i], attention_mask=mask, out=self.attn, lead=self.lead)
             self.post_graphs[i].replay()
 
     def end(self) -> None:

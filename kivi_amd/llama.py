@@ -27,17 +27,19 @@ import torch.nn.functional as F
 from . import admit
 from .attention import KiviLayerCacheMF, LlamaAttention_KIVI
 from .beam import beam_search
-from .generation import (PADS_LEFT, EagerStepper, _PaddedBatch, decode_loop, left_pad, padding_key_row,  # noqa: F401
-                         padding_position_ids, padding_prompt_mask, resolve_sampler)
+from .generation import (PADS_LEFT, DecodeLead, EagerStepper, _PaddedBatch, decode_loop, leading_pads, left_pad,  # noqa: F401
+                         padding_key_row, padding_position_ids, padding_prompt_mask, resolve_sampler)
 from .graph import DecodeGraphs
 from .prefill import left_padded
 from .sampling import RowSampler
 
 
 def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32, residual_length: int = 32,
-                max_cache_len: Optional[int] = None, prefill_kernel: bool = False) -> SimpleNamespace:
+                max_cache_len: Optional[int] = None, prefill_kernel: bool = False, decode_lead: bool = False) -> SimpleNamespace:
     """HF config.json fields (+ the four KIVI fields) -> the namespace the modules read.  `prefill_kernel`: the prompt pass's
-    attention runs kivi_prefill_attention, and every attention class serves left-padded prompts."""
+    attention runs kivi_prefill_attention, and every attention class serves left-padded prompts.
+    `decode_lead`: the decode steps of a padded batch hand the kernels every row's leading pads, and the row kernels skip the packed
+    K and V under them."""
     hidden, heads = d["hidden_size"], d["num_attention_heads"]
     return SimpleNamespace(
         hidden_size=hidden, num_attention_heads=heads, num_key_value_heads=d.get("num_key_value_heads", heads),
@@ -49,7 +51,7 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
         k_bits=d.get("k_bits", k_bits), v_bits=d.get("v_bits", v_bits), group_size=d.get("group_size", group_size),
         residual_length=d.get("residual_length", residual_length),
         kivi_max_cache_len=max_cache_len,   # opt-in reservation; by default the cache starts prompt-sized and doubles
-        kivi_prefill_kernel=bool(prefill_kernel))
+        kivi_prefill_kernel=bool(prefill_kernel), kivi_decode_lead=bool(decode_lead))
 
 
 class RMSNorm(nn.Module):
@@ -129,7 +131,10 @@ class LlamaForCausalLM_KIVI(nn.Module):
         if not padded:
             return self._forward(input_ids, past_key_values, None, None, last_token_only, False)
         pb = _PaddedBatch(padding_mask, past_len, input_ids.shape[1], lead=padded == PADS_LEFT)
-        return self._forward(input_ids, past_key_values, pb.mask, pb.position_ids, last_token_only, True)
+        mask = pb.mask
+        if past_len and input_ids.shape[1] == 1 and getattr(self.config, "kivi_decode_lead", False):
+            mask = DecodeLead(mask, leading_pads(padding_mask))     # a decode step: the key row travels with its lead (section 21)
+        return self._forward(input_ids, past_key_values, mask, pb.position_ids, last_token_only, True)
 
     def _forward(self, input_ids, past_key_values, attention_mask, position_ids, last_token_only, mask_prompt):
         x, new = self._hidden(input_ids, past_key_values, attention_mask, position_ids, mask_prompt)
@@ -465,8 +470,9 @@ class LlamaForCausalLM_KIVI(nn.Module):
     def prepare_graphs(self, batch: int, device, whole: bool = False, padded: bool = False, sampler=None) -> None:
         """Capture the decode graphs for this batch size now (otherwise on the first graphed step)."""
         key = None if sampler is None else sampler.key()
-        if self.graphs is None or not self.graphs.matches(batch, whole, padded, key):
-            self.graphs = DecodeGraphs(self, batch, device, whole, padded, sampler)
+        lead = padded and bool(getattr(self.config, "kivi_decode_lead", False))
+        if self.graphs is None or not self.graphs.matches(batch, whole, padded, key, lead):
+            self.graphs = DecodeGraphs(self, batch, device, whole, padded, sampler, lead)
 
     def release_graphs(self) -> None:
         """Drop the static buffers and everything captured; the next graphed decode builds them again."""
@@ -528,7 +534,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
     @classmethod
     def from_pretrained(cls, path: str, device="cuda", dtype=torch.float16, **kivi):
         """`path`: a local HF checkpoint directory (config.json + *.safetensors).  `kivi`: k_bits, v_bits, group_size,
-        residual_length, max_cache_len, prefill_kernel."""
+        residual_length, max_cache_len, prefill_kernel, decode_lead."""
         from safetensors.torch import load_file
         cfg = make_config(json.load(open(os.path.join(path, "config.json"))), **kivi)
         with torch.device(device):

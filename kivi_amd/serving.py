@@ -39,7 +39,7 @@ from typing import List, Optional
 
 import torch
 
-from .generation import left_pad, padding_key_row
+from .generation import decode_key_row, left_pad, padding_key_row
 from .sampling import RowSampler, SamplingParams
 
 
@@ -122,6 +122,7 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
     prompts, limits, params = check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling,
                                               model.config.vocab_size, compact, short_admissions)
     pad = 0 if pad_token_id is None else pad_token_id
+    use_lead = bool(getattr(model.config, "kivi_decode_lead", False))
     N, device = len(prompts), model.lm_head.weight.device
     B = min(batch_size, N)
     L = max(p.numel() for p in prompts)
@@ -193,7 +194,9 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
             model.decode_graphed(tok, pasts, L, 1, attention_mask=m, sampling=sampler)
             tok = model.graphs.tok.clone()
         else:
-            logits, pasts = model._forward(tok, pasts, padding_key_row(m), m.sum(-1, keepdim=True) - 1, True, True)
+            # (config.kivi_decode_lead: the row travels with the leading zeros of the SAME mask -- what an admission rewrote and
+            # a rebase dropped is in it)
+            logits, pasts = model._forward(tok, pasts, decode_key_row(m, use_lead), m.sum(-1, keepdim=True) - 1, True, True)
             tok = pick(logits, sampler)
         L += 1
     if graphed and model.graphs is not None:
