@@ -88,12 +88,19 @@ static void walk_v(int Tv, int lead, int nw) {
 }
 
 int main() {
-    const int lengths[] = {0, 32, 480, 512, 544, 1088, 4096, 8192 + 128};
+    // K stores hold whole 32-token groups; V stores end anywhere.  4352 / 4480 / 5184 and 4350 / 4478 / 5182: the long rows of
+    // tests/test_decode_lead_long_gpu.py (9 and 11 super-blocks, the last one partial)
+    const int k_lengths[] = {0, 32, 480, 512, 544, 1088, 4096, 8192 + 128, 4352, 4480, 5184};
+    const int v_lengths[] = {0, 32, 480, 512, 544, 1088, 4096, 8192 + 128, 4350, 4478, 5182};
     long cases = 0;
-    for (int Tq : lengths)
-        for (int Tv : lengths) {
+    for (int Tq : k_lengths)
+        for (int Tv : v_lengths) {
             const int n = (Tq > Tv ? Tq : Tv) + 33;                                     // a row: the packed keys, a residual, the new token
-            const int leads[] = {-7, INT_MIN, 0, 1, 511, 512, 513, 1023, 1024, Tq - 1, Tq, Tq + 1, Tv - 1, Tv, Tv + 1, n - 1, INT_MAX};
+            const int nsb = (Tq + kLeadSbTokens - 1) / kLeadSbTokens;
+            const int leads[] = {-7, INT_MIN, 0, 1, 511, 512, 513, 1023, 1024, Tq - 1, Tq, Tq + 1, Tv - 1, Tv, Tv + 1, n - 1, INT_MAX,
+                                 // the pads of longpad_masks.leadwalk_mask for 4 and 8 waves
+                                 33, 2047, 2048, 2049, 4095, 4096, 4097, 512 * (nsb - 4) - 96, 512 * (nsb - 4), 512 * (nsb - 8) - 96,
+                                 512 * (nsb - 8), 512 * (nsb - 1)};
             for (int lead : leads)
                 for (int nw : {4, 8}) {
                     walk_k(Tq, lead, nw);
@@ -104,7 +111,7 @@ int main() {
                     cases++;
                 }
         }
-    if (cases != 8 * 8 * 17 * 2) return 1;
+    if (cases != 11 * 11 * 29 * 2) return 1;
     printf("lead plan ok\n");
     return 0;
 }

@@ -3,7 +3,10 @@
 A short prompt admitted into a living cache of length L (continuous batching) is left-padded to L: its row's
 first L - len(prompt) keys are masked at the fp16 minimum at every later decode step.  With L in the thousands the mask covers whole
 512-token super-blocks, whole slices of the sliced one-launch form and often the entire packed K and V stores.  One pattern per
-batch row; every pad stops before the new token (HF never masks the token it feeds), so no row is fully masked."""
+batch row; every pad stops before the new token (HF never masks the token it feeds), so no row is fully masked.
+
+leadwalk_mask: the leads of tests/test_decode_lead_long_cpu.py and tests/test_decode_lead_long_gpu.py -- pads
+placed by the walk of a row kernel that skips them, on rows long enough for a wave to walk two super-blocks behind a lead."""
 import torch
 
 FMIN = torch.finfo(torch.float16).min
@@ -38,6 +41,54 @@ def longpad_mask(n, Tq, Tv, device, rows=None):
     if rows is not None:
         m = m[list(rows)].contiguous()
     return m.to(device)
+
+
+def leadwalk_pads(n, Tq, Tv, nw):
+    """The twelve pads of leadwalk_mask, clamped to n - 1."""
+    nsb = -(-Tq // SB)
+    p = [0, 33, SB, SB * nw - 1, SB * nw, SB * nw + 1, SB * (nsb - nw) - 96, SB * (nsb - nw), SB * (nsb - 1), Tq, max(Tq, Tv) + 1, n - 1]
+    return [max(0, min(x, n - 1)) for x in p]
+
+
+def leadwalk_mask(n, Tq, Tv, nw, device):
+    """Leading pads that follow the walk of a row kernel under a lead (kivi_amd/csrc/kivi_lead_plan.h) on rows of
+    many super-blocks: (mask, lead), mask (12, 1, 1, n) fp16 with the fp16 minimum at keys [0, lead[b]) of row b, lead (12,) int32 =
+    min(p, n - 1).  Tq / Tv as in longpad_mask, nsb = ceil(Tq / 512), nw the waves per row of the kernel under test (the packed K
+    super-blocks from the first live one on are dealt round-robin to nw waves, the live 32-token V blocks in nw contiguous runs).
+      row 0        p = 0: the lead form with nothing to skip -- the deal must equal the plain one
+      row 1        p = 33: K nothing skipped; V first live block 1: every wave's run shifts by one block
+      row 2        p = 512: first live super-block 1; waves walk two super-blocks, for one of them the second is the partial last
+      rows 3 4 5   p = 512 nw - 1, 512 nw, 512 nw + 1: a whole round of the deal skipped, and the straddle either side of it
+      row 6        p = 512 (nsb - nw) - 96: nw + 1 live super-blocks -- wave 0 walks the straddled one and the partial last; V starts
+                   three blocks before a super-block boundary
+      row 7        p = 512 (nsb - nw): exactly nw live, one per wave, the last wave on the partial one
+      row 8        p = 512 (nsb - 1): only the partial last super-block, on wave 0 alone
+      row 9        p = Tq: no packed K; V live where Tv > clamp
+      row 10       p = max(Tq, Tv) + 1: both packed stores skipped whole
+      row 11       p = n - 1: only the new token"""
+    lead = leadwalk_pads(n, Tq, Tv, nw)
+    m = torch.zeros((ROWS, 1, 1, n), dtype=torch.float16)
+    for b, p in enumerate(lead):
+        m[b, ..., :p] = FMIN
+    return m.to(device), torch.tensor(lead, dtype=torch.int32, device=device)
+
+
+def assert_leadwalk(pre, out, lead, what=""):
+    """leadwalk_mask's patterns read off the REFERENCE's step (as assert_patterns): finite, no row fully masked, the keys under a row's
+    lead -- and only those -- dead and within 32 of the clamp, row 11 left with exactly one live key.  Returns the (B, nh) live counts.
+    (A dead key is fp16(score - 65504): a score of 48 or more would land it on -65440, off what a kernel that skips the key can write.)"""
+    x = pre.detach().float().cpu()[:, :, 0]
+    n = x.shape[-1]
+    assert bool(torch.isfinite(x).all()) and bool(torch.isfinite(out.detach().float()).all()), (what, "the reference is not finite")
+    live = x > -60000
+    count = live.sum(-1)
+    assert bool((count >= 1).all()), (what, "a fully masked row")
+    dead = x[~live]
+    assert bool(((dead >= -65504) & (dead <= -65472)).all()), (what, "a dead key off the clamp", dead.min().item(), dead.max().item())
+    under = torch.arange(n)[None] < torch.as_tensor(lead).cpu().long()[:, None]
+    assert torch.equal(live, (~under)[:, None, :].expand_as(live)), (what, "the dead keys are not the keys under the lead")
+    assert bool((count[11] == 1).all()) and bool(live[11, :, n - 1].all()), (what, "row 11", count[11])
+    return count
 
 
 def assert_patterns(pre, out, Tq, rows=None, what=""):

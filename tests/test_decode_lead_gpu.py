@@ -59,17 +59,55 @@ def _dumped(layer, B, nh, n):
 
 
 # ------------------------------------------------------------------ 1. stages under a lead
-@pytest.mark.parametrize("nh,nh_kv,T0,R,kind,bits", [(4, 4, 1100, 32, "randn", 2), (4, 4, 1100, 32, "randn", 4),
-                                                      (8, 2, 1100, 128, "outlier", 2), (16, 2, 1100, 32, "randn", 2),
-                                                      (8, 2, 1100, 32, "outlier", 4)])
-def test_row_kernels_under_a_lead_match_reference_and_the_mask_alone(nh, nh_kv, T0, R, kind, bits):
+def _longpad_patterns(n, Tq, Tv):
+    return longpad_mask(n, Tq, Tv, "cuda"), longpad_lead(n, Tq, Tv)
+
+
+def _longpad_check(pre, ref, n, Tq, lead, s):
+    count = assert_patterns(pre, ref, Tq, what=("lead", s))
+    assert bool((count[5] == n - Tq).all()), (s, "row 5: the fp16 residual and the new token")
+
+
+def _cuda_kv(seed, heads, T, kind="randn"):
+    return make_kv(seed, ROWS, heads, T, D, kind).cuda()
+
+
+def _poison_under(layer, lead, Tq, Tv):
+    """Every word of the whole K and V super-blocks under each row's lead overwritten with a NaN pattern, through the cache's own
+    stores.  Returns the number of words written."""
+    words = 0
+    for b, p in enumerate(lead.tolist()):
+        for store, T in ((layer.kt, Tq), (layer.vt, Tv)):
+            nsb = min(p, T) // SB
+            store[b, :, :nsb] = NAN_WORD
+            words += store[b, :, :nsb].numel()
+    return words
+
+
+def _template_args(name):
+    """("mf_row_kernel", ["8", "8", "8", "false", "true", "2", "2", "true"]) of the launch probe's "(mf_row_kernel<8, 8, ...>)"."""
+    name = name.strip("() ")
+    kernel, _, rest = name.partition("<")
+    return kernel.strip(), [a.strip() for a in rest.rstrip("> ").split(",")] if rest else []
+
+
+def lead_stages(nh, nh_kv, T0, R, kind, bits, patterns=_longpad_patterns, check=_longpad_check, draw=_cuda_kv, what="decode lead row",
+                split_control=False, poison=False, expect=None):
+    """The stage loop under a lead, every step across one K flush (the module's docstring, 1.).  `patterns(n, Tq, Tv)` -> (mask, lead)
+    of a step, `check(pre, ref, n, Tq, lead, s)` the patterns' own assertions on the reference's rows, `draw(seed, heads, T, kind)` the
+    inputs (on the GPU; the reference is built from the same tensors).  On top of it, for tests/test_decode_lead_long_gpu.py:
+    `split_control` -- the two-launch form with the mask alone against the row form with the mask alone, inside the bar the lead is held
+    to against the mask alone (two forms that shipped before the lead: an input where they miss it is a badly chosen input);
+    `poison` -- at step 0 a clone whose whole super-blocks under each lead hold NaNs gives finite, bit-identical outputs;
+    `expect` -- (kernel, template arguments with None for "any") of the instantiation the launch probe must name at every step.
+    Returns the worst ratios (stage A, stage B, against the mask alone, split against row)."""
     from kivi_amd import _lib
     from kivi_amd.attention import KiviConfig, KiviLayerCacheMF, kivi_attention_decode, make_layer_cache
     B = ROWS
     steps = (R - T0 % R) + 3                    # exactly one K flush (at step index steps - 4) and three steps after it
     flush = steps - 4
     cfg = KiviConfig(bits, bits, G32, R)
-    k0, v0 = make_kv(1, B, nh_kv, T0, D, kind).cuda(), make_kv(2, B, nh_kv, T0, D).cuda()
+    k0, v0 = draw(1, nh_kv, T0, kind), draw(2, nh_kv, T0)
     layer = make_layer_cache(cfg, B, nh_kv, D, T0 + 8, "cuda", num_heads=nh)     # small capacity: the cache must grow
     assert isinstance(layer, KiviLayerCacheMF)
     forced = _forced("row")
@@ -78,23 +116,48 @@ def test_row_kernels_under_a_lead_match_reference_and_the_mask_alone(nh, nh_kv, 
     assert _lib.load().kivi_mf_launch_plan(B, nh, nh_kv, layer.k_quant_len, layer.k_res_len, R, layer.flags, bits, 0) == 1
     product, plain = layer.clone(), layer.clone()        # the lead without the dump flag; the mask alone (dumped)
     product.flags = forced
+    split = None
+    if split_control:
+        split = layer.clone()
+        split.flags = _forced("split")
+    probe = None
+    if expect is not None:
+        from test_fullsize_gpu import LaunchProbe
+        probe = LaunchProbe()
     past = T64.prefill_cache(k0, v0, bits, bits, G32, R)
+    del k0, v0
     _same_tuple(layer, past, "after the prompt pass")
-    worst_a = worst_b = worst_m = 0.0
+    worst_a = worst_b = worst_m = worst_c = 0.0
     keys = torch.arange(T0 + steps + 1, device="cuda")
     for s in range(steps):
-        q, kn, vn = _step_inputs(s, B, nh, nh_kv, kind)
+        q, kn, vn = draw(100 + s, nh, 1), draw(200 + s, nh_kv, 1, kind), draw(300 + s, nh_kv, 1)
         n = T0 + s + 1
         Tq, Tv = _lengths(past, bits)
-        mask, lead = longpad_mask(n, Tq, Tv, "cuda"), longpad_lead(n, Tq, Tv)
+        mask, lead = patterns(n, Tq, Tv)
         for c in (layer, plain):
             c.ensure_room(1)
+        poisoned = None
+        if poison and s == 0:
+            poisoned = product.clone()
+            assert _poison_under(poisoned, lead, Tq, Tv) > 0
         layer._desc(nh, q.device)[4][0].fill_(float("nan"))          # the scratch rows of this step (a stale row must not pass)
         out = kivi_attention_decode(q, kn, vn, layer, attention_mask=mask, lead=lead)
         x_gpu = _dumped(layer, B, nh, n)                              # the rows the softmax consumed
+        if probe is not None:
+            probe.arm()
         out_p = kivi_attention_decode(q, kn, vn, product, attention_mask=mask, lead=lead)
+        if probe is not None:
+            kernel, args = _template_args(probe.kernel())
+            want = [None if a is None else str(a).lower() for a in expect[1]]
+            assert kernel == expect[0] and len(args) == len(want) and all(w is None or w == a for w, a in zip(want, args)), \
+                ("the instantiation that ran", s, kernel, args, expect)
         assert torch.isfinite(out).all(), s
         assert same_bits(out, out_p), ("the product instantiation differs from the dumped one", s)
+        if poisoned is not None:
+            out_n = kivi_attention_decode(q, kn, vn, poisoned, attention_mask=mask, lead=lead)
+            assert bool(torch.isfinite(out_n).all()), "a poisoned super-block under the lead reached the output"
+            assert same_bits(out_n, out_p), "the poisoned cache's output differs from the clean one's"
+            del poisoned, out_n
         plain._desc(nh, q.device)[4][0].fill_(float("nan"))
         out_m = kivi_attention_decode(q, kn, vn, plain, attention_mask=mask)
         x_m = _dumped(plain, B, nh, n)
@@ -106,22 +169,30 @@ def test_row_kernels_under_a_lead_match_reference_and_the_mask_alone(nh, nh_kv, 
         assert bool(under.any()) and bool((x_gpu.view(torch.int16)[under] == FMIN_BITS).all()), ("skipped slots hold -65504", s)
         ok, rm = gemv_close(out, out_m, rtol=1.5e-3, ulps=1)
         assert ok, ("lead against the mask alone", s, rm)
+        if split is not None:                                         # the control of that bar: two forms that shipped before the lead
+            out_s = kivi_attention_decode(q, kn, vn, split, attention_mask=mask)
+            ok, rc = gemv_close(out_s, out_m, rtol=1.5e-3, ulps=1)
+            assert ok, ("control: split against row, the mask alone", s, rc)
+            worst_c = max(worst_c, rc)
+            del out_s
+        del x_m, at_or_after, under
         # ---- against the reference, as in _longpad_stages
         ref, new_past, pre = T64.decode_step(q, kn, vn, past, bits, bits, G32, R, attention_mask=mask)
         _, _, pre0 = T64.decode_step(q, kn, vn, past, bits, bits, G32, R)
-        count = assert_patterns(pre, ref, Tq, what=("lead", s))
-        assert bool((count[5] == n - Tq).all()), (s, "row 5: the fp16 residual and the new token")
+        check(pre, ref, n, Tq, lead, s)
         assert not torch.isnan(x_gpu).any(), ("a key of the row was not written", s)
         live = pre.float() > -60000
         ok, ra = gemv_close(torch.where(live, x_gpu, pre0), torch.where(live, pre, pre0), rtol=1e-3, ulps=1)
         assert ok, ("stage A", s, ra)
         xd, pd = x_gpu.float()[~live], pre.float()[~live]
         assert bool((xd <= -60000).all()) and bool(((xd - pd).abs() <= 32).all()), ("masked keys", s)
+        del xd, pd, pre0, live
         ref_b, _, _ = T64.decode_step(q, kn, vn, past, bits, bits, G32, R, attention_mask=mask, scores_override=x_gpu)
         ok, rb = gemv_close(out, ref_b, rtol=2e-3, ulps=1)
         assert ok, ("stage B", s, rb)
         worst_a, worst_b, worst_m = max(worst_a, ra), max(worst_b, rb), max(worst_m, rm)
         past = new_past
+        del ref, ref_b, pre, x_gpu, new_past                          # (the fp64 reference's step: gigabytes at the many-unit shapes)
         if s == flush:
             assert _lengths(past, bits)[0] == Tq + R, "the K flush"
         if s in (0, flush, flush + 1, steps - 1):
@@ -129,8 +200,19 @@ def test_row_kernels_under_a_lead_match_reference_and_the_mask_alone(nh, nh_kv, 
     assert layer.k_res_len == 3
     _assert_same_state(layer, product)
     _assert_same_state(layer, plain)
-    print(f"decode lead row {nh}/{nh_kv} T0={T0} R={R} {kind} {bits}-bit: worst ratio: scores {worst_a:.3f} of 1e-3+1ulp, "
-          f"attend {worst_b:.3f} of 2e-3+1ulp, against the mask alone {worst_m:.3f} of 1.5e-3+1ulp over {steps} steps")
+    if split is not None:
+        _same_tuple(split, past, "split, last step")
+    print(f"{what} {nh}/{nh_kv} T0={T0} R={R} {kind} {bits}-bit: worst ratio: scores {worst_a:.3f} of 1e-3+1ulp, "
+          f"attend {worst_b:.3f} of 2e-3+1ulp, against the mask alone {worst_m:.3f} of 1.5e-3+1ulp over {steps} steps"
+          + (f", control split against row {worst_c:.3f} of 1.5e-3+1ulp" if split is not None else ""))
+    return worst_a, worst_b, worst_m, worst_c
+
+
+@pytest.mark.parametrize("nh,nh_kv,T0,R,kind,bits", [(4, 4, 1100, 32, "randn", 2), (4, 4, 1100, 32, "randn", 4),
+                                                      (8, 2, 1100, 128, "outlier", 2), (16, 2, 1100, 32, "randn", 2),
+                                                      (8, 2, 1100, 32, "outlier", 4)])
+def test_row_kernels_under_a_lead_match_reference_and_the_mask_alone(nh, nh_kv, T0, R, kind, bits):
+    lead_stages(nh, nh_kv, T0, R, kind, bits)
 
 
 # ------------------------------------------------------------------ 2. the skip really skips
