@@ -37,8 +37,10 @@
  *                               back: checkpoint and restore of either cache layout)
  *               sampling:       kivi_sample (temperature / top-k / top-p / min-p draw of one token per row, Philox RNG state on
  *                               the device), kivi_sample_rows (the same draw with per-row parameters, seeds, streams and
- *                               greedy rows read from device memory)
- *               scoring:        kivi_token_logprob (log-probability and rank of one given token per row of logits)
+ *                               greedy rows read from device memory), kivi_sample_rows_pen (the same with repetition /
+ *                               presence / frequency penalties per row over a history table in device memory), kivi_seen_mark
+ *                               (clears and marks rows of that table)
+ *               scoring:       kivi_token_logprob (log-probability and rank of one given token per row of logits)
  *               prompt pass:    kivi_prefill_attention (causal grouped-query attention over fp16 q / k / v with leading pads)
  *   BUILDING BLOCKS (what the layer steps are composed of; exported for tests, tools and callers that keep their own cache
  *               bookkeeping -- same contracts, but no stability promise beyond the ABI version):  kivi_gemv_k_paged,
@@ -724,6 +726,61 @@ typedef struct {         /* 32 bytes, 8-byte aligned */
 } kivi_sample_row;
 int kivi_sample_rows(const void* logits, int logits_bits, int64_t row_stride, int B, int V, const kivi_sample_row* rows,
                      int64_t* draw_index, int64_t* out_tokens, int64_t out_stride, kivi_stream_t stream);
+/*
+ * kivi_sample_rows_pen: kivi_sample_rows with a repetition, a presence and a frequency penalty per row (HF's
+ * and vLLM's repetition_penalty over prompt and output tokens, OpenAI's and vLLM's presence_penalty / frequency_penalty over output
+ * tokens), applied where the logit is read, in the same single launch.
+ *   seen   the history table: one uint16 per (row, token), row b at seen + b * seen_stride (elements), seen_stride >= V, rows
+ *          16-byte aligned.  Bit 15: the token occurred in the row's prompt.  Bits 0-14: c, the number of times the row has emitted
+ *          the token, saturating at 32767.  any = (word != 0).
+ *   pen    one kivi_sample_penalty per row in device memory, read only: theta = repetition, presence, frequency
+ * THE PENALISED LOGIT, before the temperature (the order of HF's _get_logits_processor), for greedy rows too.  Every operation is
+ * one correctly rounded IEEE fp32 operation and none is contracted into an fma, so an fp32 restatement on the CPU gives the same bits:
+ *   x = float(logit)
+ *   if any:    x = (x > 0) ? x / theta : x * theta
+ *   t = frequency * float(c);  x = x - t            (always; c = 0 leaves x unchanged)
+ *   if c > 0:  x = x - presence
+ *   s = (temperature != 1 ? x / temperature : x) + 0.0f, and from there kivi_sample_rows unchanged: thresholds, tie classes, the
+ *   2^40 integer weights, Philox, the greedy tie rule.
+ * After writing its token j, the workgroup of row b adds 1 to the count of seen[b][j] unless it is 32767 (one lane, a plain 16-bit
+ * vector store; the prompt bit stays), and stores draw_index[b] + 1: one launch, which a captured graph replays without host writes.
+ * IDENTITY A: with every record neutral (1, 0, 0) the tokens are bit for bit those of kivi_sample_rows, whatever the table holds (a
+ * workgroup whose record is neutral takes the unpenalised path and reads no table word but the one it counts).
+ * IDENTITY B: with any records and table the tokens are bit for bit those of kivi_sample_rows on the fp32 logits the rule gives.
+ * A record outside the contract degrades as kivi_sample_rows' do: theta not finite or <= 0 is read as 1, a presence or frequency
+ * that is not finite as 0; the kernel never loops and never indexes outside its row of logits or of the table.
+ * Refusals (nothing enqueued) as kivi_sample_rows, and KIVI_EINVAL for a null pen / seen or seen_stride < V; KIVI_EALIGN for pen
+ * not 4-byte aligned, seen not 16-byte aligned, seen_stride not a multiple of 8.
+ */
+typedef struct {         /* 16 bytes, 4-byte aligned */
+    float repetition;    /* theta: finite, > 0; 1 = off */
+    float presence;      /* finite; 0 = off */
+    float frequency;     /* finite; 0 = off */
+    uint32_t reserved;   /* 0 */
+} kivi_sample_penalty;
+int kivi_sample_rows_pen(const void* logits, int logits_bits, int64_t row_stride, int B, int V, const kivi_sample_row* rows,
+                         int64_t* draw_index, const kivi_sample_penalty* pen, uint16_t* seen, int64_t seen_stride,
+                         int64_t* out_tokens, int64_t out_stride, kivi_stream_t stream);
+/*
+ * kivi_seen_mark: writes rows of the history table of kivi_sample_rows_pen.  Entry i of the call (i < n) serves table row rows[i]
+ * (rows: int32[n] in device memory, distinct, each a row of the table -- the entry cannot check them, the caller does; a negative
+ * one is skipped; null: row i) with the tokens tokens[i * tok_row_stride + t], t in [lead[i], T).
+ *   KIVI_SEEN_CLEAR   the row's seen_stride words are zeroed first (16-byte stores)
+ *   KIVI_SEEN_PROMPT  bit 15 of every token's word is set
+ *   KIVI_SEEN_OUTPUT  1 is added to every token's count instead: exact, duplicates count, saturating at 32767
+ * At most one of PROMPT / OUTPUT.  Token ids outside [0, V) are skipped.  lead (int32[n] in device memory or null = 0) is clamped
+ * to [0, T] on the device and never read on the host, as in kivi_prefill_attention.  Two tokens share a 32-bit word of the table:
+ * the marks are atomics on that word.  T == 0 with CLEAR is legal and resets the rows (tokens may then be null); T == 0 without it
+ * enqueues nothing.  One launch, n workgroups.
+ * KIVI_EINVAL (nothing enqueued) for flags 0, unknown or PROMPT | OUTPUT, V outside [1, KIVI_SAMPLE_MAX_V], n outside
+ * [1, KIVI_SAMPLE_MAX_B], T < 0, a null seen, seen_stride < V, null tokens with marks and T > 0, tok_row_stride < T (n > 1);
+ * KIVI_EALIGN for seen not 16-byte aligned, seen_stride not a multiple of 8, rows or lead not 4-byte, tokens not 8-byte aligned.
+ */
+#define KIVI_SEEN_CLEAR 1
+#define KIVI_SEEN_PROMPT 2
+#define KIVI_SEEN_OUTPUT 4
+int kivi_seen_mark(uint16_t* seen, int64_t seen_stride, int V, const int32_t* rows, int n, const int64_t* tokens,
+                   int64_t tok_row_stride, int T, const int32_t* lead, int flags, kivi_stream_t stream);
 /*
  * kivi_token_logprob: the log-probability of one given token per row of (N, V) logits, log-softmax + gather in one launch without
  * an fp32 (N, V) intermediate (teacher-forced scoring, perplexity, the log-probabilities of generated tokens).

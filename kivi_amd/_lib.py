@@ -199,6 +199,8 @@ SIGNATURES = {
                                    _i64, _vp]),
     "kivi_sample": (_i32, [_vp, _i32, _i64, _i32, _i32, ctypes.c_float, _i32, ctypes.c_float, ctypes.c_float, _vp, _vp, _i64, _vp]),
     "kivi_sample_rows": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "kivi_sample_rows_pen": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "kivi_seen_mark": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp]),
     "kivi_token_logprob": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "kivi_prefill_attention": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
                                       _i32, _i32, _i32, _i32, _i32, ctypes.c_float, _vp]),

@@ -17,6 +17,8 @@
 // kivi_sample: a second, one-thread launch advances the draw counter n of the RNG state after the sampler has read it.
 // kivi_sample_rows: the same row body with parameters, seed, stream and draw index read per row from device
 // memory; a greedy flag per row; each block advances its own row's draw index.
+// kivi_sample_rows_pen: the row kernel with repetition / presence / frequency penalties read from a per-row
+// history table where the logit is read (PenRow), the token counted in the table where it is written; kivi_seen_mark fills the table.
 #include "kivi_common.h"
 
 namespace {
@@ -93,11 +95,57 @@ struct Row {
     }
 };
 
+// The reader of kivi_sample_rows_pen: the penalised logit of include/kivi_hip.h from the row's history word (bit 15: in the prompt;
+// bits 0-14: times emitted), then Row's score.  Every operation is one correctly rounded fp32 operation, none contracted into an
+// fma, so a torch fp32 restatement gives the same bits (kivi_amd/sampling.py: reference_penalise).
+template <typename T>
+struct PenRow {
+    const T* p;
+    float temp;
+    bool div;
+    const uint16_t* seen;
+    float theta, pres, freq;
+    const uint8_t* marks;                            // LDS, mark_chunks(): bit c of the row = some word of tokens [64 c, 64 c + 64) is set
+    __device__ __forceinline__ float penalised(float x, uint32_t w) const {
+#pragma clang fp contract(off)                       // (HIP's __fmul_rn / __fsub_rn are plain * and -: they would contract)
+        const uint32_t c = w & 0x7FFFu;
+        if (w) x = x > 0.0f ? x / theta : x * theta; // (the build divides correctly rounded, as x / temp below)
+        const float t = freq * (float)c;
+        x = x - t;
+        if (c) x = x - pres;
+        return x;
+    }
+    __device__ __forceinline__ float s(int e) const {
+        float x = (float)p[e];
+        // Every pass walks the row in aligned runs of 64 tokens per wave, so this branch is wave-uniform: a wave whose run holds no
+        // marked token -- most of them -- loads no table word and skips the arithmetic.  For a zero word the rule only subtracts
+        // a zero, which can at most turn -0 into +0, as the + 0 below does anyway.
+        if ((marks[e >> 9] >> ((e >> 6) & 7)) & 1) x = penalised(x, seen[e]);
+        return (div ? x / temp : x) + 0.0f;
+    }
+};
+
+// The chunk bitmap of PenRow, by the whole block, once per launch: a wave step reads 512 words of the row's history with one 16-byte
+// load per lane (rows are 16-byte aligned and a multiple of 8 words long, so a load that starts below V ends inside the row; what
+// lies between V and the row's end can only set a bit too many) and stores the byte of its 8 chunks.  The caller's barrier follows.
+__device__ __forceinline__ void mark_chunks(uint8_t* marks, const uint16_t* hist, int V) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint4* q = reinterpret_cast<const uint4*>(hist);
+    for (int g = wave; g * 512 < V; g += kWaves) {
+        const int e = g * 512 + lane * 8;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (e < V) v = q[e >> 3];
+        const uint64_t any = __builtin_amdgcn_ballot_w64((v.x | v.y | v.z | v.w) != 0);
+        const uint64_t bits = __builtin_amdgcn_ballot_w64(lane < 8 && ((any >> (8 * (lane & 7))) & 0xFFu) != 0);
+        if (lane == 0) marks[g] = (uint8_t)bits;
+    }
+}
+
 // One radix digit over the tokens of this wave's segment: histogram (counts, or weights when MASS) of the keys >= lo whose bits
 // above `shift + nbits` equal those of `prefix`, then wave 0 picks the lowest non-empty bin whose strictly-higher total is < the
 // remaining target (for counts: the bin that holds the k-th largest; for weights: the bin that holds the top-p boundary class).
-template <bool MASS, typename T>
-__device__ void radix_digit(Shared& sh, const Row<T>& row, int e0, int e1, float m, uint32_t lo, uint32_t& prefix, int shift,
+template <bool MASS, class Reader>
+__device__ void radix_digit(Shared& sh, const Reader& row, int e0, int e1, float m, uint32_t lo, uint32_t& prefix, int shift,
                             int nbits, uint64_t& rem, double frac) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int nb = 1 << nbits;
@@ -160,8 +208,8 @@ __device__ void radix_digit(Shared& sh, const Row<T>& row, int e0, int e1, float
     __syncthreads();
 }
 
-template <bool MASS, typename T>
-__device__ uint32_t radix_select(Shared& sh, const Row<T>& row, int e0, int e1, float m, uint32_t lo, uint64_t rem, double frac) {
+template <bool MASS, class Reader>
+__device__ uint32_t radix_select(Shared& sh, const Reader& row, int e0, int e1, float m, uint32_t lo, uint64_t rem, double frac) {
     uint32_t prefix = 0;
     radix_digit<MASS>(sh, row, e0, e1, m, lo, prefix, 21, 11, rem, frac);
     radix_digit<MASS>(sh, row, e0, e1, m, lo, prefix, 10, 11, rem, -1.0);
@@ -171,12 +219,12 @@ __device__ uint32_t radix_select(Shared& sh, const Row<T>& row, int e0, int e1, 
 
 // One row, by the whole workgroup: the body of both kernels.  Every branch below is on values that are the same for all threads of
 // the block (the row's parameters, V, BS), so every __syncthreads() is reached by all 1024 threads on every path.
-// Counter word 0 of the draw is `c0`, the key `seed`, the draw index `n`.
-template <typename T>
-__device__ __forceinline__ void sample_row(Shared& sh, const T* __restrict__ logits, int V, int BS, float temp, int top_k, float top_p,
-                                           float min_p, uint32_t c0, uint64_t seed, int64_t n, int64_t* __restrict__ out) {
+// Counter word 0 of the draw is `c0`, the key `seed`, the draw index `n`.  `row`: the reader of the row's scores (Row, or PenRow with
+// the penalties of kivi_sample_rows_pen).  Returns the token (every thread).
+template <class R>
+__device__ __forceinline__ int sample_row(Shared& sh, const R& row, int V, int BS, int top_k, float top_p, float min_p, uint32_t c0,
+                                          uint64_t seed, int64_t n, int64_t* __restrict__ out) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const Row<T> row{logits, temp, temp != 1.0f};
     const int nbk = (V + BS - 1) / BS, bpw = (nbk + kWaves - 1) / kWaves;
     const int bk0 = min(nbk, wave * bpw), bk1 = min(nbk, (wave + 1) * bpw);
     const int e0 = min(V, bk0 * BS), e1 = min(V, bk1 * BS);
@@ -244,14 +292,15 @@ __device__ __forceinline__ void sample_row(Shared& sh, const T* __restrict__ log
     }
     __syncthreads();
     if (tid == 0) *out = (int64_t)sh.token;
+    return (int)sh.token;
 }
 
 // A greedy row: the lowest index that maximises float(logit) (-0 and +0 tie), the tie rule of kivi_token_logprob's rank.  The key
 // image orders -inf below every finite value, so a -inf logit wins only when the whole row is -inf; NaN / +inf rows get some index.
-template <typename T>
-__device__ __forceinline__ void greedy_row(Shared& sh, const T* __restrict__ logits, int V, int64_t* __restrict__ out) {
+// Returns the token on thread 0 (0 on the others).
+template <class R>
+__device__ __forceinline__ int greedy_row(Shared& sh, const R& row, int V, int64_t* __restrict__ out) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const Row<T> row{logits, 1.0f, false};
     uint64_t best = 0;                                // (key << 32) | ~index: the maximum is the largest key at the lowest index
     for (int e = tid; e < V; e += kThreads) best = max(best, ((uint64_t)key_of(row.s(e)) << 32) | (uint32_t)~(uint32_t)e);
 #pragma unroll
@@ -264,8 +313,11 @@ __device__ __forceinline__ void greedy_row(Shared& sh, const T* __restrict__ log
     if (tid == 0) {
         for (int w = 0; w < kWaves; ++w) best = max(best, sh.wsum[w]);
         const uint32_t j = ~(uint32_t)best;
-        *out = j < (uint32_t)V ? (int64_t)j : 0;      // (V >= 1: thread 0 always has an entry, so j < V; the guard is for form)
+        const uint32_t tok = j < (uint32_t)V ? j : 0;  // (V >= 1: thread 0 always has an entry, so j < V; the guard is for form)
+        *out = (int64_t)tok;
+        return (int)tok;
     }
+    return 0;
 }
 
 template <typename T>
@@ -273,8 +325,26 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const T* __restrict__ 
                                                           int top_k, float top_p, float min_p, const int64_t* __restrict__ state,
                                                           int64_t* __restrict__ out, int64_t out_stride) {
     __shared__ Shared sh;
-    sample_row<T>(sh, logits + (int64_t)blockIdx.x * row_stride, V, BS, temp, top_k, top_p, min_p, blockIdx.x, (uint64_t)state[0],
-                  state[1], out + (int64_t)blockIdx.x * out_stride);
+    sample_row(sh, Row<T>{logits + (int64_t)blockIdx.x * row_stride, temp, temp != 1.0f}, V, BS, top_k, top_p, min_p, blockIdx.x,
+               (uint64_t)state[0], state[1], out + (int64_t)blockIdx.x * out_stride);
+}
+
+// The row body of sample_rows_kernel (below, kept as it was) over any reader, for sample_rows_pen_kernel: the greedy or the sampling
+// path -- a block-uniform choice -- over `row`, whose temp / div this sets, with the same clamps of a record outside the contract.
+// Returns the token on thread 0.
+template <class R>
+__device__ __forceinline__ int rows_token(Shared& sh, R row, const kivi_sample_row& r, int V, int BS, int64_t n,
+                                          int64_t* __restrict__ dst) {
+    const bool greedy = (r.flags & KIVI_SAMPLE_ROW_GREEDY) || !(r.temperature > 0.0f) || !__builtin_isfinite(r.temperature);
+    if (greedy) return greedy_row(sh, row, V, dst);                     // (temp 1, no division)
+    row.temp = r.temperature;
+    row.div = r.temperature != 1.0f;
+    const int top_k = max(r.top_k, 0);
+    float top_p = r.top_p <= 1.0f ? r.top_p : 1.0f;                     // NaN and > 1: off
+    if (!(top_p > 0.0f)) top_p = 1.17549435e-38f;                       // <= 0: the smallest (0, 1] value, the top class alone
+    float min_p = r.min_p >= 0.0f ? r.min_p : 0.0f;                     // NaN and < 0: off
+    if (min_p >= 1.0f) min_p = 0.99999994f;                             // the largest value below 1: the maximum stays
+    return sample_row(sh, row, V, BS, top_k, top_p, min_p, r.stream, (uint64_t)r.seed, n, dst);
 }
 
 // Per-row parameters and RNG streams (kivi_sample_rows): block b reads rows[b] and draw_index[b], takes the greedy or the sampling
@@ -293,16 +363,94 @@ __global__ __launch_bounds__(kThreads) void sample_rows_kernel(const T* __restri
     int64_t* dst = out + (int64_t)b * out_stride;
     const bool greedy = (r.flags & KIVI_SAMPLE_ROW_GREEDY) || !(r.temperature > 0.0f) || !__builtin_isfinite(r.temperature);
     if (greedy) {
-        greedy_row<T>(sh, row, V, dst);
+        greedy_row(sh, Row<T>{row, 1.0f, false}, V, dst);
     } else {
         const int top_k = max(r.top_k, 0);
         float top_p = r.top_p <= 1.0f ? r.top_p : 1.0f;                 // NaN and > 1: off
         if (!(top_p > 0.0f)) top_p = 1.17549435e-38f;                   // <= 0: the smallest (0, 1] value, the top class alone
         float min_p = r.min_p >= 0.0f ? r.min_p : 0.0f;                 // NaN and < 0: off
         if (min_p >= 1.0f) min_p = 0.99999994f;                         // the largest value below 1: the maximum stays
-        sample_row<T>(sh, row, V, BS, r.temperature, top_k, top_p, min_p, r.stream, (uint64_t)r.seed, n, dst);
+        sample_row(sh, Row<T>{row, r.temperature, r.temperature != 1.0f}, V, BS, top_k, top_p, min_p, r.stream, (uint64_t)r.seed, n,
+                   dst);
     }
     if (threadIdx.x == 0) draw_index[b] = n + 1;
+}
+
+// kivi_sample_rows_pen: the same block per row, with the row's penalty record and its row of the history
+// table.  A block whose record is neutral after the clamps of the header -- a block-uniform fact -- takes the reader of
+// sample_rows_kernel and loads nothing from the table; any other first folds the row's history into a bitmap of 64-token chunks in
+// LDS (mark_chunks), so that the passes touch the table only where something is marked.  Either way thread 0 then counts the token it has just written: one 16-bit
+// load, one plain 16-bit vector store, after the last barrier of the row body, so after every read of the table by this block; no
+// other block reads or writes this row of the table.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void sample_rows_pen_kernel(const T* __restrict__ logits, int64_t row_stride, int V, int BS,
+                                                                   const kivi_sample_row* __restrict__ rows, int64_t* draw_index,
+                                                                   const kivi_sample_penalty* __restrict__ pen, uint16_t* seen,
+                                                                   int64_t seen_stride, int64_t* __restrict__ out, int64_t out_stride) {
+    __shared__ Shared sh;
+    __shared__ uint8_t marks[KIVI_SAMPLE_MAX_V / 512];
+    const int b = blockIdx.x;
+    const kivi_sample_row r = rows[b];
+    const int64_t n = draw_index[b];
+    float theta = pen[b].repetition, pres = pen[b].presence, freq = pen[b].frequency;
+    if (!(theta > 0.0f) || !__builtin_isfinite(theta)) theta = 1.0f;
+    if (!__builtin_isfinite(pres)) pres = 0.0f;
+    if (!__builtin_isfinite(freq)) freq = 0.0f;
+    const T* row = logits + (int64_t)b * row_stride;
+    uint16_t* hist = seen + (int64_t)b * seen_stride;
+    int64_t* dst = out + (int64_t)b * out_stride;
+    int tok;
+    if (theta == 1.0f && pres == 0.0f && freq == 0.0f) {
+        tok = rows_token(sh, Row<T>{row, 1.0f, false}, r, V, BS, n, dst);
+    } else {
+        mark_chunks(marks, hist, V);
+        __syncthreads();
+        tok = rows_token(sh, PenRow<T>{row, 1.0f, false, hist, theta, pres, freq, marks}, r, V, BS, n, dst);
+    }
+    if (threadIdx.x == 0) {
+        draw_index[b] = n + 1;
+        const uint16_t w = hist[tok];                                   // tok in [0, V), V <= seen_stride
+        if ((w & 0x7FFFu) != 0x7FFFu) hist[tok] = (uint16_t)(w + 1);
+    }
+}
+
+// kivi_seen_mark: block i serves destination row rows[i] (null: i).  CLEAR zeroes the row's seen_stride words with 16-byte stores;
+// a fence and a barrier put the marks of the same block after them.  Two tokens share a 32-bit word of the table, so a mark is an
+// atomic on that word: an OR of bit 15 (PROMPT), or a compare-and-swap that adds 1 to the 15-bit count unless it is 32767 (OUTPUT;
+// a plain add would carry into bit 15).  Each failed swap is another thread's success, so the loop ends.
+__global__ __launch_bounds__(256) void seen_mark_kernel(uint16_t* seen, int64_t seen_stride, int V, const int32_t* __restrict__ rows,
+                                                        const int64_t* __restrict__ tokens, int64_t tok_row_stride, int T,
+                                                        const int32_t* __restrict__ lead, int flags) {
+    const int i = blockIdx.x;
+    const int64_t d = rows ? (int64_t)rows[i] : (int64_t)i;
+    if (d < 0) return;                                                  // (block-uniform)
+    uint16_t* hist = seen + d * seen_stride;
+    if (flags & KIVI_SEEN_CLEAR) {
+        uint4* q = reinterpret_cast<uint4*>(hist);
+        for (int64_t j = threadIdx.x; j < seen_stride / 8; j += blockDim.x) q[j] = make_uint4(0, 0, 0, 0);
+        __threadfence();
+        __syncthreads();
+    }
+    if (!(flags & (KIVI_SEEN_PROMPT | KIVI_SEEN_OUTPUT))) return;
+    const int t0 = lead ? min(max(lead[i], 0), T) : 0;
+    unsigned int* words = reinterpret_cast<unsigned int*>(hist);
+    const int64_t* tk = tokens + (int64_t)i * tok_row_stride;
+    for (int t = t0 + (int)threadIdx.x; t < T; t += blockDim.x) {
+        const int64_t id = tk[t];
+        if (id < 0 || id >= V) continue;
+        unsigned int* w = words + (id >> 1);
+        const int sft = (int)(id & 1) * 16;
+        if (flags & KIVI_SEEN_PROMPT) {
+            atomicOr(w, 0x8000u << sft);
+        } else {
+            unsigned int old = __atomic_load_n(w, __ATOMIC_RELAXED);
+            while (((old >> sft) & 0x7FFFu) != 0x7FFFu) {
+                const unsigned int got = atomicCAS(w, old, old + (1u << sft));
+                if (got == old) break;
+                old = got;
+            }
+        }
+    }
 }
 
 __global__ void advance_kernel(int64_t* state) { state[1] += 1; }
@@ -364,4 +512,60 @@ extern "C" int kivi_sample_rows(const void* logits, int logits_bits, int64_t row
         KIVI_LAUNCH(sample_rows_kernel<float>, dim3(B), dim3(kThreads), s, (const float*)logits, row_stride, V, BS, rows, draw_index,
                     out_tokens, out_stride);
     return kivi_launch_status("kivi_sample_rows");
+}
+
+extern "C" int kivi_sample_rows_pen(const void* logits, int logits_bits, int64_t row_stride, int B, int V, const kivi_sample_row* rows,
+                                    int64_t* draw_index, const kivi_sample_penalty* pen, uint16_t* seen, int64_t seen_stride,
+                                    int64_t* out_tokens, int64_t out_stride, kivi_stream_t stream) {
+    KIVI_REQUIRE(logits_bits == 16 || logits_bits == 32, KIVI_EINVAL, "kivi_sample_rows_pen: logits_bits=%d (16: fp16, 32: fp32)",
+                 logits_bits);
+    KIVI_REQUIRE(B >= 1 && B <= KIVI_SAMPLE_MAX_B, KIVI_EINVAL, "kivi_sample_rows_pen: B=%d (1 <= B <= %d)", B, KIVI_SAMPLE_MAX_B);
+    KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "kivi_sample_rows_pen: V=%d (1 <= V <= %d)", V, KIVI_SAMPLE_MAX_V);
+    KIVI_REQUIRE(row_stride >= V || B == 1, KIVI_EINVAL, "kivi_sample_rows_pen: row_stride=%lld below V=%d", (long long)row_stride, V);
+    KIVI_REQUIRE(out_stride >= 1 || B == 1, KIVI_EINVAL, "kivi_sample_rows_pen: out_stride=%lld", (long long)out_stride);
+    KIVI_REQUIRE(logits && rows && draw_index && out_tokens && pen && seen, KIVI_EINVAL, "kivi_sample_rows_pen: null pointer");
+    KIVI_REQUIRE(seen_stride >= V, KIVI_EINVAL, "kivi_sample_rows_pen: seen_stride=%lld below V=%d", (long long)seen_stride, V);
+    const int esz = logits_bits / 8;
+    KIVI_REQUIRE((uintptr_t)logits % esz == 0 && (uintptr_t)rows % 8 == 0 && (uintptr_t)draw_index % 8 == 0 &&
+                     (uintptr_t)out_tokens % 8 == 0,
+                 KIVI_EALIGN, "kivi_sample_rows_pen: misaligned logits (%d-byte elements), rows, draw_index or out_tokens (8 bytes)",
+                 esz);
+    KIVI_REQUIRE((uintptr_t)pen % 4 == 0 && (uintptr_t)seen % 16 == 0 && seen_stride % 8 == 0, KIVI_EALIGN,
+                 "kivi_sample_rows_pen: misaligned pen (4 bytes) or seen (16 bytes), or seen_stride=%lld not a multiple of 8",
+                 (long long)seen_stride);
+    int BS = KIVI_WAVE;                              // as kivi_sample
+    while ((int64_t)BS * 1024 < V) BS <<= 1;
+    const hipStream_t s = (hipStream_t)stream;
+    if (logits_bits == 16)
+        KIVI_LAUNCH(sample_rows_pen_kernel<f16>, dim3(B), dim3(kThreads), s, (const f16*)logits, row_stride, V, BS, rows, draw_index,
+                    pen, seen, seen_stride, out_tokens, out_stride);
+    else
+        KIVI_LAUNCH(sample_rows_pen_kernel<float>, dim3(B), dim3(kThreads), s, (const float*)logits, row_stride, V, BS, rows,
+                    draw_index, pen, seen, seen_stride, out_tokens, out_stride);
+    return kivi_launch_status("kivi_sample_rows_pen");
+}
+
+extern "C" int kivi_seen_mark(uint16_t* seen, int64_t seen_stride, int V, const int32_t* rows, int n, const int64_t* tokens,
+                              int64_t tok_row_stride, int T, const int32_t* lead, int flags, kivi_stream_t stream) {
+    const int marks = flags & (KIVI_SEEN_PROMPT | KIVI_SEEN_OUTPUT);
+    KIVI_REQUIRE(flags != 0 && !(flags & ~(KIVI_SEEN_CLEAR | KIVI_SEEN_PROMPT | KIVI_SEEN_OUTPUT)) &&
+                     marks != (KIVI_SEEN_PROMPT | KIVI_SEEN_OUTPUT),
+                 KIVI_EINVAL, "kivi_seen_mark: flags=%d (KIVI_SEEN_CLEAR, and at most one of KIVI_SEEN_PROMPT / KIVI_SEEN_OUTPUT)", flags);
+    KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "kivi_seen_mark: V=%d (1 <= V <= %d)", V, KIVI_SAMPLE_MAX_V);
+    KIVI_REQUIRE(n >= 1 && n <= KIVI_SAMPLE_MAX_B, KIVI_EINVAL, "kivi_seen_mark: n=%d (1 <= n <= %d)", n, KIVI_SAMPLE_MAX_B);
+    KIVI_REQUIRE(T >= 0, KIVI_EINVAL, "kivi_seen_mark: T=%d", T);
+    KIVI_REQUIRE(seen, KIVI_EINVAL, "kivi_seen_mark: null seen");
+    KIVI_REQUIRE(seen_stride >= V, KIVI_EINVAL, "kivi_seen_mark: seen_stride=%lld below V=%d", (long long)seen_stride, V);
+    KIVI_REQUIRE(tokens || T == 0 || !marks, KIVI_EINVAL, "kivi_seen_mark: null tokens with T=%d", T);
+    KIVI_REQUIRE(tok_row_stride >= T || n == 1, KIVI_EINVAL, "kivi_seen_mark: tok_row_stride=%lld below T=%d",
+                 (long long)tok_row_stride, T);
+    KIVI_REQUIRE((uintptr_t)seen % 16 == 0 && seen_stride % 8 == 0, KIVI_EALIGN,
+                 "kivi_seen_mark: misaligned seen (16 bytes), or seen_stride=%lld not a multiple of 8", (long long)seen_stride);
+    KIVI_REQUIRE((uintptr_t)rows % 4 == 0 && (uintptr_t)lead % 4 == 0 && (uintptr_t)tokens % 8 == 0, KIVI_EALIGN,
+                 "kivi_seen_mark: misaligned rows or lead (4 bytes) or tokens (8 bytes)");
+    const bool mark = marks && T > 0;
+    if (!mark && !(flags & KIVI_SEEN_CLEAR)) return 0;                  // nothing to do, nothing enqueued
+    KIVI_LAUNCH(seen_mark_kernel, dim3(n), dim3(256), (hipStream_t)stream, seen, seen_stride, V, rows, tokens, tok_row_stride,
+                mark ? T : 0, lead, mark ? flags : KIVI_SEEN_CLEAR);
+    return kivi_launch_status("kivi_seen_mark");
 }

@@ -113,11 +113,25 @@ class _PaddedBatch:
 
 
 def resolve_sampler(device, B: int, num_return_sequences: int, num_beams: int, do_sample: bool, temperature, top_k, top_p, min_p,
-                    seed, sampling):
+                    seed, sampling, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
+                    vocab_size: Optional[int] = None):
     """The sampler of a generate / generate_graphed call -> (pick, fan): `pick(logits) -> tokens` is a Sampler (`do_sample=True`), a
     RowSampler (`sampling=`: B requests with `fan` = num_return_sequences samples each, row b * fan + j is request b with Philox
-    stream j) or None (greedy); without `sampling=` fan is 1.  Every argument is checked before anything runs on a device."""
-    from .sampling import RowSampler, Sampler, SamplingParams
+    stream j) or None (greedy); without `sampling=` fan is 1.  Every argument is checked before anything runs on a device.
+    A non-neutral `repetition_penalty` / `presence_penalty` / `frequency_penalty` without `sampling=`: a
+    RowSampler of B identical rows with streams 0..B-1 and the call's seed -- by the identity of kivi_sample_rows what the Sampler
+    would have drawn from the penalised logits --, greedy rows when `do_sample=False`; not with beams.  With `sampling=` the penalties
+    come from the SamplingParams, the three arguments have to be neutral.  `vocab_size`: the width of the history table of a
+    RowSampler made here for penalised rows."""
+    from .sampling import NEUTRAL, RowSampler, Sampler, SamplingParams, check_penalties
+    check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+    penalised = (float(repetition_penalty), float(presence_penalty), float(frequency_penalty)) != NEUTRAL
+    if sampling is None and penalised:
+        if num_beams != 1:
+            raise ValueError(f"repetition / presence / frequency penalties with beam search (num_beams={num_beams}) are not supported")
+        p = RowSampler._bind(SamplingParams(bool(do_sample), temperature, top_k, top_p, min_p, seed, repetition_penalty=repetition_penalty,
+                                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty))
+        return RowSampler([p] * B, device, list(range(B)), vocab_size=vocab_size), 1
     if sampling is None:
         if not do_sample:
             return None, 1
@@ -125,9 +139,10 @@ def resolve_sampler(device, B: int, num_return_sequences: int, num_beams: int, d
             raise ValueError(f"beam sampling (do_sample=True with num_beams={num_beams}) is not supported")
         return Sampler(temperature, top_k, top_p, min_p, seed, device), 1
     n = num_return_sequences
-    if do_sample or temperature != 1.0 or top_k != 50 or top_p != 1.0 or min_p is not None or seed is not None:
+    if do_sample or temperature != 1.0 or top_k != 50 or top_p != 1.0 or min_p is not None or seed is not None or penalised:
         raise ValueError("sampling= carries the parameters of every row: it cannot be combined with do_sample=True or with "
-                         "temperature / top_k / top_p / min_p / seed arguments")
+                         "temperature / top_k / top_p / min_p / seed / repetition_penalty / presence_penalty / frequency_penalty "
+                         "arguments")
     if num_beams != 1:
         raise ValueError(f"sampling= with beam search (num_beams={num_beams}) is not supported")
     if isinstance(n, bool) or not isinstance(n, int) or n < 1:
@@ -143,7 +158,23 @@ def resolve_sampler(device, B: int, num_return_sequences: int, num_beams: int, d
     if len(sampling) != B:
         raise ValueError(f"{len(sampling)} SamplingParams for a batch of {B} requests")
     bound = [RowSampler._bind(p) for p in sampling]          # one seed per request, shared by its n streams
-    return RowSampler([p for p in bound for _ in range(n)], device, [j for _ in bound for j in range(n)]), n
+    return RowSampler([p for p in bound for _ in range(n)], device, [j for _ in bound for j in range(n)],
+                      vocab_size=vocab_size if any(p.penalised for p in bound) else None), n
+
+
+def observe_prompts(pick, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], fan: int = 1) -> None:
+    """A generate call marks its `input_ids` (B, T) in the history table of its RowSampler, if it has one (any other `pick` knows no
+    history): without the pads of HF's 2D mask (B, past + T), whose last T columns cover `input_ids`, and `fan` times per request,
+    once for every forked row.  With `past_key_values` only this call's `input_ids` are known: the earlier turns stay marked only
+    in a RowSampler that the caller passes again."""
+    if getattr(pick, "seen", None) is None:
+        return
+    T = input_ids.shape[1]
+    mask = None if attention_mask is None or attention_mask.dim() != 2 else attention_mask[:, attention_mask.shape[1] - T:]
+    if fan > 1:
+        input_ids = input_ids.repeat_interleave(fan, dim=0)
+        mask = None if mask is None else mask.repeat_interleave(fan, dim=0)
+    pick.observe_prompt(input_ids, attention_mask=mask)
 
 
 class EagerStepper:

@@ -28,7 +28,8 @@ from . import admit
 from .attention import KiviLayerCacheMF, LlamaAttention_KIVI
 from .beam import beam_search
 from .generation import (PADS_LEFT, DecodeLead, EagerStepper, _PaddedBatch, decode_loop, leading_pads, left_pad,  # noqa: F401
-                         padding_key_row, padding_position_ids, padding_prompt_mask, resolve_sampler)
+                         padding_key_row, padding_position_ids, padding_prompt_mask, observe_prompts,
+                         resolve_sampler)
 from .graph import DecodeGraphs
 from .prefill import left_padded
 from .sampling import RowSampler
@@ -411,7 +412,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
                  pad_token_id: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False, do_sample: bool = False,
                  temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
-                 seed: Optional[int] = None, return_logprobs: bool = False, sampling=None):
+                 seed: Optional[int] = None, return_logprobs: bool = False, sampling=None, repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
         """Greedy decoding (the recipe of the reference's mem_spd_test.py / example.py), or sampling with `do_sample=True`.
         With `past_key_values` (the caches of an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one
         pass (kivi_attention_extend) and decoding continues from there; the caches are advanced in place.  `attention_mask`:
@@ -444,12 +446,23 @@ class LlamaForCausalLM_KIVI(nn.Module):
         bit from the second new token on (the same head call on the same states); the first new token is scored on the prompt
         pass, whose head runs here on the last position alone and in score() on all T positions -- the same arithmetic, in
         whatever kernel the GEMM library picks for each row count.
-        With beams use `return_scores`."""
+        With beams use `return_scores`.
+
+        `repetition_penalty` (HF, vLLM: over prompt and output tokens), `presence_penalty`, `frequency_penalty` (OpenAI, vLLM: over
+        output tokens): applied inside the fused sampler (kivi_sample_rows_pen), greedy rows included.
+        Non-neutral values make the call's sampler a RowSampler of identical rows (Philox streams 0..B-1, the call's `seed`), which
+        draws what `do_sample=True` would have drawn from the penalised logits; with `sampling=` the penalties are those of the
+        SamplingParams and the three arguments stay neutral.  The call marks its `input_ids` as the prompts (pads of the 2D mask
+        are not marked; `num_return_sequences` forks carry the marks).  Not with beams.  `return_logprobs` stays under the RAW
+        distribution.  Two facts: the loop's trailing pick (decode_loop) counts one token more than the call returns; and with
+        `past_key_values` only this call's `input_ids` are known as prompt -- the earlier turns count only when the caller passes
+        the same RowSampler again (`sampling=`), whose table keeps them."""
         if return_logprobs and num_beams > 1:
             raise ValueError("return_logprobs is for greedy decoding and sampling; beam search (num_beams > 1) returns its "
                              "sequences_scores with return_scores=True")
         pick, fan = resolve_sampler(input_ids.device, input_ids.shape[0], num_return_sequences, num_beams, do_sample, temperature,
-                                    top_k, top_p, min_p, seed, sampling)
+                                    top_k, top_p, min_p, seed, sampling, repetition_penalty, presence_penalty, frequency_penalty,
+                                    self.config.vocab_size)
         if eos_token_id is not None and pad_token_id is None:
             raise ValueError("eos_token_id needs a pad_token_id for the rows that have finished")
         if sampling is None and (num_beams < 1 or num_return_sequences < 1 or num_return_sequences > num_beams):
@@ -457,6 +470,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
         if return_scores and num_beams == 1:
             raise ValueError("return_scores: sequences_scores exist for beam search (num_beams > 1) only")
         stepper = EagerStepper(self, input_ids, past_key_values, attention_mask, max_new_tokens, max(num_beams, fan))
+        observe_prompts(pick, input_ids, attention_mask, fan)
         if num_beams > 1:
             seqs, scores = beam_search(stepper.step, input_ids, stepper.logits, num_beams, max_new_tokens, eos_token_id,
                                        pad_token_id, length_penalty, early_stopping, num_return_sequences)
@@ -513,17 +527,21 @@ class LlamaForCausalLM_KIVI(nn.Module):
     def generate_graphed(self, input_ids: torch.LongTensor, max_new_tokens: int,
                          attention_mask: Optional[torch.Tensor] = None, num_beams: int = 1, do_sample: bool = False,
                          temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
-                         seed: Optional[int] = None, sampling=None) -> torch.LongTensor:
+                         seed: Optional[int] = None, sampling=None, repetition_penalty: float = 1.0,
+                         presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> torch.LongTensor:
         """generate() with the dense part of every decode step replayed from hipGraphs (kivi_amd.graph.DecodeGraphs).
         `attention_mask`: HF's 2D (B, T) mask of left-padded prompts (1 = real token).  Greedy, or sampling with `do_sample=True`
         and the parameters of generate() (the draw inside the graph; the same tokens as generate() with the same seed).  Beams
         are refused (a graphed beam step is open; use generate()).  `sampling=`: per-request parameters as in
-        generate() (a SamplingParams, a list of B, or a RowSampler of B rows); the graphs are keyed by the RowSampler's buffers."""
+        generate() (a SamplingParams, a list of B, or a RowSampler of B rows); the graphs are keyed by the RowSampler's buffers.
+        `repetition_penalty` / `presence_penalty` / `frequency_penalty`: as in generate(); the penalised draw and the count of its
+        token are inside the captured step."""
         if sampling is None and num_beams != 1 and not do_sample:
             raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
         pick, _ = resolve_sampler(input_ids.device, input_ids.shape[0], 1, num_beams, do_sample, temperature, top_k, top_p, min_p,
-                                  seed, sampling)
+                                  seed, sampling, repetition_penalty, presence_penalty, frequency_penalty, self.config.vocab_size)
         logits, pasts = self.forward(input_ids, padding_mask=attention_mask)
+        observe_prompts(pick, input_ids, attention_mask)
         if attention_mask is not None:
             attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, :1])], dim=1)
         tok = logits.argmax(-1) if pick is None else pick(logits)

@@ -10,8 +10,13 @@ u * (kept mass), u = (x0 >> 8) * 2^-24 from Philox4x32-10 at key (seed low, seed
 device memory (kivi_sample_rows), so requests with different parameters -- greedy ones among them -- share one launch, a row's
 tokens do not depend on its place in the batch, and a captured decode step depends on two buffers, not on parameter values.
 
-`philox4x32` and `reference_sample` (fp64, explicit u) restate the contract on the CPU for tests and tools; the product path
-never calls them.
+Penalties: `SamplingParams(repetition_penalty=, presence_penalty=, frequency_penalty=)`; a RowSampler made with
+`vocab_size=` owns one penalty record per row and a history table (row, token) in device memory, draws through
+kivi_sample_rows_pen -- the penalties applied where the kernel reads a logit, the drawn token counted where it is written -- and
+marks prompts and earlier outputs with kivi_seen_mark (`observe_prompt`, `set_row(prompt=, generated=)`).
+
+`philox4x32`, `reference_sample` (fp64, explicit u) and `reference_penalise` (fp32, the kernel's bits) restate the contract on the
+CPU for tests and tools; the product path never calls them.
 """
 from __future__ import annotations
 
@@ -40,6 +45,21 @@ def check_params(temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, 
         raise ValueError(f"top_p has to be a float in (0, 1] (1 = off), got {top_p!r}")
     if min_p is not None and (not isinstance(min_p, (int, float)) or not (0.0 <= min_p < 1.0)):
         raise ValueError(f"min_p has to be None or a float in [0, 1), got {min_p!r}")
+
+
+NEUTRAL = (1.0, 0.0, 0.0)     # (repetition_penalty, presence_penalty, frequency_penalty) that change nothing
+
+
+def check_penalties(repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> None:
+    """Raise ValueError, naming the field, for a penalty outside its range (no device work)."""
+    def real(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v)
+    if not real(repetition_penalty) or repetition_penalty <= 0:
+        raise ValueError(f"repetition_penalty has to be a strictly positive finite float (1 = off), got {repetition_penalty!r}")
+    if not real(presence_penalty):
+        raise ValueError(f"presence_penalty has to be a finite float (0 = off), got {presence_penalty!r}")
+    if not real(frequency_penalty):
+        raise ValueError(f"frequency_penalty has to be a finite float (0 = off), got {frequency_penalty!r}")
 
 
 def check_seed(seed) -> None:
@@ -122,19 +142,53 @@ class SampleRow(ctypes.Structure):
 class SamplingParams:
     """The sampling parameters of one request, with HF's names, ranges and defaults.  `do_sample=False`: a greedy row (the lowest
     index of the largest logit; the other fields are still validated, and ignored).  `seed=None`: one is drawn with draw_seed()
-    when the parameters are bound to a row of a RowSampler."""
+    when the parameters are bound to a row of a RowSampler.
+    `repetition_penalty` (HF, vLLM: over prompt and output tokens; finite, > 0, 1 = off), `presence_penalty` and `frequency_penalty`
+    (OpenAI, vLLM: over output tokens; finite, 0 = off): DESIGN.md section 22; greedy rows are penalised too.  The three are
+    init-only variables that __post_init__ stores: they are attributes, keywords of the constructor and of dataclasses.replace,
+    and part of ==, hash and repr, while the dataclass's own field tuple -- astuple(), positional construction -- stays the six
+    fields above."""
     do_sample: bool = True
     temperature: float = 1.0
     top_k: int = 50
     top_p: float = 1.0
     min_p: Optional[float] = None
     seed: Optional[int] = None
+    repetition_penalty: dataclasses.InitVar[float] = 1.0
+    presence_penalty: dataclasses.InitVar[float] = 0.0
+    frequency_penalty: dataclasses.InitVar[float] = 0.0
 
-    def __post_init__(self):
+    def __post_init__(self, repetition_penalty, presence_penalty, frequency_penalty):
         if not isinstance(self.do_sample, bool):
             raise ValueError(f"do_sample has to be a bool, got {self.do_sample!r}")
         check_params(self.temperature, self.top_k, self.top_p, self.min_p)
         check_seed(self.seed)
+        check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        for name, v in (("repetition_penalty", repetition_penalty), ("presence_penalty", presence_penalty),
+                        ("frequency_penalty", frequency_penalty)):
+            object.__setattr__(self, name, float(v))
+
+    @property
+    def penalties(self):
+        """(repetition_penalty, presence_penalty, frequency_penalty)."""
+        return (self.repetition_penalty, self.presence_penalty, self.frequency_penalty)
+
+    @property
+    def penalised(self) -> bool:
+        return self.penalties != NEUTRAL
+
+    def __eq__(self, other):
+        if other.__class__ is not self.__class__:
+            return NotImplemented
+        return dataclasses.astuple(self) + self.penalties == dataclasses.astuple(other) + other.penalties
+
+    def __hash__(self):
+        return hash(dataclasses.astuple(self) + self.penalties)
+
+    def __repr__(self):
+        body = [f"{f.name}={getattr(self, f.name)!r}" for f in dataclasses.fields(self)]
+        body += [f"{n}={getattr(self, n)!r}" for n in ("repetition_penalty", "presence_penalty", "frequency_penalty")]
+        return f"SamplingParams({', '.join(body)})"
 
 
 def _check_stream(stream) -> int:
@@ -151,16 +205,51 @@ def _record(p: SamplingParams, stream: int) -> torch.Tensor:
     return torch.tensor(np.frombuffer(bytes(rec), dtype=np.int64))
 
 
+SEEN_CLEAR, SEEN_PROMPT, SEEN_OUTPUT = 1, 2, 4     # include/kivi_hip.h: KIVI_SEEN_*
+SEEN_PROMPT_BIT, SEEN_COUNT_MAX = 0x8000, 0x7FFF   # a word of the history table: bit 15 = in the prompt, bits 0-14 = times emitted
+
+
+class SamplePenalty(ctypes.Structure):
+    """include/kivi_hip.h: kivi_sample_penalty (16 bytes)."""
+    _fields_ = [("repetition", ctypes.c_float), ("presence", ctypes.c_float), ("frequency", ctypes.c_float),
+                ("reserved", ctypes.c_uint32)]
+
+
+def _penalty_record(p: SamplingParams) -> torch.Tensor:
+    """The 16 bytes of one row's kivi_sample_penalty as 4 fp32 on the CPU (the reserved word 0 is the bits of 0.0)."""
+    rec = SamplePenalty(p.repetition_penalty, p.presence_penalty, p.frequency_penalty, 0)
+    return torch.tensor(np.frombuffer(bytes(rec), dtype=np.float32))
+
+
+def _token_rows(tokens, device) -> Optional[torch.Tensor]:
+    """Token ids (a sequence, a 1-D or a 2-D tensor) as (n, T) int64 on `device` with unit inner stride; None when there are none."""
+    if tokens is None:
+        return None
+    t = torch.as_tensor(tokens, dtype=torch.long)
+    t = t.reshape(1, -1) if t.dim() < 2 else t
+    if t.dim() != 2:
+        raise ValueError(f"token ids have to be (T,) or (n, T), got {tuple(t.shape)}")
+    if not t.numel():
+        return None
+    t = t.to(device)
+    return t if t.stride(1) == 1 else t.contiguous()
+
+
 class RowSampler:
     """The fused sampler with one record {temperature, top_k, top_p, min_p, seed, stream, greedy} and one draw index per row, both
     in device memory and owned by the sampler (`records` (B, 4) int64, `draw_index` (B,) int64).  `params`: one SamplingParams for
     every row, or a sequence of B of them; `streams`: the Philox stream of every row (default 0, so a request with seed s draws in
     ANY row what Sampler(seed=s) draws for a batch of one); rows that share a seed need different streams to draw differently.
     `B`: the number of rows when `params` is a single SamplingParams (default 1).
+    `vocab_size`: the sampler also owns the state of the penalties: `penalties` (B, 4) fp32, one
+    kivi_sample_penalty per row, and `seen` (B, vocab_size rounded up to 8) int16, the history table -- bit 15 of a word: the token
+    is in the row's prompt, bits 0-14: how often the row has emitted it.  Both are allocated here, once, so before anything can be
+    captured; calls then go through kivi_sample_rows_pen, which counts every token it draws.  Without it (None) the sampler is
+    what it was, and penalised `params` are refused: the table's width has to be known here.
     Every argument is checked before a device is touched."""
 
     def __init__(self, params: Union[SamplingParams, Sequence[SamplingParams]], device="cuda",
-                 streams: Optional[Sequence[int]] = None, B: Optional[int] = None):
+                 streams: Optional[Sequence[int]] = None, B: Optional[int] = None, vocab_size: Optional[int] = None):
         if isinstance(params, SamplingParams):
             if B is None:
                 B = 1 if streams is None else len(streams)
@@ -176,10 +265,20 @@ class RowSampler:
         streams = [0] * len(params) if streams is None else [_check_stream(s) for s in streams]
         if len(streams) != len(params):
             raise ValueError(f"{len(streams)} streams for {len(params)} rows")
+        if vocab_size is not None and (isinstance(vocab_size, bool) or not isinstance(vocab_size, int)
+                                       or not 1 <= vocab_size <= _lib.SAMPLE_MAX_V):
+            raise ValueError(f"vocab_size has to be None or an integer in [1, {_lib.SAMPLE_MAX_V}], got {vocab_size!r}")
+        if vocab_size is None and any(p.penalised for p in params):
+            raise ValueError("a row has a repetition / presence / frequency penalty: pass vocab_size= so that the sampler can "
+                             "allocate its history table")
         self.params = [self._bind(p) for p in params]
         self.streams = streams
         self.records = torch.stack([_record(p, s) for p, s in zip(self.params, streams)]).to(device)
         self.draw_index = torch.zeros(len(params), dtype=torch.int64, device=device)
+        self.vocab_size, self.penalties, self.seen = vocab_size, None, None
+        if vocab_size is not None:
+            self.penalties = torch.stack([_penalty_record(p) for p in self.params]).to(device)
+            self.seen = torch.zeros((len(params), (vocab_size + 7) // 8 * 8), dtype=torch.int16, device=device)
 
     @staticmethod
     def _bind(p: SamplingParams) -> SamplingParams:
@@ -191,13 +290,60 @@ class RowSampler:
 
     def key(self):
         """What a captured call depends on: the number of rows and the two buffers -- not the parameter values, which a replay reads
-        from the records.  (The leading string keeps it apart from every Sampler.key().)"""
-        return ("rows", self.B, self.records.data_ptr(), self.draw_index.data_ptr())
+        from the records -- and, when they exist, the penalty records and the history table.  (The leading string keeps it apart
+        from every Sampler.key().)"""
+        key = ("rows", self.B, self.records.data_ptr(), self.draw_index.data_ptr())
+        return key if self.seen is None else key + (self.penalties.data_ptr(), self.seen.data_ptr())
 
-    def set_row(self, b: int, params: SamplingParams, stream: int = 0, draw_index: int = 0) -> None:
+    def _mark(self, flags: int, tokens=None, rows: Optional[Sequence[int]] = None, lead: Optional[torch.Tensor] = None) -> None:
+        """kivi_seen_mark on the current stream: `tokens` (n, T) for the table rows `rows` (None: all B, in order)."""
+        _lib.require_gpu(self.seen, "the history table")
+        dev = self.seen.device
+        n = self.B if rows is None else len(rows)
+        tokens = _token_rows(tokens, dev)
+        if tokens is not None and tokens.shape[0] != n:
+            raise ValueError(f"{tokens.shape[0]} rows of token ids for {n} rows of the sampler")
+        if tokens is None and not flags & SEEN_CLEAR:
+            return
+        rows_t = None if rows is None else torch.tensor(list(rows), dtype=torch.int32).to(dev)
+        T = 0 if tokens is None else tokens.shape[1]
+        _lib.check(_lib.load().kivi_seen_mark(_lib.ptr(self.seen), self.seen.stride(0), self.vocab_size,
+                                              None if rows_t is None else _lib.ptr(rows_t), n,
+                                              None if tokens is None else _lib.ptr(tokens), 0 if tokens is None else tokens.stride(0),
+                                              T, None if lead is None or tokens is None else _lib.ptr(lead), flags,
+                                              _lib.stream_ptr(self.seen)),
+                   "kivi_seen_mark")
+
+    def observe_prompt(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                       lead: Optional[torch.Tensor] = None) -> None:
+        """Marks `input_ids` (B, T) as the rows' prompts (bit 15 of the tokens' words; what the table holds stays).  The pads of a
+        left-padded batch are not marked: `attention_mask`, HF's 2D (B, T) mask, or `lead`, (B,) int32 on the device, the leading
+        pads of every row -- never read on the host.  A sampler without a table has nothing to mark."""
+        if self.seen is None:
+            return
+        if input_ids.dim() != 2 or input_ids.shape[0] != self.B:
+            raise ValueError(f"input_ids (B = {self.B}, T) expected, got {tuple(input_ids.shape)}")
+        if attention_mask is not None:
+            if lead is not None:
+                raise ValueError("pass either attention_mask= or lead=, not both")
+            if tuple(attention_mask.shape) != tuple(input_ids.shape):
+                raise ValueError(f"the 2D attention mask should be of size {tuple(input_ids.shape)}, but is "
+                                 f"{tuple(attention_mask.shape)}")
+            from .generation import leading_pads
+            lead = leading_pads(attention_mask.to(self.seen.device))
+        if lead is not None:
+            if lead.dtype != torch.int32 or tuple(lead.shape) != (self.B,) or lead.device != self.seen.device:
+                raise ValueError(f"lead has to be ({self.B},) int32 on {self.seen.device}")
+            lead = lead.contiguous()
+        self._mark(SEEN_PROMPT, input_ids, lead=lead)
+
+    def set_row(self, b: int, params: SamplingParams, stream: int = 0, draw_index: int = 0, prompt=None, generated=None) -> None:
         """A new request takes over row b: its record is rewritten and its draw index set to `draw_index` (default 0; a scheduler
         that has drawn the request's first tokens elsewhere passes how many), by asynchronous copies on the current stream (ordered
-        after the calls already enqueued there); no other row is touched and nothing has to be captured again."""
+        after the calls already enqueued there); no other row is touched and nothing has to be captured again.
+        With a history table the row's penalty record is rewritten too, and its row of the table is cleared and marked again:
+        `prompt`, the request's prompt tokens (1-D, no pads), `generated`, the tokens it has emitted so far (1-D; duplicates
+        count).  Without a table they are ignored, and penalised `params` are a ValueError."""
         if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < self.B:
             raise ValueError(f"row {b!r} outside [0, {self.B})")
         if not isinstance(params, SamplingParams):
@@ -205,38 +351,61 @@ class RowSampler:
         stream = _check_stream(stream)
         if isinstance(draw_index, bool) or not isinstance(draw_index, int) or not 0 <= draw_index < 2 ** 63:
             raise ValueError(f"draw_index has to be an integer in [0, 2^63), got {draw_index!r}")
+        if self.seen is None and params.penalised:
+            raise ValueError("params carry a repetition / presence / frequency penalty, but this RowSampler has no history table: "
+                             "pass vocab_size= when it is made")
         p = self._bind(params)
         rec = _record(p, stream)
         if self.records.is_cuda:
             rec = rec.pin_memory()
         self.records[b].copy_(rec, non_blocking=True)
         self.draw_index[b: b + 1].fill_(draw_index)
+        if self.seen is not None:
+            pen = _penalty_record(p)
+            self.penalties[b].copy_(pen.pin_memory() if self.penalties.is_cuda else pen, non_blocking=True)
+            self._mark(SEEN_CLEAR | SEEN_PROMPT, prompt, rows=[b])
+            self._mark(SEEN_OUTPUT, generated, rows=[b])
         self.params[b], self.streams[b] = p, stream
 
     def reset(self) -> None:
-        """All draw indices back to 0 (the records stay)."""
+        """All draw indices back to 0 (the records stay); the history table, if there is one, back to all zeros."""
         self.draw_index.zero_()
+        if self.seen is not None:
+            self.seen.zero_()
 
     def select(self, idx, streams: Optional[Sequence[int]] = None) -> "RowSampler":
-        """A new RowSampler (its own buffers) whose row i is this one's row idx[i], seeds and draw indices included: the sampler side
-        of a cache fork by index_select.  `streams`: new streams for the rows (default: those of the source rows)."""
+        """A new RowSampler (its own buffers) whose row i is this one's row idx[i], seeds, draw indices, penalty records and rows of
+        the history table included: the sampler side of a cache fork by index_select.  `streams`: new streams for the rows
+        (default: those of the source rows)."""
         idx = [int(i) for i in (idx.tolist() if torch.is_tensor(idx) else idx)]
         if not idx or not all(0 <= i < self.B for i in idx):
             raise ValueError(f"idx has to be a non-empty sequence of rows in [0, {self.B})")
         new = RowSampler([self.params[i] for i in idx], self.records.device,
-                         [self.streams[i] for i in idx] if streams is None else streams)
-        new.draw_index.copy_(self.draw_index.index_select(0, torch.tensor(idx, device=self.draw_index.device)))
+                         [self.streams[i] for i in idx] if streams is None else streams, vocab_size=self.vocab_size)
+        at = torch.tensor(idx, device=self.draw_index.device)
+        new.draw_index.copy_(self.draw_index.index_select(0, at))
+        if self.seen is not None:
+            new.seen.copy_(self.seen.index_select(0, at))
         return new
 
     def __call__(self, logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """As Sampler.__call__: one token per row into (B, 1) int64 (`out` when given), in ONE kivi_sample_rows launch."""
+        """As Sampler.__call__: one token per row into (B, 1) int64 (`out` when given), in ONE launch: kivi_sample_rows, or -- exactly
+        when the sampler has a history table -- kivi_sample_rows_pen, which also counts the tokens in the table."""
         logits, out = _call_args(logits, out, self)
         B, V = logits.shape
         lib = _lib.load()
-        _lib.check(lib.kivi_sample_rows(_lib.ptr(logits), 16 if logits.dtype == torch.float16 else 32, logits.stride(0), B, V,
-                                        _lib.ptr(self.records), _lib.ptr(self.draw_index), _lib.ptr(out),
-                                        out.stride(0) if out.dim() else 1, _lib.stream_ptr(logits)),
-                   "kivi_sample_rows")
+        bits, out_stride = 16 if logits.dtype == torch.float16 else 32, out.stride(0) if out.dim() else 1
+        if self.seen is None:
+            _lib.check(lib.kivi_sample_rows(_lib.ptr(logits), bits, logits.stride(0), B, V, _lib.ptr(self.records),
+                                            _lib.ptr(self.draw_index), _lib.ptr(out), out_stride, _lib.stream_ptr(logits)),
+                       "kivi_sample_rows")
+            return out
+        if V > self.vocab_size:
+            raise ValueError(f"logits of {V} tokens do not fit the history table of this RowSampler (vocab_size={self.vocab_size})")
+        _lib.check(lib.kivi_sample_rows_pen(_lib.ptr(logits), bits, logits.stride(0), B, V, _lib.ptr(self.records),
+                                            _lib.ptr(self.draw_index), _lib.ptr(self.penalties), _lib.ptr(self.seen),
+                                            self.seen.stride(0), _lib.ptr(out), out_stride, _lib.stream_ptr(logits)),
+                   "kivi_sample_rows_pen")
         return out
 
 
@@ -323,3 +492,29 @@ def reference_sample(logits: torch.Tensor, u, temperature: float = 1.0, top_k: i
     u = torch.as_tensor(np.asarray(u, dtype=np.float64)).reshape(-1, 1)
     tok = (cum <= u * cum[:, -1:]).sum(-1)
     return tok.clamp(max=logits.shape[-1] - 1)
+
+
+def reference_penalise(logits: torch.Tensor, prompt_mask: torch.Tensor, counts: torch.Tensor, theta, presence, frequency) -> torch.Tensor:
+    """The penalised logit of kivi_sample_rows_pen (include/kivi_hip.h) restated in torch fp32 on the CPU, one
+    separately rounded operation per step as in the kernel, so the result is the kernel's bit for bit: (B, V) fp32.
+    `logits` (B, V) fp16 / fp32; `prompt_mask` (B, V) bool, the token is in the row's prompt (bit 15 of the history word); `counts`
+    (B, V) integers, how often the row has emitted it (bits 0-14); `theta`, `presence`, `frequency`: a number or one per row.
+    seen_words() takes a history table apart into the two."""
+    x = logits.detach().cpu().float()
+    B = x.shape[0]
+
+    def col(v):
+        return torch.as_tensor(v, dtype=torch.float32).reshape(-1, 1).expand(B, 1)
+    theta, presence, frequency = col(theta), col(presence), col(frequency)
+    c = counts.detach().cpu().to(torch.int64)
+    seen = prompt_mask.detach().cpu().bool() | (c > 0)
+    x = torch.where(seen, torch.where(x > 0, x / theta, x * theta), x)
+    x = x - frequency * c.float()
+    return torch.where(c > 0, x - presence, x)
+
+
+def seen_words(seen: torch.Tensor, V: Optional[int] = None):
+    """A history table (B, stride) int16 -> (prompt_mask (B, V) bool, counts (B, V) int64) on the CPU."""
+    w = seen.detach().cpu().to(torch.int64) & 0xFFFF
+    w = w if V is None else w[:, :V]
+    return (w & SEEN_PROMPT_BIT) != 0, w & SEEN_COUNT_MAX

@@ -32,6 +32,10 @@ The policy is fixed (tests restate it):
   * Token i of a request is draw i of its own seed with Philox stream 0, whichever row and step it lands on:
     the first token is drawn by a RowSampler of the admitted rows alone, then the batch's RowSampler row is bound with
     set_row(..., draw_index=1).
+  * Penalties: when a request's SamplingParams carry one, both samplers get a history table.  The
+    first-token sampler of an admission has the admitted prompts marked; the batch's row is bound with
+    set_row(..., draw_index=1, prompt=<the prompt>, generated=[the first token]), which clears what the row's last request left.
+    The table is indexed by token id, not by cache position: a rebase and an admission offset do not touch it.
 """
 from __future__ import annotations
 
@@ -129,7 +133,10 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
 
     ids, mask = left_pad(prompts[:B], pad, device, length=L)
     logits, pasts = model.forward(ids, padding_mask=mask)
-    sampler = None if params is None else RowSampler(params[:B], device)
+    table = model.config.vocab_size if params is not None and any(p.penalised for p in params) else None
+    sampler = None if params is None else RowSampler(params[:B], device, vocab_size=table)
+    if table is not None:
+        sampler.observe_prompt(ids, attention_mask=mask)
 
     def pick(lg, rows_sampler):
         return lg.argmax(-1) if rows_sampler is None else rows_sampler(lg)
@@ -174,13 +181,16 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
             if off:
                 mask2d[rows, :off] = 0                                             # the zeroed lead is masked like any pad
             mask2d[rows, off:L] = new_mask
-            first = pick(lg, None if params is None else RowSampler([params[r] for r in reqs], device))     # draw 0 of each
+            first_sampler = None if params is None else RowSampler([params[r] for r in reqs], device, vocab_size=table)
+            if table is not None:
+                first_sampler.observe_prompt(new_ids, attention_mask=new_mask)
+            first = pick(lg, first_sampler)                                                                 # draw 0 of each
             tok[rows] = first
             for b, r, t in zip(rows, reqs, first.view(-1).tolist()):
                 owner[b] = r
                 lead[b] = L - prompts[r].numel()
                 if sampler is not None:
-                    sampler.set_row(b, params[r], draw_index=1)
+                    sampler.set_row(b, params[r], draw_index=1, prompt=prompts[r], generated=[t])
                 record(b, t)
         if all(r is None for r in owner):
             break
