@@ -40,7 +40,8 @@
  *                               greedy rows read from device memory), kivi_sample_rows_pen (the same with repetition /
  *                               presence / frequency penalties per row over a history table in device memory), kivi_seen_mark
  *                               (clears and marks rows of that table)
- *               scoring:       kivi_token_logprob (log-probability and rank of one given token per row of logits)
+ *               scoring:       kivi_token_logprob (log-probability and rank of one given token per row of logits),
+ *                              kivi_token_top_logprobs (the same plus the k most likely tokens with theirs)
  *               prompt pass:    kivi_prefill_attention (causal grouped-query attention over fp16 q / k / v with leading pads)
  *   BUILDING BLOCKS (what the layer steps are composed of; exported for tests, tools and callers that keep their own cache
  *               bookkeeping -- same contracts, but no stability promise beyond the ABI version):  kivi_gemv_k_paged,
@@ -801,6 +802,32 @@ int kivi_seen_mark(uint16_t* seen, int64_t seen_stride, int V, const int32_t* ro
 int kivi_token_logprob(const void* logits, int logits_bits, int64_t row_stride, int64_t N, int V, const int64_t* targets,
                        int64_t target_stride, int64_t ignore_index, float* out_logprob, float* out_lse, int32_t* out_rank,
                        kivi_stream_t stream);
+/*
+ * kivi_token_top_logprobs: the k most likely tokens of every row of (N, V) logits with their log-probabilities, and -- with
+ * targets -- everything kivi_token_logprob gives, in one launch (the `logprobs` / `top_logprobs=k` pair of a serving interface;
+ * DESIGN.md section 23).  Per row r, with x_j = float(logit[r, j]):
+ *   m, S and lse are those of kivi_token_logprob; with targets, out_logprob / out_lse / out_rank follow its rules (ignore_index,
+ *   targets out of range, -inf) and hold the same bits as it writes for the same row.
+ *   Order: token j comes before j' iff x_j > x_j', or x_j == x_j' and j < j' (the order out_rank counts in; -0 and +0 tie).
+ *   out_top_ids[r * top_stride + i] = the token of rank i, out_top_logprobs[r * top_stride + i] = x_id - lse, for i in [0, k);
+ *   an entry on a -inf logit is exactly -inf.  So out_top_ids[r, 0] is the row's argmax, and a scored target of rank < k has
+ *   out_top_ids[r, rank] == t and out_top_logprobs[r, rank] bit-identical to out_logprob[r].
+ *   targets     int64 or null; null: out_logprob and out_rank must be null (out_lse may be given).  A row whose target is ignored
+ *               or out of range still gets its list.
+ *   out_top_ids int64, out_top_logprobs fp32: k entries per row, rows top_stride elements apart; nothing else is written
+ * A row that is all -inf or holds NaN / +inf gets some value.  The same row gives the same bits strided or contiguous, at any
+ * element alignment, eager or replayed: integer LDS atomics only, every output element written by one lane.
+ * One 1024-thread workgroup per row, rows taken grid-stride; the row is read 3 (fp16) or 4 (fp32) times, 2 more when the tie class
+ * at the k-th place straddles the cut.
+ * KIVI_EINVAL (nothing enqueued) for every case of kivi_token_logprob (targets only when given), k outside
+ * [1, min(V, KIVI_TOP_LOGPROBS_MAX)], top_stride < k (N > 1), a null out_top_ids / out_top_logprobs, out_logprob or out_rank
+ * without targets, targets without out_logprob; KIVI_EALIGN as there, and for out_top_ids off 8 bytes or out_top_logprobs off 4.
+ */
+#define KIVI_TOP_LOGPROBS_MAX 32
+int kivi_token_top_logprobs(const void* logits, int logits_bits, int64_t row_stride, int64_t N, int V, int k,
+                            const int64_t* targets, int64_t target_stride, int64_t ignore_index, int64_t* out_top_ids,
+                            float* out_top_logprobs, int64_t top_stride, float* out_logprob, float* out_lse, int32_t* out_rank,
+                            kivi_stream_t stream);
 /*
  * kivi_prefill_attention: the attention of a prompt pass over fp16 q / k / v -- causal, grouped-query, with leading pads per batch
  * row (the reference's prompt pass, models/llama_kivi.py:401-452, without the repeat_kv copies and without a

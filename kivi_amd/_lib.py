@@ -202,6 +202,7 @@ SIGNATURES = {
     "kivi_sample_rows_pen": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "kivi_seen_mark": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp]),
     "kivi_token_logprob": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "kivi_token_top_logprobs": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "kivi_prefill_attention": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
                                       _i32, _i32, _i32, _i32, _i32, ctypes.c_float, _vp]),
     "kivi_mf_step_key": (_i64, [ctypes.POINTER(MfStep), _i32, _i32, _i32, _i32, _i32]),

@@ -217,15 +217,19 @@ class EagerStepper:
 
 
 def decode_loop(first_logits: torch.Tensor, step: Callable, pick: Callable, max_new_tokens: int,
-                eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, want_logprobs: bool = False):
+                eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, want_logprobs: bool = False,
+                top_k: int = 0):
     """Greedy decoding and sampling: every token is `pick` of the logits (B, 1, vocab) before it -- `first_logits`, then `step(tok)`.
     -> (tokens (B, generated) int64, their fp32 log-probabilities under the raw distribution or None).  A row that has produced
     `eos_token_id` emits `pad_token_id` from then on and scores target -100; the loop stops when every row has finished (the one
     synchronisation of a step, only with `eos_token_id`).  Otherwise the last token is still stepped and picked over: caches end
-    max_new_tokens tokens on, a sampler max_new_tokens + 1 draws on."""
+    max_new_tokens tokens on, a sampler max_new_tokens + 1 draws on.
+    `top_k` > 0 (with want_logprobs): the second result is (logprobs, top_ids (B, generated, top_k) int64, top_logprobs (B, generated,
+    top_k) fp32) -- the k most likely tokens of every step's raw distribution, from ONE kivi_token_top_logprobs launch per step in
+    place of the kivi_token_logprob launch; a finished row's pads get id -1 and value 0."""
     if want_logprobs:
-        from .scoring import token_logprobs
-    logits, out, lps = first_logits, [], []
+        from .scoring import token_logprobs, top_logprobs
+    logits, out, lps, tids, tlps = first_logits, [], [], [], []
     tok = pick(logits)
     B = tok.shape[0]
     live = None if eos_token_id is None else torch.ones((B, 1), dtype=torch.bool, device=tok.device)
@@ -233,7 +237,14 @@ def decode_loop(first_logits: torch.Tensor, step: Callable, pick: Callable, max_
         if live is not None:
             tok = torch.where(live, tok, torch.full_like(tok, pad_token_id))
         if want_logprobs:                              # a finished row scores nothing: its target is the ignore_index
-            lps.append(token_logprobs(logits, tok if live is None else torch.where(live, tok, torch.full_like(tok, -100))))
+            tgt = tok if live is None else torch.where(live, tok, torch.full_like(tok, -100))
+            if top_k:
+                res = top_logprobs(logits, top_k, tgt)
+                lps.append(res.target_logprob)
+                tids.append(res.ids if live is None else res.ids.masked_fill(~live.unsqueeze(-1), -1))
+                tlps.append(res.logprobs if live is None else res.logprobs.masked_fill(~live.unsqueeze(-1), 0.0))
+            else:
+                lps.append(token_logprobs(logits, tgt))
         if live is not None:
             live = live & (tok != eos_token_id)
         out.append(tok)
@@ -243,4 +254,7 @@ def decode_loop(first_logits: torch.Tensor, step: Callable, pick: Callable, max_
         tok = pick(logits)
     if want_logprobs:
         lps = torch.cat(lps, dim=1) if lps else logits.new_empty((B, 0), dtype=torch.float32)
+        if top_k:
+            lps = (lps, torch.cat(tids, dim=1) if tids else tok.new_empty((B, 0, top_k)),
+                   torch.cat(tlps, dim=1) if tlps else logits.new_empty((B, 0, top_k), dtype=torch.float32))
     return torch.cat(out, dim=1) if out else tok.new_empty((B, 0)), lps if want_logprobs else None

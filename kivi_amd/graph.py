@@ -32,6 +32,7 @@ from . import _lib
 from .attention import _rotate_half, kivi_attention_decode, rope_cos_sin
 from .cache_mf import SB, KiviLayerCacheMF
 from .generation import _MIN16, leading_pads
+from .scoring import score_into
 
 
 class MfStepDriver:
@@ -177,9 +178,14 @@ class DecodeGraphs:
     `sampler`: the last post() draws into `tok` with it instead of argmax.  The captured call holds what the sampler's key() names:
     a Sampler's parameters and state buffer, a RowSampler's row count and two buffers -- other parameter values in the same
     RowSampler (set_row, another request mix) replay the graphs that exist, another key builds them again.
+    `logprobs`: None, or k >= 0 -- the last post() also scores the token it has just written into `tok` under
+    the logits it has in hand, inside the captured step and after the draw, into the static buffers `lp` (B, 1) and, for k > 0,
+    `top_ids` / `top_lp` (B, 1, k): one kivi_token_logprob (k == 0) or kivi_token_top_logprobs launch.  The warm-up scores too, so
+    that a capture sees the launch; k is part of what matches() compares.
     `stats`: (eager steps, captures, replays) of the whole-step form, cumulative over the calls on one set of caches."""
 
-    def __init__(self, model, B: int, device, whole: bool = False, padded: bool = False, sampler=None, lead: bool = False):
+    def __init__(self, model, B: int, device, whole: bool = False, padded: bool = False, sampler=None, lead: bool = False,
+                 logprobs: Optional[int] = None):
         cfg, layers = model.config, model.model.layers
         nh, nkv = cfg.num_attention_heads, cfg.num_key_value_heads
         D, dt = layers[0].self_attn.head_dim, model.lm_head.weight.dtype
@@ -196,11 +202,18 @@ class DecodeGraphs:
         self.qkv = [(zeros(B, nh, 1, D), zeros(B, nkv, 1, D), zeros(B, nkv, 1, D)) for _ in layers]
         self.mask = self.pos = self.driver = self.graphed = self.stats = None
         self.lead = zeros(B, dtype=torch.int32) if padded and lead else None
+        self.logprobs = logprobs
+        self.lp = self.top_ids = self.top_lp = None
+        if logprobs is not None:
+            self.lp = zeros(B, 1, dtype=torch.float32)
+            if logprobs:
+                self.top_ids, self.top_lp = zeros(B, 1, logprobs, dtype=torch.long), zeros(B, 1, logprobs, dtype=torch.float32)
         if not whole:
             self._capture_layers()
 
-    def matches(self, B: int, whole: bool, padded: bool, sampler_key, lead: bool = False) -> bool:
-        return (self.B, self.whole, self.padded, self.sampler_key, self.lead is not None) == (B, whole, padded, sampler_key, bool(lead))
+    def matches(self, B: int, whole: bool, padded: bool, sampler_key, lead: bool = False, logprobs: Optional[int] = None) -> bool:
+        return ((self.B, self.whole, self.padded, self.sampler_key, self.lead is not None, self.logprobs) ==
+                (B, whole, padded, sampler_key, bool(lead), logprobs))
 
     def pre(self, i: int) -> None:
         layer = self.model.model.layers[i]
@@ -223,6 +236,8 @@ class DecodeGraphs:
                 self.tok.copy_(logits.argmax(-1))
             else:
                 self.sampler(logits, out=self.tok)
+            if self.logprobs is not None:
+                score_into(logits, self.tok, self.lp, self.top_ids, self.top_lp)
 
     def _capture_layers(self) -> None:
         device, n = self.tok.device, len(self.qkv)

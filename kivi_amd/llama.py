@@ -33,6 +33,8 @@ from .generation import (PADS_LEFT, DecodeLead, EagerStepper, _PaddedBatch, deco
 from .graph import DecodeGraphs
 from .prefill import left_padded
 from .sampling import RowSampler
+from .scoring import check_top_k, check_top_logprobs, token_logprobs
+from .scoring import top_logprobs as scoring_top_logprobs
 
 
 def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32, residual_length: int = 32,
@@ -272,15 +274,17 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     def generate_continuous(self, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
                             pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False, compact: Optional[int] = None,
-                            short_admissions: bool = False):
+                            short_admissions: bool = False, return_logprobs: bool = False, top_logprobs: int = 0):
         """Continuous batching over a queue of requests (kivi_amd/serving.py: generate_continuous): a batch of `batch_size` rows whose
         finished rows are taken over by the waiting prompts.  -> the generated tokens of every request, in request order.
         `compact`: None, or the fewest leading tokens worth dropping from the living caches between two steps (rebase_).
         `short_admissions`: admit at an offset, the prompt pass over about the prompt's length instead of the caches' (DESIGN.md
-        section 19; tokens may differ from the default)."""
+        section 19; tokens may differ from the default).
+        `return_logprobs` / `top_logprobs=k`: -> (tokens, logprobs[, top_ids, top_logprobs]), each a list with one tensor per request
+        (DESIGN.md section 23)."""
         from .serving import generate_continuous
         return generate_continuous(self, prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, graphed, compact,
-                                   short_admissions)
+                                   short_admissions, return_logprobs, top_logprobs)
 
     # ------------------------------------------------------------------ rebase (DESIGN.md section 17)
     @classmethod
@@ -321,32 +325,47 @@ class LlamaForCausalLM_KIVI(nn.Module):
             raise ValueError(f"chunk_size has to be a positive integer, got {chunk_size!r}")
         return [(0, first)] + [(a, min(a + step, T)) for a in range(first, T, step)]
 
-    def _head_logprobs(self, x, targets, return_rank):
+    def _head_logprobs(self, x, targets, return_rank, top_k: int = 0):
         """token_logprobs of `targets` (B, q) under lm_head(norm(x)), x (B, q, H): the head runs on slabs of at most _HEAD_SLAB rows
-        (one slab: the very call forward() makes), so logits never exist for more rows than that."""
-        from .scoring import token_logprobs
+        (one slab: the very call forward() makes), so logits never exist for more rows than that.  -> (logprobs, ranks or None,
+        top ids or None, top log-probabilities or None); `top_k` > 0: one kivi_token_top_logprobs launch per slab in place of the
+        kivi_token_logprob launch, with the lists (B, q, top_k) of every row."""
+        from .scoring import token_logprobs, top_logprobs
+
+        def head(hs, ts):
+            if top_k:
+                r = top_logprobs(self.lm_head(hs), top_k, ts, return_rank=return_rank)
+                return r.target_logprob, r.rank, r.ids, r.logprobs
+            r = token_logprobs(self.lm_head(hs), ts, return_rank=return_rank)
+            return (r + (None, None)) if return_rank else (r, None, None, None)
+
         h = self.model.norm(x)
         B, q = targets.shape
         if B * q <= self._HEAD_SLAB:
-            res = token_logprobs(self.lm_head(h), targets, return_rank=return_rank)
-            return res if return_rank else (res, None)
+            return head(h, targets)
         h, t = h.reshape(B * q, -1), targets.reshape(-1)
         lp = torch.empty(B * q, dtype=torch.float32, device=x.device)
         rk = torch.empty(B * q, dtype=torch.int32, device=x.device) if return_rank else None
+        ti = torch.empty((B * q, top_k), dtype=torch.int64, device=x.device) if top_k else None
+        tl = torch.empty((B * q, top_k), dtype=torch.float32, device=x.device) if top_k else None
         for s in range(0, B * q, self._HEAD_SLAB):
-            res = token_logprobs(self.lm_head(h[s: s + self._HEAD_SLAB]), t[s: s + self._HEAD_SLAB], return_rank=return_rank)
-            if return_rank:
-                lp[s: s + self._HEAD_SLAB], rk[s: s + self._HEAD_SLAB] = res
-            else:
-                lp[s: s + self._HEAD_SLAB] = res
-        return lp.view(B, q), rk.view(B, q) if return_rank else None
+            sl = slice(s, s + self._HEAD_SLAB)
+            res = head(h[sl], t[sl])
+            for dst, src in zip((lp, rk, ti, tl), res):
+                if dst is not None:
+                    dst[sl] = src
+        return (lp.view(B, q), rk.view(B, q) if return_rank else None, ti.view(B, q, top_k) if top_k else None,
+                tl.view(B, q, top_k) if top_k else None)
 
     @torch.no_grad()
     def score(self, input_ids: torch.LongTensor, attention_mask: Optional[torch.Tensor] = None,
               past_key_values: Optional[List] = None, first_chunk: Optional[int] = None, chunk_size: Optional[int] = None,
-              return_rank: bool = False):
+              return_rank: bool = False, top_logprobs: int = 0):
         """Teacher-forced log-probabilities of given tokens: (logprobs (B, T - 1) fp32, valid (B, T - 1) bool, past_key_values)
-        [, ranks (B, T - 1) int32 with `return_rank`: 0 where the token is the argmax of its distribution, -1 where not valid].
+        [, ranks (B, T - 1) int32 with `return_rank`: 0 where the token is the argmax of its distribution, -1 where not valid]
+        [, top_ids (B, T - 1, k) int64, top_logprobs (B, T - 1, k) fp32 with `top_logprobs=k` in [1, min(vocab_size, 32)]: the k most
+        likely tokens of every distribution, most likely first, ties by ascending id, from the same launch as the logprobs
+        (kivi_token_top_logprobs); id -1 and value 0 where not valid].
         Entry i is log p(input_ids[:, i + 1] | tokens <= i) under the model's raw distribution (kivi_amd/scoring.py,
         kivi_token_logprob); the caches are advanced over all T tokens, in place when `past_key_values` is given.
 
@@ -363,6 +382,9 @@ class LlamaForCausalLM_KIVI(nn.Module):
         vocab_size, and the mask is looked at, once: one synchronisation per call.  T < 2, a chunk size < 1 or first_chunk outside
         [1, T] raise ValueError before any device work."""
         plan = self._score_plan(input_ids, first_chunk, chunk_size)
+        k = top_logprobs
+        if k != 0:
+            check_top_k(k, self.config.vocab_size, "top_logprobs")
         B, T = input_ids.shape
         facts = list(torch.aminmax(input_ids))
         past_len = self._past_len(past_key_values)
@@ -383,6 +405,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
         targets[:, :-1] = torch.where(valid, input_ids[:, 1:], targets[:, :-1])
         logprobs = torch.empty((B, T), dtype=torch.float32, device=input_ids.device)
         ranks = torch.empty((B, T), dtype=torch.int32, device=input_ids.device) if return_rank else None
+        top_ids = torch.empty((B, T, k), dtype=torch.int64, device=input_ids.device) if k else None
+        top_lps = torch.empty((B, T, k), dtype=torch.float32, device=input_ids.device) if k else None
         pasts = past_key_values
         for a, b in plan:
             if padded:
@@ -390,12 +414,16 @@ class LlamaForCausalLM_KIVI(nn.Module):
                 x, pasts = self._hidden(input_ids[:, a:b], pasts, pb.mask, pb.position_ids, True)
             else:
                 x, pasts = self._hidden(input_ids[:, a:b], pasts, None, None, False)
-            lp, rk = self._head_logprobs(x, targets[:, a:b], return_rank)
+            lp, rk, ti, tl = self._head_logprobs(x, targets[:, a:b], return_rank, k)
             logprobs[:, a:b] = lp
             if return_rank:
                 ranks[:, a:b] = rk
-        res = (logprobs[:, :-1], valid, pasts)
-        return res + (ranks[:, :-1],) if return_rank else res
+            if k:
+                top_ids[:, a:b], top_lps[:, a:b] = ti, tl
+        res = (logprobs[:, :-1], valid, pasts) + ((ranks[:, :-1],) if return_rank else ())
+        if k:
+            res += (top_ids[:, :-1].masked_fill(~valid.unsqueeze(-1), -1), top_lps[:, :-1].masked_fill(~valid.unsqueeze(-1), 0.0))
+        return res
 
     @torch.no_grad()
     def perplexity(self, input_ids: torch.LongTensor, attention_mask: Optional[torch.Tensor] = None,
@@ -413,7 +441,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
                  early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False, do_sample: bool = False,
                  temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
                  seed: Optional[int] = None, return_logprobs: bool = False, sampling=None, repetition_penalty: float = 1.0,
-                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, top_logprobs: int = 0):
         """Greedy decoding (the recipe of the reference's mem_spd_test.py / example.py), or sampling with `do_sample=True`.
         With `past_key_values` (the caches of an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one
         pass (kivi_attention_extend) and decoding continues from there; the caches are advanced in place.  `attention_mask`:
@@ -446,7 +474,10 @@ class LlamaForCausalLM_KIVI(nn.Module):
         bit from the second new token on (the same head call on the same states); the first new token is scored on the prompt
         pass, whose head runs here on the last position alone and in score() on all T positions -- the same arithmetic, in
         whatever kernel the GEMM library picks for each row count.
-        With beams use `return_scores`.
+        With beams use `return_scores`.  `top_logprobs=k` (with `return_logprobs`; k in [1, min(vocab_size, 32)]): the result gains
+        top_ids (B, generated, k) int64 and top_logprobs (B, generated, k) fp32, the k most likely tokens of every step's raw
+        distribution, most likely first -- one kivi_token_top_logprobs launch per step in place of the kivi_token_logprob launch
+        (DESIGN.md section 23); the pads of a finished row get id -1 and value 0.
 
         `repetition_penalty` (HF, vLLM: over prompt and output tokens), `presence_penalty`, `frequency_penalty` (OpenAI, vLLM: over
         output tokens): applied inside the fused sampler (kivi_sample_rows_pen), greedy rows included.
@@ -460,6 +491,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
         if return_logprobs and num_beams > 1:
             raise ValueError("return_logprobs is for greedy decoding and sampling; beam search (num_beams > 1) returns its "
                              "sequences_scores with return_scores=True")
+        check_top_logprobs(top_logprobs, return_logprobs, num_beams, self.config.vocab_size)
         pick, fan = resolve_sampler(input_ids.device, input_ids.shape[0], num_return_sequences, num_beams, do_sample, temperature,
                                     top_k, top_p, min_p, seed, sampling, repetition_penalty, presence_penalty, frequency_penalty,
                                     self.config.vocab_size)
@@ -476,17 +508,23 @@ class LlamaForCausalLM_KIVI(nn.Module):
                                        pad_token_id, length_penalty, early_stopping, num_return_sequences)
             return (seqs, scores) if return_scores else seqs
         new, logprobs = decode_loop(stepper.logits, stepper.step, pick or (lambda lg: lg.argmax(-1)), max_new_tokens, eos_token_id,
-                                    pad_token_id, return_logprobs)
+                                    pad_token_id, return_logprobs, top_logprobs)
         seqs = torch.cat([stepper.input_ids, new], dim=1)
+        if top_logprobs:
+            return (seqs,) + logprobs
         return (seqs, logprobs) if return_logprobs else seqs
 
     # ------------------------------------------------------------------ hipGraph decode (kivi_amd/graph.py: DecodeGraphs)
-    def prepare_graphs(self, batch: int, device, whole: bool = False, padded: bool = False, sampler=None) -> None:
-        """Capture the decode graphs for this batch size now (otherwise on the first graphed step)."""
+    def prepare_graphs(self, batch: int, device, whole: bool = False, padded: bool = False, sampler=None,
+                       logprobs: Optional[int] = None) -> None:
+        """Capture the decode graphs for this batch size now (otherwise on the first graphed step).  `logprobs`: as decode_graphed."""
         key = None if sampler is None else sampler.key()
         lead = padded and bool(getattr(self.config, "kivi_decode_lead", False))
-        if self.graphs is None or not self.graphs.matches(batch, whole, padded, key, lead):
-            self.graphs = DecodeGraphs(self, batch, device, whole, padded, sampler, lead)
+        if logprobs is None:                                    # (the call as it was before the option existed)
+            if self.graphs is None or not self.graphs.matches(batch, whole, padded, key, lead):
+                self.graphs = DecodeGraphs(self, batch, device, whole, padded, sampler, lead)
+        elif self.graphs is None or not self.graphs.matches(batch, whole, padded, key, lead, logprobs):
+            self.graphs = DecodeGraphs(self, batch, device, whole, padded, sampler, lead, logprobs)
 
     def release_graphs(self) -> None:
         """Drop the static buffers and everything captured; the next graphed decode builds them again."""
@@ -494,7 +532,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     @torch.no_grad()
     def decode_graphed(self, tok: torch.LongTensor, past_key_values: List, position: int, steps: int,
-                       attention_mask: Optional[torch.Tensor] = None, sampler=None, sampling=None) -> torch.LongTensor:
+                       attention_mask: Optional[torch.Tensor] = None, sampler=None, sampling=None,
+                       logprobs: Optional[int] = None):
         """`steps` decode steps from token `tok` (B, 1) at position `position` with the dense part replayed from
         hipGraphs; the caches in `past_key_values` are advanced in place.  Returns the (B, steps) tokens fed to the model
         (tok first); the token following them is left in the graph's token buffer (`self.graphs.tok`).
@@ -502,7 +541,13 @@ class LlamaForCausalLM_KIVI(nn.Module):
         every row takes its own position from the mask (`position` is not used) and the pads are masked in every step.
         `sampler`: a kivi_amd.sampling.Sampler that draws each next token (one draw per step, inside the graph); None: greedy.
         `sampling`: a kivi_amd.sampling.RowSampler of B rows in its place (per-row parameters; not together with `sampler`).  The
-        graphs depend on its buffers only: set_row() between steps or calls replays what was captured."""
+        graphs depend on its buffers only: set_row() between steps or calls replays what was captured.
+        `logprobs`: None, or k in [0, min(vocab_size, 32)] -- every captured step also scores the token it produces under its raw
+        logits and the call returns (tokens, logprobs (B, steps) fp32[, top_ids (B, steps, k) int64,
+        top_logprobs (B, steps, k) fp32 for k > 0]): entry s is the score of the token step s PRODUCED (tokens[:, s + 1]; the last
+        one is the token left in `self.graphs.tok`).  The host clones the static buffers after every step, as it clones `tok`."""
+        if logprobs is not None and logprobs != 0:
+            check_top_k(logprobs, self.config.vocab_size, "logprobs")
         if sampling is not None:
             if sampler is not None:
                 raise ValueError("pass either sampler= or sampling=, not both")
@@ -515,29 +560,45 @@ class LlamaForCausalLM_KIVI(nn.Module):
         whole = all(isinstance(c, KiviLayerCacheMF) for c in caches)      # the whole step as one graph, else per-layer graphs
         B, kv0 = tok.shape[0], caches[0].kv_seq_len
         padded = attention_mask is not None and self._padded(attention_mask, B, kv0 + 1, kv0)
-        self.prepare_graphs(B, tok.device, whole, padded, sampler)
+        self.prepare_graphs(B, tok.device, whole, padded, sampler, logprobs)
         self.graphs.begin(tok, caches, attention_mask)
-        out = []
+        out, lps, tids, tlps = [], [], [], []
         for s in range(steps):
             out.append(self.graphs.tok.clone())
             self.graphs.step(position + s)
-        return torch.cat(out, dim=1)
+            if logprobs is not None:
+                lps.append(self.graphs.lp.clone())
+                if logprobs:
+                    tids.append(self.graphs.top_ids.clone())
+                    tlps.append(self.graphs.top_lp.clone())
+        toks = torch.cat(out, dim=1) if out else tok.new_empty((B, 0))
+        if logprobs is None:
+            return toks
+        res = (toks, torch.cat(lps, dim=1) if lps else self.graphs.lp.new_empty((B, 0)))
+        if logprobs:
+            res += (torch.cat(tids, dim=1) if tids else tok.new_empty((B, 0, logprobs)),
+                    torch.cat(tlps, dim=1) if tlps else self.graphs.lp.new_empty((B, 0, logprobs)))
+        return res
 
     @torch.no_grad()
     def generate_graphed(self, input_ids: torch.LongTensor, max_new_tokens: int,
                          attention_mask: Optional[torch.Tensor] = None, num_beams: int = 1, do_sample: bool = False,
                          temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
                          seed: Optional[int] = None, sampling=None, repetition_penalty: float = 1.0,
-                         presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> torch.LongTensor:
+                         presence_penalty: float = 0.0, frequency_penalty: float = 0.0, return_logprobs: bool = False,
+                         top_logprobs: int = 0):
         """generate() with the dense part of every decode step replayed from hipGraphs (kivi_amd.graph.DecodeGraphs).
         `attention_mask`: HF's 2D (B, T) mask of left-padded prompts (1 = real token).  Greedy, or sampling with `do_sample=True`
         and the parameters of generate() (the draw inside the graph; the same tokens as generate() with the same seed).  Beams
         are refused (a graphed beam step is open; use generate()).  `sampling=`: per-request parameters as in
         generate() (a SamplingParams, a list of B, or a RowSampler of B rows); the graphs are keyed by the RowSampler's buffers.
         `repetition_penalty` / `presence_penalty` / `frequency_penalty`: as in generate(); the penalised draw and the count of its
-        token are inside the captured step."""
+        token are inside the captured step.
+        `return_logprobs` / `top_logprobs=k`: the tuple generate() returns with the same arguments: the first
+        new token is scored eagerly on the prompt logits, every later one inside the captured step that produces it."""
         if sampling is None and num_beams != 1 and not do_sample:
             raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
+        check_top_logprobs(top_logprobs, return_logprobs, num_beams, self.config.vocab_size)
         pick, _ = resolve_sampler(input_ids.device, input_ids.shape[0], 1, num_beams, do_sample, temperature, top_k, top_p, min_p,
                                   seed, sampling, repetition_penalty, presence_penalty, frequency_penalty, self.config.vocab_size)
         logits, pasts = self.forward(input_ids, padding_mask=attention_mask)
@@ -545,9 +606,18 @@ class LlamaForCausalLM_KIVI(nn.Module):
         if attention_mask is not None:
             attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, :1])], dim=1)
         tok = logits.argmax(-1) if pick is None else pick(logits)
-        new = self.decode_graphed(tok, pasts, input_ids.shape[1], max_new_tokens, attention_mask, pick)
-        self.graphs.end()           # the caches of this request die with it: so does the graph captured over them
-        return torch.cat([input_ids, new], dim=1)
+        if not return_logprobs:
+            new = self.decode_graphed(tok, pasts, input_ids.shape[1], max_new_tokens, attention_mask, pick)
+            self.graphs.end()           # the caches of this request die with it: so does the graph captured over them
+            return torch.cat([input_ids, new], dim=1)
+        k = top_logprobs
+        first = scoring_top_logprobs(logits, k, tok) if k else None
+        first_lp = first.target_logprob if k else token_logprobs(logits, tok)
+        new, *scores = self.decode_graphed(tok, pasts, input_ids.shape[1], max_new_tokens, attention_mask, pick, logprobs=k)
+        self.graphs.end()
+        n = new.shape[1]                # step s scores the token after new[:, s]: the first token's score in front, the last one off
+        firsts = (first_lp,) + ((first.ids, first.logprobs) if k else ())
+        return (torch.cat([input_ids, new], dim=1),) + tuple(torch.cat([f, sc], dim=1)[:, :n] for f, sc in zip(firsts, scores))
 
     @classmethod
     def from_pretrained(cls, path: str, device="cuda", dtype=torch.float16, **kivi):

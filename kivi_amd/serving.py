@@ -36,6 +36,11 @@ The policy is fixed (tests restate it):
     first-token sampler of an admission has the admitted prompts marked; the batch's row is bound with
     set_row(..., draw_index=1, prompt=<the prompt>, generated=[the first token]), which clears what the row's last request left.
     The table is indexed by token id, not by cache position: a rebase and an admission offset do not touch it.
+  * `return_logprobs` / `top_logprobs=k`: every recorded token is scored under the raw logits it was picked
+    from -- the batch's step logits, or the admission's prompt logits for a first token -- by one kivi_token_logprob /
+    kivi_token_top_logprobs launch beside the pick (graphed: inside the captured step).  The values are read where the tokens are
+    read, so a step keeps its one synchronisation.  Eager, the rows with nothing to do score the ignore index; the captured step
+    scores every row and the host drops what no request owns.
 """
 from __future__ import annotations
 
@@ -45,6 +50,8 @@ import torch
 
 from .generation import decode_key_row, left_pad, padding_key_row
 from .sampling import RowSampler, SamplingParams
+from .scoring import check_top_logprobs, token_logprobs
+from .scoring import top_logprobs as score_top
 
 
 def _positive_int(x) -> bool:
@@ -111,7 +118,8 @@ def admission_offset(L: int, longest_prompt: int, R: int, quantum: int) -> int:
 @torch.no_grad()
 def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
                         pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False,
-                        compact: Optional[int] = None, short_admissions: bool = False) -> List[torch.Tensor]:
+                        compact: Optional[int] = None, short_admissions: bool = False, return_logprobs: bool = False,
+                        top_logprobs: int = 0):
     """`prompts`: a list of token id sequences, possibly more than `batch_size`; `max_new_tokens`: an int or one per request;
     `sampling`: None (greedy), one SamplingParams, or one per request.  -> the generated tokens of every request as 1-D int64
     tensors, in request order, ending with `eos_token_id` where it was produced.  The policy: the module docstring.
@@ -122,9 +130,14 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
     leading tokens no live row and no waiting prompt needs are dropped from the living caches (model.rebase_), if there are at least
     that many.
     `short_admissions`: False -- every admission is a prompt pass at the caches' length --, or True: at about the prompts' length,
-    admitted at an offset (the module docstring; tokens can differ from False)."""
+    admitted at an offset (the module docstring; tokens can differ from False).
+    `return_logprobs`: -> (tokens, logprobs), the second a list of fp32 tensors of the tokens' lengths: the log-probability of every
+    token under the raw distribution it was picked from; with `top_logprobs=k` also top_ids (n, k) int64 and top_logprobs (n, k)
+    fp32 per request, the k most likely tokens of each of those distributions."""
     prompts, limits, params = check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling,
                                               model.config.vocab_size, compact, short_admissions)
+    check_top_logprobs(top_logprobs, return_logprobs, 1, model.config.vocab_size)
+    k = top_logprobs
     pad = 0 if pad_token_id is None else pad_token_id
     use_lead = bool(getattr(model.config, "kivi_decode_lead", False))
     N, device = len(prompts), model.lm_head.weight.device
@@ -141,24 +154,42 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
     def pick(lg, rows_sampler):
         return lg.argmax(-1) if rows_sampler is None else rows_sampler(lg)
 
+    def score(lg, t, skip=()):
+        """The scores of the picked tokens t (n, 1) under lg (n, 1, V), as device tensors (read later, with the tokens)."""
+        if skip:
+            t = t.clone()
+            t[list(skip)] = -100
+        if not k:
+            return (token_logprobs(lg, t),)
+        res = score_top(lg, k, t)
+        return res.target_logprob, res.ids, res.logprobs
+
     tok = pick(logits, sampler)
+    scores = score(logits, tok) if return_logprobs else None
     mask2d = torch.ones((B, 2 * L + 64), dtype=torch.long, device=device)      # column t: 1 = cache token t of the row is real
     mask2d[:, :L] = mask
     owner: List[Optional[int]] = list(range(B))                                # the request of every row (None: nothing to do)
     lead = [L - prompts[r].numel() for r in range(B)]                          # leading pads of every row (host side, no device read)
     out: List[List[int]] = [[] for _ in range(N)]
+    out_scores: List[List[list]] = [[[] for _ in range(N)] for _ in range(3)]      # logprob, top ids, top logprobs of every token
     waiting = B
 
-    def record(b: int, t: int) -> None:
+    def record(b: int, t: int, sc=None, i: int = 0) -> None:
+        """Row b's request takes token t; sc: the host copies of score()'s tensors, i the row of them that belongs to b."""
         r = owner[b]
         out[r].append(t)
+        if sc is not None:
+            for dst, v in zip(out_scores, sc):
+                dst[r].append(v[i])
         if len(out[r]) >= limits[r] or (eos_token_id is not None and t == eos_token_id):
             owner[b] = None
 
     while True:
-        for b, t in enumerate(tok.view(-1).tolist()):                          # the one synchronisation of a step
+        toks = tok.view(-1).tolist()                                           # the one synchronisation of a step
+        sc = None if scores is None else [v.squeeze(1).tolist() for v in scores]
+        for b, t in enumerate(toks):
             if owner[b] is not None:
-                record(b, t)
+                record(b, t, sc, b)
         if compact is not None:
             drop = compact_drop([lead[b] for b in range(B) if owner[b] is not None], L,
                                 max((prompts[r].numel() for r in range(waiting, N)), default=0),
@@ -185,13 +216,16 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
             if table is not None:
                 first_sampler.observe_prompt(new_ids, attention_mask=new_mask)
             first = pick(lg, first_sampler)                                                                 # draw 0 of each
+            first_scores = score(lg, first) if return_logprobs else None
             tok[rows] = first
-            for b, r, t in zip(rows, reqs, first.view(-1).tolist()):
+            firsts = first.view(-1).tolist()
+            fsc = None if first_scores is None else [v.squeeze(1).tolist() for v in first_scores]
+            for i, (b, r, t) in enumerate(zip(rows, reqs, firsts)):
                 owner[b] = r
                 lead[b] = L - prompts[r].numel()
                 if sampler is not None:
                     sampler.set_row(b, params[r], draw_index=1, prompt=prompts[r], generated=[t])
-                record(b, t)
+                record(b, t, fsc, i)
         if all(r is None for r in owner):
             break
         idle = [b for b in range(B) if owner[b] is None]
@@ -200,7 +234,10 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
         if L + 1 > mask2d.shape[1]:
             mask2d = torch.cat([mask2d, torch.ones_like(mask2d)], dim=1)
         m = mask2d[:, : L + 1]                                                 # the fed token is real in every row
-        if graphed:
+        if graphed and return_logprobs:
+            _, *scores = model.decode_graphed(tok, pasts, L, 1, attention_mask=m, sampling=sampler, logprobs=k)
+            tok = model.graphs.tok.clone()
+        elif graphed:
             model.decode_graphed(tok, pasts, L, 1, attention_mask=m, sampling=sampler)
             tok = model.graphs.tok.clone()
         else:
@@ -208,7 +245,16 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
             # a rebase dropped is in it)
             logits, pasts = model._forward(tok, pasts, decode_key_row(m, use_lead), m.sum(-1, keepdim=True) - 1, True, True)
             tok = pick(logits, sampler)
+            if return_logprobs:
+                scores = score(logits, tok, idle)
         L += 1
     if graphed and model.graphs is not None:
         model.graphs.end()           # the caches of this call die with it: so does the graph captured over them
-    return [torch.tensor(o, dtype=torch.long, device=device) for o in out]
+    tokens = [torch.tensor(o, dtype=torch.long, device=device) for o in out]
+    if not return_logprobs:
+        return tokens
+    res = (tokens, [torch.tensor(o, dtype=torch.float32, device=device) for o in out_scores[0]])
+    if k:
+        res += ([torch.tensor(o, dtype=torch.long, device=device) for o in out_scores[1]],
+                [torch.tensor(o, dtype=torch.float32, device=device) for o in out_scores[2]])
+    return res
