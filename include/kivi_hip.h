@@ -40,6 +40,8 @@
  *                               greedy rows read from device memory), kivi_sample_rows_pen (the same with repetition /
  *                               presence / frequency penalties per row over a history table in device memory), kivi_seen_mark
  *                               (clears and marks rows of that table)
+ *               finishing:      kivi_stop_rows (stop token ids, stop sequences and a length limit per row, tracked in device
+ *                               memory: one launch per decode step, the live rows counted on the device)
  *               scoring:       kivi_token_logprob (log-probability and rank of one given token per row of logits),
  *                              kivi_token_top_logprobs (the same plus the k most likely tokens with theirs)
  *               prompt pass:    kivi_prefill_attention (causal grouped-query attention over fp16 q / k / v with leading pads)
@@ -782,6 +784,59 @@ int kivi_sample_rows_pen(const void* logits, int logits_bits, int64_t row_stride
 #define KIVI_SEEN_OUTPUT 4
 int kivi_seen_mark(uint16_t* seen, int64_t seen_stride, int V, const int32_t* rows, int n, const int64_t* tokens,
                    int64_t tok_row_stride, int T, const int32_t* lead, int flags, kivi_stream_t stream);
+/*
+ * kivi_stop_rows: the finish tracker of a decode batch, advanced by one token per row: stop token ids, stop
+ * sequences and a length limit per row, state in device memory, so that a captured step knows which rows are live without asking the
+ * host.  Entry i of the call (i < n) serves table row r = rows[i] (rows: n int32 (rows_bytes 4) or int64 (8) indices in DEVICE
+ * memory, distinct -- the caller's duty, as for kivi_seen_mark; a value outside [0, B) leaves the entry unused: its token is neither
+ * read nor written; null: r = i, and n <= B) with the token t = tokens[i * tok_stride]:
+ *   state[r].reason != 0 (the row has finished):  tokens[i * tok_stride] = pad, nothing else changes.
+ *   state[r].reason == 0 (live):  produced += 1, and t enters the ring at slot (produced - 1) % KIVI_STOP_MAX_LEN (a t outside
+ *     [0, 2^31) enters as -1 and matches nothing).  The row finishes when
+ *       (a) t == ids[j] for some j < n_ids                                            reason 1, index = the lowest such j
+ *       (b) for some j < n_seqs, m = seq_len[j] <= produced and seq[j][0..m) equals the last m produced tokens
+ *                                                                                     reason 2, index = the lowest such j
+ *       (c) produced == limit                                                         reason 3, index = -1
+ *     with the priority (a), (b), (c) when several hold.  t itself stays in the token buffer: the stop is part of the output.
+ * Only tokens produced since the row's state was last reset count (the host rebinds a row by rewriting its two records: produced 0,
+ * reason 0, index -1): a sequence never matches across two requests nor into a prompt.
+ * After the n entries *n_live = the number of rows of the WHOLE table (B rows) with reason == 0.  n == 0 is legal and only counts
+ * (tokens and rows may then be null).
+ * The values INSIDE the records cannot be checked by the host entry (kivi_amd/stopping.py validates them).  A record outside the
+ * contract degrades, it never indexes outside itself: n_ids is clamped into [0, KIVI_STOP_MAX_IDS], n_seqs into
+ * [0, KIVI_STOP_MAX_SEQS], a seq_len outside [1, KIVI_STOP_MAX_LEN] never matches, a limit < 1 never ends the row.
+ * One launch of ONE 256-thread workgroup (n_live counts the whole table): 16 lanes per entry -- lane l compares ids[l] and position
+ * l of every sequence, a wave ballot gathers the matches --, 16 entries per pass; a barrier, then the count.  No LDS atomics, no
+ * scratch, every global write an ordinary vector store, no host read, no allocation: capturable.
+ * KIVI_EINVAL (nothing enqueued) for B outside [1, KIVI_SAMPLE_MAX_B], n outside [0, KIVI_SAMPLE_MAX_B], n > B without rows,
+ * rows_bytes not 4 or 8 (with rows), tok_stride < 1 (n > 1), a null params / state / n_live, null tokens with n > 0; KIVI_EALIGN for
+ * tokens, params or state not 8-byte aligned, rows not aligned to rows_bytes, n_live not 4-byte aligned.
+ */
+#define KIVI_STOP_MAX_IDS 16
+#define KIVI_STOP_MAX_SEQS 8
+#define KIVI_STOP_MAX_LEN 16
+#define KIVI_STOP_LIVE 0
+#define KIVI_STOP_TOKEN 1
+#define KIVI_STOP_SEQUENCE 2
+#define KIVI_STOP_LENGTH 3
+typedef struct {                                         /* 624 bytes, 8-byte aligned; host-written, read only by the kernel */
+    int32_t n_ids;                                       /* [0, KIVI_STOP_MAX_IDS] */
+    int32_t n_seqs;                                      /* [0, KIVI_STOP_MAX_SEQS] */
+    int32_t limit;                                       /* >= 1: the tokens the row may produce (INT32_MAX: none in practice) */
+    int32_t reserved;                                    /* 0 */
+    int32_t ids[KIVI_STOP_MAX_IDS];                      /* stop token ids, >= 0 */
+    int32_t seq_len[KIVI_STOP_MAX_SEQS];                 /* [1, KIVI_STOP_MAX_LEN] */
+    int32_t seq[KIVI_STOP_MAX_SEQS][KIVI_STOP_MAX_LEN];  /* seq[j][0..seq_len[j]), oldest token first */
+} kivi_stop_params;
+typedef struct {                                         /* 80 bytes, 8-byte aligned */
+    int32_t produced;                                    /* tokens since the row was bound (at the finish: the output's length) */
+    int32_t reason;                                      /* KIVI_STOP_* */
+    int32_t index;                                       /* which id / sequence matched; -1: live or length */
+    int32_t reserved;                                    /* 0 */
+    int32_t ring[KIVI_STOP_MAX_LEN];                     /* produced token p (0-based) at slot p % KIVI_STOP_MAX_LEN */
+} kivi_stop_state;
+int kivi_stop_rows(int64_t* tokens, int64_t tok_stride, const kivi_stop_params* params, kivi_stop_state* state, const void* rows,
+                   int rows_bytes, int n, int B, int64_t pad, int32_t* n_live, kivi_stream_t stream);
 /*
  * kivi_token_logprob: the log-probability of one given token per row of (N, V) logits, log-softmax + gather in one launch without
  * an fp32 (N, V) intermediate (teacher-forced scoring, perplexity, the log-probabilities of generated tokens).

@@ -218,7 +218,7 @@ class EagerStepper:
 
 def decode_loop(first_logits: torch.Tensor, step: Callable, pick: Callable, max_new_tokens: int,
                 eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, want_logprobs: bool = False,
-                top_k: int = 0):
+                top_k: int = 0, stopper=None):
     """Greedy decoding and sampling: every token is `pick` of the logits (B, 1, vocab) before it -- `first_logits`, then `step(tok)`.
     -> (tokens (B, generated) int64, their fp32 log-probabilities under the raw distribution or None).  A row that has produced
     `eos_token_id` emits `pad_token_id` from then on and scores target -100; the loop stops when every row has finished (the one
@@ -226,7 +226,15 @@ def decode_loop(first_logits: torch.Tensor, step: Callable, pick: Callable, max_
     max_new_tokens tokens on, a sampler max_new_tokens + 1 draws on.
     `top_k` > 0 (with want_logprobs): the second result is (logprobs, top_ids (B, generated, top_k) int64, top_logprobs (B, generated,
     top_k) fp32) -- the k most likely tokens of every step's raw distribution, from ONE kivi_token_top_logprobs launch per step in
-    place of the kivi_token_logprob launch; a finished row's pads get id -1 and value 0."""
+    place of the kivi_token_logprob launch; a finished row's pads get id -1 and value 0.
+    `stopper` (not with `eos_token_id`): a finish tracker in place of the torch `live` arithmetic -- an object
+    with `reason` ((B,) integers, 0 = the row is live), `__call__(tok)` (takes the picked tokens (B, 1) in place: a live row's token
+    is counted and may finish the row, a finished row's is overwritten with the pad) and `n_live` (one integer, the live rows after
+    the call); kivi_amd.stopping.StopRows is one, on the device.  A row that was not live before its token scores target -100;
+    `int(stopper.n_live)` is the step's one synchronisation, and the loop leaves when it is 0 -- a length limit is a finish like any
+    other, so a call whose rows all end by their limits does NOT run the pass after the last token."""
+    if stopper is not None and eos_token_id is not None:
+        raise ValueError("decode_loop takes either eos_token_id or a stopper (whose stop ids include it), not both")
     if want_logprobs:
         from .scoring import token_logprobs, top_logprobs
     logits, out, lps, tids, tlps = first_logits, [], [], [], []
@@ -234,7 +242,10 @@ def decode_loop(first_logits: torch.Tensor, step: Callable, pick: Callable, max_
     B = tok.shape[0]
     live = None if eos_token_id is None else torch.ones((B, 1), dtype=torch.bool, device=tok.device)
     for _ in range(max_new_tokens):
-        if live is not None:
+        if stopper is not None:
+            live = (stopper.reason == 0).view(B, 1)    # before this token: a new tensor, the tracker's own state moves on below
+            stopper(tok)
+        elif live is not None:
             tok = torch.where(live, tok, torch.full_like(tok, pad_token_id))
         if want_logprobs:                              # a finished row scores nothing: its target is the ignore_index
             tgt = tok if live is None else torch.where(live, tok, torch.full_like(tok, -100))
@@ -245,10 +256,13 @@ def decode_loop(first_logits: torch.Tensor, step: Callable, pick: Callable, max_
                 tlps.append(res.logprobs if live is None else res.logprobs.masked_fill(~live.unsqueeze(-1), 0.0))
             else:
                 lps.append(token_logprobs(logits, tgt))
-        if live is not None:
+        if stopper is None and live is not None:
             live = live & (tok != eos_token_id)
         out.append(tok)
-        if live is not None and not bool(live.any()):
+        if stopper is not None:
+            if int(stopper.n_live) == 0:
+                break
+        elif live is not None and not bool(live.any()):
             break
         logits = step(tok)
         tok = pick(logits)

@@ -182,10 +182,14 @@ class DecodeGraphs:
     the logits it has in hand, inside the captured step and after the draw, into the static buffers `lp` (B, 1) and, for k > 0,
     `top_ids` / `top_lp` (B, 1, k): one kivi_token_logprob (k == 0) or kivi_token_top_logprobs launch.  The warm-up scores too, so
     that a capture sees the launch; k is part of what matches() compares.
+    `stopper`: a kivi_amd.stopping.StopRows of B rows -- the last post() runs it on `tok` after the draw and
+    before the scores: one kivi_stop_rows launch, which counts the token of every live row, writes the pad over a finished row's
+    and leaves the number of live rows in the stopper's `n_live`.  Not in the `draw=False` warm-up, which may not advance the
+    state any more than it may consume a draw.  matches() compares the stopper's key(): its buffers, not its records.
     `stats`: (eager steps, captures, replays) of the whole-step form, cumulative over the calls on one set of caches."""
 
     def __init__(self, model, B: int, device, whole: bool = False, padded: bool = False, sampler=None, lead: bool = False,
-                 logprobs: Optional[int] = None):
+                 logprobs: Optional[int] = None, stopper=None):
         cfg, layers = model.config, model.model.layers
         nh, nkv = cfg.num_attention_heads, cfg.num_key_value_heads
         D, dt = layers[0].self_attn.head_dim, model.lm_head.weight.dtype
@@ -195,6 +199,7 @@ class DecodeGraphs:
 
         self.model, self.B, self.whole, self.padded, self.sampler = model, B, whole, padded, sampler
         self.sampler_key = None if sampler is None else sampler.key()
+        self.stopper, self.stopper_key = stopper, None if stopper is None else stopper.key()
         self.tok = zeros(B, 1, dtype=torch.long)
         self.cos, self.sin = (zeros(B if padded else 1, 1, 1, D) for _ in range(2))
         self.x = [zeros(B, 1, cfg.hidden_size) for _ in range(len(layers) + 1)]
@@ -211,9 +216,10 @@ class DecodeGraphs:
         if not whole:
             self._capture_layers()
 
-    def matches(self, B: int, whole: bool, padded: bool, sampler_key, lead: bool = False, logprobs: Optional[int] = None) -> bool:
-        return ((self.B, self.whole, self.padded, self.sampler_key, self.lead is not None, self.logprobs) ==
-                (B, whole, padded, sampler_key, bool(lead), logprobs))
+    def matches(self, B: int, whole: bool, padded: bool, sampler_key, lead: bool = False, logprobs: Optional[int] = None,
+                stopper_key=None) -> bool:
+        return ((self.B, self.whole, self.padded, self.sampler_key, self.lead is not None, self.logprobs, self.stopper_key) ==
+                (B, whole, padded, sampler_key, bool(lead), logprobs, stopper_key))
 
     def pre(self, i: int) -> None:
         layer = self.model.model.layers[i]
@@ -236,6 +242,8 @@ class DecodeGraphs:
                 self.tok.copy_(logits.argmax(-1))
             else:
                 self.sampler(logits, out=self.tok)
+            if self.stopper is not None and draw:
+                self.stopper(self.tok)
             if self.logprobs is not None:
                 score_into(logits, self.tok, self.lp, self.top_ids, self.top_lp)
 

@@ -35,6 +35,7 @@ from .prefill import left_padded
 from .sampling import RowSampler
 from .scoring import check_top_k, check_top_logprobs, token_logprobs
 from .scoring import top_logprobs as scoring_top_logprobs
+from .stopping import SYNC_EVERY, StopRows, check_sync_every, resolve_stopping
 
 
 def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32, residual_length: int = 32,
@@ -115,6 +116,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
         self.model = _Body(config, attention_cls)
         self.lm_head = nn.Linear(config.hidden_size, config.vocab_size, bias=False)
         self.graphs = None          # kivi_amd.graph.DecodeGraphs of the last graphed decode (prepare_graphs / release_graphs)
+        self._stoppers = {}         # (rows, device, pad) -> the StopRows that generate_graphed binds its keyword stops to
         if getattr(config, "tie_word_embeddings", False):
             self.lm_head.weight = self.model.embed_tokens.weight
 
@@ -274,17 +276,20 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     def generate_continuous(self, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
                             pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False, compact: Optional[int] = None,
-                            short_admissions: bool = False, return_logprobs: bool = False, top_logprobs: int = 0):
+                            short_admissions: bool = False, return_logprobs: bool = False, top_logprobs: int = 0, stopping=None,
+                            return_finish: bool = False):
         """Continuous batching over a queue of requests (kivi_amd/serving.py: generate_continuous): a batch of `batch_size` rows whose
         finished rows are taken over by the waiting prompts.  -> the generated tokens of every request, in request order.
         `compact`: None, or the fewest leading tokens worth dropping from the living caches between two steps (rebase_).
         `short_admissions`: admit at an offset, the prompt pass over about the prompt's length instead of the caches' (DESIGN.md
         section 19; tokens may differ from the default).
         `return_logprobs` / `top_logprobs=k`: -> (tokens, logprobs[, top_ids, top_logprobs]), each a list with one tensor per request
-        (DESIGN.md section 23)."""
+        (DESIGN.md section 23).
+        `eos_token_id`: an int or a list; `stopping`: None, one StopParams, or one per request (stop ids, stop sequences, a limit of
+        its own); `return_finish`: the result gains a list of (reason, index) per request."""
         from .serving import generate_continuous
         return generate_continuous(self, prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, graphed, compact,
-                                   short_admissions, return_logprobs, top_logprobs)
+                                   short_admissions, return_logprobs, top_logprobs, stopping, return_finish)
 
     # ------------------------------------------------------------------ rebase (DESIGN.md section 17)
     @classmethod
@@ -441,7 +446,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
                  early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False, do_sample: bool = False,
                  temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
                  seed: Optional[int] = None, return_logprobs: bool = False, sampling=None, repetition_penalty: float = 1.0,
-                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, top_logprobs: int = 0):
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, top_logprobs: int = 0, stop_token_ids=None,
+                 stop_sequences=None, stopping=None):
         """Greedy decoding (the recipe of the reference's mem_spd_test.py / example.py), or sampling with `do_sample=True`.
         With `past_key_values` (the caches of an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one
         pass (kivi_attention_extend) and decoding continues from there; the caches are advanced in place.  `attention_mask`:
@@ -487,7 +493,17 @@ class LlamaForCausalLM_KIVI(nn.Module):
         are not marked; `num_return_sequences` forks carry the marks).  Not with beams.  `return_logprobs` stays under the RAW
         distribution.  Two facts: the loop's trailing pick (decode_loop) counts one token more than the call returns; and with
         `past_key_values` only this call's `input_ids` are known as prompt -- the earlier turns count only when the caller passes
-        the same RowSampler again (`sampling=`), whose table keeps them."""
+        the same RowSampler again (`sampling=`), whose table keeps them.
+
+        Finish conditions beyond one eos id (kivi_amd/stopping.py): `eos_token_id` may be a list, whose ids
+        join `stop_token_ids` (at most 16 in all); `stop_sequences`: at most 8 sequences of 1 to 16 token ids, matched against the
+        tokens the row has produced in this call, never into the prompt; or `stopping=`: a StopParams, a list of B of them (per-request
+        conditions and limits), or a ready StopRows of B * num_return_sequences rows, used as it is (its state is not reset) -- not
+        together with the other three.  With any of them the rows are tracked on the device (one kivi_stop_rows launch per token; the
+        step's one synchronisation is the read of its live count): a finished row emits `pad_token_id`, which is required, and the
+        stop itself stays in the output, as `eos_token_id` does; a call whose rows have all finished -- by their `max_new_tokens` too
+        -- ends without the pass after the last token.  Beam search keeps its own handling of ONE `eos_token_id` and refuses the
+        rest.  The plain call with one int `eos_token_id` is what it was."""
         if return_logprobs and num_beams > 1:
             raise ValueError("return_logprobs is for greedy decoding and sampling; beam search (num_beams > 1) returns its "
                              "sequences_scores with return_scores=True")
@@ -501,8 +517,18 @@ class LlamaForCausalLM_KIVI(nn.Module):
             raise ValueError(f"num_return_sequences ({num_return_sequences}) must lie in [1, num_beams ({num_beams})]")
         if return_scores and num_beams == 1:
             raise ValueError("return_scores: sequences_scores exist for beam search (num_beams > 1) only")
+        stops = resolve_stopping(input_ids.shape[0], max_new_tokens, eos_token_id, pad_token_id, stop_token_ids, stop_sequences,
+                                 stopping, num_beams, self.config.vocab_size, fan)
         stepper = EagerStepper(self, input_ids, past_key_values, attention_mask, max_new_tokens, max(num_beams, fan))
         observe_prompts(pick, input_ids, attention_mask, fan)
+        if stops is not None:
+            stopper = stops if isinstance(stops, StopRows) else StopRows(stops, input_ids.device, pad_token_id=pad_token_id)
+            new, logprobs = decode_loop(stepper.logits, stepper.step, pick or (lambda lg: lg.argmax(-1)), max_new_tokens,
+                                        want_logprobs=return_logprobs, top_k=top_logprobs, stopper=stopper)
+            seqs = torch.cat([stepper.input_ids, new], dim=1)
+            if top_logprobs:
+                return (seqs,) + logprobs
+            return (seqs, logprobs) if return_logprobs else seqs
         if num_beams > 1:
             seqs, scores = beam_search(stepper.step, input_ids, stepper.logits, num_beams, max_new_tokens, eos_token_id,
                                        pad_token_id, length_penalty, early_stopping, num_return_sequences)
@@ -516,11 +542,15 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     # ------------------------------------------------------------------ hipGraph decode (kivi_amd/graph.py: DecodeGraphs)
     def prepare_graphs(self, batch: int, device, whole: bool = False, padded: bool = False, sampler=None,
-                       logprobs: Optional[int] = None) -> None:
-        """Capture the decode graphs for this batch size now (otherwise on the first graphed step).  `logprobs`: as decode_graphed."""
+                       logprobs: Optional[int] = None, stopper=None) -> None:
+        """Capture the decode graphs for this batch size now (otherwise on the first graphed step).  `logprobs`, `stopper`: as
+        decode_graphed."""
         key = None if sampler is None else sampler.key()
         lead = padded and bool(getattr(self.config, "kivi_decode_lead", False))
-        if logprobs is None:                                    # (the call as it was before the option existed)
+        if stopper is not None:
+            if self.graphs is None or not self.graphs.matches(batch, whole, padded, key, lead, logprobs, stopper.key()):
+                self.graphs = DecodeGraphs(self, batch, device, whole, padded, sampler, lead, logprobs, stopper)
+        elif logprobs is None:                                  # (the call as it was before the option existed)
             if self.graphs is None or not self.graphs.matches(batch, whole, padded, key, lead):
                 self.graphs = DecodeGraphs(self, batch, device, whole, padded, sampler, lead)
         elif self.graphs is None or not self.graphs.matches(batch, whole, padded, key, lead, logprobs):
@@ -529,11 +559,12 @@ class LlamaForCausalLM_KIVI(nn.Module):
     def release_graphs(self) -> None:
         """Drop the static buffers and everything captured; the next graphed decode builds them again."""
         self.graphs = None
+        self._stoppers.clear()
 
     @torch.no_grad()
     def decode_graphed(self, tok: torch.LongTensor, past_key_values: List, position: int, steps: int,
                        attention_mask: Optional[torch.Tensor] = None, sampler=None, sampling=None,
-                       logprobs: Optional[int] = None):
+                       logprobs: Optional[int] = None, stopper=None, sync_every: int = SYNC_EVERY):
         """`steps` decode steps from token `tok` (B, 1) at position `position` with the dense part replayed from
         hipGraphs; the caches in `past_key_values` are advanced in place.  Returns the (B, steps) tokens fed to the model
         (tok first); the token following them is left in the graph's token buffer (`self.graphs.tok`).
@@ -545,9 +576,18 @@ class LlamaForCausalLM_KIVI(nn.Module):
         `logprobs`: None, or k in [0, min(vocab_size, 32)] -- every captured step also scores the token it produces under its raw
         logits and the call returns (tokens, logprobs (B, steps) fp32[, top_ids (B, steps, k) int64,
         top_logprobs (B, steps, k) fp32 for k > 0]): entry s is the score of the token step s PRODUCED (tokens[:, s + 1]; the last
-        one is the token left in `self.graphs.tok`).  The host clones the static buffers after every step, as it clones `tok`."""
+        one is the token left in `self.graphs.tok`).  The host clones the static buffers after every step, as it clones `tok`.
+        `stopper`: a kivi_amd.stopping.StopRows of B rows, which has already seen `tok`; every captured step
+        runs it on the token it produces (one kivi_stop_rows launch after the draw): finished rows feed its pad.  Before step s, for
+        every s that is a multiple of `sync_every`, the host reads the stopper's `n_live` -- the only synchronisation -- and leaves
+        when it is 0, so fewer than `steps` columns may come back and at most sync_every - 1 steps run after the last row has
+        finished.  `sync_every=None`: never read, all `steps` run."""
         if logprobs is not None and logprobs != 0:
             check_top_k(logprobs, self.config.vocab_size, "logprobs")
+        if stopper is not None:
+            if not isinstance(stopper, StopRows) or stopper.B != tok.shape[0]:
+                raise ValueError(f"decode_graphed(stopper=) takes a StopRows of {tok.shape[0]} rows")
+            check_sync_every(sync_every)
         if sampling is not None:
             if sampler is not None:
                 raise ValueError("pass either sampler= or sampling=, not both")
@@ -560,10 +600,12 @@ class LlamaForCausalLM_KIVI(nn.Module):
         whole = all(isinstance(c, KiviLayerCacheMF) for c in caches)      # the whole step as one graph, else per-layer graphs
         B, kv0 = tok.shape[0], caches[0].kv_seq_len
         padded = attention_mask is not None and self._padded(attention_mask, B, kv0 + 1, kv0)
-        self.prepare_graphs(B, tok.device, whole, padded, sampler, logprobs)
+        self.prepare_graphs(B, tok.device, whole, padded, sampler, logprobs, stopper)
         self.graphs.begin(tok, caches, attention_mask)
         out, lps, tids, tlps = [], [], [], []
         for s in range(steps):
+            if stopper is not None and sync_every is not None and s % sync_every == 0 and int(stopper.n_live) == 0:
+                break
             out.append(self.graphs.tok.clone())
             self.graphs.step(position + s)
             if logprobs is not None:
@@ -586,7 +628,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
                          temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
                          seed: Optional[int] = None, sampling=None, repetition_penalty: float = 1.0,
                          presence_penalty: float = 0.0, frequency_penalty: float = 0.0, return_logprobs: bool = False,
-                         top_logprobs: int = 0):
+                         top_logprobs: int = 0, eos_token_id=None, pad_token_id: Optional[int] = None, stop_token_ids=None,
+                         stop_sequences=None, stopping=None, sync_every: Optional[int] = SYNC_EVERY):
         """generate() with the dense part of every decode step replayed from hipGraphs (kivi_amd.graph.DecodeGraphs).
         `attention_mask`: HF's 2D (B, T) mask of left-padded prompts (1 = real token).  Greedy, or sampling with `do_sample=True`
         and the parameters of generate() (the draw inside the graph; the same tokens as generate() with the same seed).  Beams
@@ -595,17 +638,31 @@ class LlamaForCausalLM_KIVI(nn.Module):
         `repetition_penalty` / `presence_penalty` / `frequency_penalty`: as in generate(); the penalised draw and the count of its
         token are inside the captured step.
         `return_logprobs` / `top_logprobs=k`: the tuple generate() returns with the same arguments: the first
-        new token is scored eagerly on the prompt logits, every later one inside the captured step that produces it."""
+        new token is scored eagerly on the prompt logits, every later one inside the captured step that produces it.
+        `eos_token_id` (an int or a list) / `stop_token_ids` / `stop_sequences` / `stopping=` with `pad_token_id`: the finish
+        conditions of generate(), tracked by one kivi_stop_rows launch inside the captured step; the first
+        token goes through the tracker by one eager call.  The result is exactly what generate() returns for the same arguments,
+        the width included: the host reads the live count before every `sync_every`-th step (None: never) and leaves when it is 0;
+        the at most sync_every - 1 steps that ran past that point are cut off -- the caches of a graphed call die with it, nothing
+        else observes them -- and the scores of a finished row's pads are masked from the tracker's lengths (0, id -1).  With the
+        keyword forms the model keeps one tracker per (B, device, pad) and rebinds its rows, so another call with other stops
+        replays the graphs that exist; a StopRows passed as `stopping=` is used as it is and keys the graphs by its own buffers."""
         if sampling is None and num_beams != 1 and not do_sample:
             raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
         check_top_logprobs(top_logprobs, return_logprobs, num_beams, self.config.vocab_size)
         pick, _ = resolve_sampler(input_ids.device, input_ids.shape[0], 1, num_beams, do_sample, temperature, top_k, top_p, min_p,
                                   seed, sampling, repetition_penalty, presence_penalty, frequency_penalty, self.config.vocab_size)
+        check_sync_every(sync_every)
+        stops = resolve_stopping(input_ids.shape[0], max_new_tokens, eos_token_id, pad_token_id, stop_token_ids, stop_sequences,
+                                 stopping, 1, self.config.vocab_size, torch_eos=False)
         logits, pasts = self.forward(input_ids, padding_mask=attention_mask)
         observe_prompts(pick, input_ids, attention_mask)
         if attention_mask is not None:
             attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, :1])], dim=1)
         tok = logits.argmax(-1) if pick is None else pick(logits)
+        if stops is not None and max_new_tokens > 0:
+            return self._generate_graphed_stopping(input_ids, max_new_tokens, attention_mask, pick, logits, pasts, tok, stops,
+                                                   pad_token_id, sync_every, top_logprobs if return_logprobs else None)
         if not return_logprobs:
             new = self.decode_graphed(tok, pasts, input_ids.shape[1], max_new_tokens, attention_mask, pick)
             self.graphs.end()           # the caches of this request die with it: so does the graph captured over them
@@ -618,6 +675,45 @@ class LlamaForCausalLM_KIVI(nn.Module):
         n = new.shape[1]                # step s scores the token after new[:, s]: the first token's score in front, the last one off
         firsts = (first_lp,) + ((first.ids, first.logprobs) if k else ())
         return (torch.cat([input_ids, new], dim=1),) + tuple(torch.cat([f, sc], dim=1)[:, :n] for f, sc in zip(firsts, scores))
+
+    def _kept_stopper(self, params, device, pad_token_id: int) -> StopRows:
+        """The model's own finish tracker for (rows, device, pad), its rows bound to `params`: the buffers stay from call to call, so
+        the graphs captured over them are replayed whatever the stops of the next call are."""
+        kept = self._stoppers
+        key = (len(params), str(device), pad_token_id)
+        if key in kept:
+            kept[key].rebind(params)
+        else:
+            kept[key] = StopRows(params, device, pad_token_id=pad_token_id)
+        return kept[key]
+
+    def _generate_graphed_stopping(self, input_ids, max_new_tokens, attention_mask, pick, logits, pasts, tok, stops, pad_token_id,
+                                   sync_every, k):
+        """generate_graphed with finish conditions, from the first token `tok` picked of the prompt `logits` on; k: None, or the
+        top_logprobs of a return_logprobs call."""
+        stopper = stops if isinstance(stops, StopRows) else self._kept_stopper(stops, input_ids.device, pad_token_id)
+        before = stopper.length.clone()                 # (a caller's StopRows may have counted earlier tokens)
+        stopper(tok)                                    # the first token, eagerly
+        firsts = ()
+        if k is not None:
+            first = scoring_top_logprobs(logits, k, tok) if k else None
+            firsts = (first.target_logprob, first.ids, first.logprobs) if k else (token_logprobs(logits, tok),)
+        res = self.decode_graphed(tok, pasts, input_ids.shape[1], max_new_tokens - 1, attention_mask, pick, logprobs=k,
+                                  stopper=stopper, sync_every=sync_every)
+        fed, scores = (res, ()) if k is None else (res[0], res[1:])
+        new = torch.cat([fed, self.graphs.tok], dim=1)  # step s has produced new[:, s + 1] and its scores
+        self.graphs.end()
+        own, reason = torch.stack([stopper.length - before, stopper.reason]).tolist()
+        width = new.shape[1] if 0 in reason else max(max(own), 1)       # all finished: up to the longest row, as generate()
+        seqs = torch.cat([input_ids, new[:, :width]], dim=1)
+        if k is None:
+            return seqs
+        pads = torch.arange(width, device=new.device)[None, :] >= torch.tensor(own, device=new.device)[:, None]
+        lp, *tops = (torch.cat([f, sc], dim=1)[:, :width] for f, sc in zip(firsts, scores))
+        out = (seqs, lp.masked_fill(pads, 0.0))
+        if k:
+            out += (tops[0].masked_fill(pads.unsqueeze(-1), -1), tops[1].masked_fill(pads.unsqueeze(-1), 0.0))
+        return out
 
     @classmethod
     def from_pretrained(cls, path: str, device="cuda", dtype=torch.float16, **kivi):

@@ -11,6 +11,9 @@ The policy is fixed (tests restate it):
     ALL requests of the call -- every later admission (at a length >= L0) then fits.
   * Every iteration picks a token for every row from the logits the row has; a live row records it.  A row is finished when the
     token is `eos_token_id` or the request holds its `max_new_tokens` (the one synchronisation of a step: the tokens are read).
+    In full: the rule of kivi_amd/stopping.py -- stop ids (the eos ids first), stop sequences over the
+    request's own tokens, the limit -- run in Python on the tokens the scheduler has read anyway (StopState.push); there is no
+    device tracker here, a launch would buy nothing where the host already holds the tokens, and the captured step stays as it is.
   * Finished rows take the next waiting requests, lowest row first and in FIFO order, through ONE admit_ at the current length.
     An admitted request's first token is picked from its prompt logits and replaces the row's token before the step; should that
     token already finish the request, the row is free again and the admission repeats at the same length.
@@ -52,6 +55,7 @@ from .generation import decode_key_row, left_pad, padding_key_row
 from .sampling import RowSampler, SamplingParams
 from .scoring import check_top_logprobs, token_logprobs
 from .scoring import top_logprobs as score_top
+from .stopping import LIVE, StopParams, StopState, stop_ids
 
 
 def _positive_int(x) -> bool:
@@ -100,6 +104,30 @@ def check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token
     return seqs, limits, params
 
 
+def check_stopping(limits, eos_token_id, pad_token_id, stopping, vocab_size: Optional[int] = None):
+    """The finish conditions of every request as one StopParams each (kivi_amd/stopping.py): the ids of `eos_token_id` (None, an int
+    or a list) in front of the request's own stop ids, its stop sequences, and the smaller of its two limits.  `stopping`: None, one
+    StopParams, or one per request.  ValueError (no device work) for anything else."""
+    N = len(limits)
+    if stopping is None:
+        stopping = [StopParams()] * N
+    elif isinstance(stopping, StopParams):
+        stopping = [stopping] * N
+    elif not isinstance(stopping, (list, tuple)) or not all(isinstance(p, StopParams) for p in stopping):
+        raise ValueError("stopping has to be None, a StopParams, or a list with one StopParams per request")
+    if len(stopping) != N:
+        raise ValueError(f"{len(stopping)} StopParams for {N} requests")
+    if pad_token_id is None and any(p.stop_token_ids or p.stop_sequences for p in stopping):
+        raise ValueError("stop ids and stop sequences need a pad_token_id for the rows that have nothing to do")
+    eos = stop_ids(eos_token_id, None)
+    out = []
+    for p, limit in zip(stopping, limits):
+        p = StopParams(eos + p.stop_token_ids, p.stop_sequences, min(limit, p.limit))
+        p.check_vocab(vocab_size)
+        out.append(p)
+    return out
+
+
 def compact_drop(leads, L: int, longest_waiting: int, limit: int, quantum: int) -> int:
     """The tokens to drop from the front of every row of living caches at length L: `leads`, the leading pads of the LIVE rows (none:
     the whole length counts); `longest_waiting`, the longest prompt still in the queue (0: none), which has to fit into the new
@@ -119,7 +147,7 @@ def admission_offset(L: int, longest_prompt: int, R: int, quantum: int) -> int:
 def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
                         pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False,
                         compact: Optional[int] = None, short_admissions: bool = False, return_logprobs: bool = False,
-                        top_logprobs: int = 0):
+                        top_logprobs: int = 0, stopping=None, return_finish: bool = False):
     """`prompts`: a list of token id sequences, possibly more than `batch_size`; `max_new_tokens`: an int or one per request;
     `sampling`: None (greedy), one SamplingParams, or one per request.  -> the generated tokens of every request as 1-D int64
     tensors, in request order, ending with `eos_token_id` where it was produced.  The policy: the module docstring.
@@ -133,9 +161,14 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
     admitted at an offset (the module docstring; tokens can differ from False).
     `return_logprobs`: -> (tokens, logprobs), the second a list of fp32 tensors of the tokens' lengths: the log-probability of every
     token under the raw distribution it was picked from; with `top_logprobs=k` also top_ids (n, k) int64 and top_logprobs (n, k)
-    fp32 per request, the k most likely tokens of each of those distributions."""
+    fp32 per request, the k most likely tokens of each of those distributions.
+    `eos_token_id`: an int or a list of ids; `stopping`: None, one StopParams or one per request -- stop ids (after the eos ids),
+    stop sequences, and a max_new_tokens of its own (the smaller of the two limits holds).  A request's tokens end with the stop that
+    finished it.  `return_finish=True`: the result (a tuple in any case then) gains a last element, a list of (reason, index) per
+    request -- kivi_amd.stopping: TOKEN / SEQUENCE / LENGTH and the position of the id or sequence that matched (-1 for LENGTH)."""
     prompts, limits, params = check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling,
                                               model.config.vocab_size, compact, short_admissions)
+    finish = [StopState(p) for p in check_stopping(limits, eos_token_id, pad_token_id, stopping, model.config.vocab_size)]
     check_top_logprobs(top_logprobs, return_logprobs, 1, model.config.vocab_size)
     k = top_logprobs
     pad = 0 if pad_token_id is None else pad_token_id
@@ -181,7 +214,7 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
         if sc is not None:
             for dst, v in zip(out_scores, sc):
                 dst[r].append(v[i])
-        if len(out[r]) >= limits[r] or (eos_token_id is not None and t == eos_token_id):
+        if finish[r].push(t) != LIVE:              # the rule of kivi_amd/stopping.py on the request's own tokens
             owner[b] = None
 
     while True:
@@ -251,10 +284,11 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
     if graphed and model.graphs is not None:
         model.graphs.end()           # the caches of this call die with it: so does the graph captured over them
     tokens = [torch.tensor(o, dtype=torch.long, device=device) for o in out]
+    finished = ([(f.reason, f.index) for f in finish],) if return_finish else ()
     if not return_logprobs:
-        return tokens
+        return (tokens,) + finished if return_finish else tokens
     res = (tokens, [torch.tensor(o, dtype=torch.float32, device=device) for o in out_scores[0]])
     if k:
         res += ([torch.tensor(o, dtype=torch.long, device=device) for o in out_scores[1]],
                 [torch.tensor(o, dtype=torch.float32, device=device) for o in out_scores[2]])
-    return res
+    return res + finished
