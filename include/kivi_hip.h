@@ -39,7 +39,9 @@
  *                               the device), kivi_sample_rows (the same draw with per-row parameters, seeds, streams and
  *                               greedy rows read from device memory), kivi_sample_rows_pen (the same with repetition /
  *                               presence / frequency penalties per row over a history table in device memory), kivi_seen_mark
- *                               (clears and marks rows of that table)
+ *                               (clears and marks rows of that table), kivi_sample_rows_con (the same with a constraint per
+ *                               row: an allow mask, a list of biased or suppressed tokens, a minimum of new tokens),
+ *                               kivi_allow_mark (writes rows of the allow masks from id lists)
  *               finishing:      kivi_stop_rows (stop token ids, stop sequences and a length limit per row, tracked in device
  *                               memory: one launch per decode step, the live rows counted on the device)
  *               scoring:       kivi_token_logprob (log-probability and rank of one given token per row of logits),
@@ -784,6 +786,82 @@ int kivi_sample_rows_pen(const void* logits, int logits_bits, int64_t row_stride
 #define KIVI_SEEN_OUTPUT 4
 int kivi_seen_mark(uint16_t* seen, int64_t seen_stride, int V, const int32_t* rows, int n, const int64_t* tokens,
                    int64_t tok_row_stride, int T, const int32_t* lead, int flags, kivi_stream_t stream);
+/*
+ * kivi_sample_rows_con: kivi_sample_rows_pen with a constraint per row: an allow mask (what a grammar engine
+ * hands a sampler at every step), a short list of tokens with an additive bias (logit_bias; -inf: a banned token), and list entries
+ * that are suppressed until the row has made a number of draws (min_new_tokens over the eos / stop ids) -- applied where the logit
+ * is read, in the same single launch, for greedy rows too.
+ *   con    one kivi_sample_constraint per row in device memory, read only
+ *   allow  the allow masks: uint32 words, row b at allow + b * allow_stride (words); bit (e & 31) of word (e >> 5) is 1 when token e
+ *          is allowed; allow_stride >= ceil(V / 32) and a multiple of 4, the base 16-byte aligned; bits at or beyond V are ignored.
+ *          Read only for rows whose record sets KIVI_CONSTRAINT_MASK; may be null when none does (a null allow reads as "no mask").
+ *   list   the lists: kivi_sample_list_entry, row b at list + b * list_stride (entries), list_stride in [0, KIVI_SAMPLE_MAX_LIST], the
+ *          base 8-byte aligned; a row's first n_list entries count, in ascending token order, one per token (sorting and merging
+ *          is the host's duty).  May be null when every n_list is 0 (a null list reads as empty lists).
+ *   pen / seen / seen_stride as in kivi_sample_rows_pen, or BOTH null: no penalties, and the drawn token is not counted.
+ * THE RULE, before the temperature; every operation one correctly rounded IEEE fp32 operation, none contracted into an fma:
+ *   x = float(logit)
+ *   if token e has a list entry:
+ *       if (entry.word & KIVI_LIST_SUPPRESS) and draw_index[b] < suppress_until:  masked = true
+ *       else:                                                                     x = x + entry.value
+ *   x = the penalised logit of kivi_sample_rows_pen on x   (only with pen / seen and a record that is not neutral; unchanged)
+ *   if masked or (KIVI_CONSTRAINT_MASK and bit e of the row's allow mask is 0):   x = -inf
+ *   s = (temperature != 1 ? x / temperature : x) + 0.0f, and from there kivi_sample_rows unchanged.
+ * suppress_until is a draw index: the host stores (the row's draw index when the request is bound) + min_new_tokens, and the store
+ * of draw_index[b] + 1 that every launch makes advances the row towards it -- inside a captured graph too.
+ * A row whose every token is masked is an all -inf row: some token in [0, V), as in kivi_sample.
+ * IDENTITY A: with every constraint record neutral (no MASK, n_list 0), whatever allow and list hold, tokens, draw_index and the
+ * history table are bit for bit those of kivi_sample_rows_pen (with null pen / seen: the tokens those of kivi_sample_rows): a
+ * workgroup whose record is neutral takes that kernel's path and reads neither allow nor list.
+ * IDENTITY B: with any records the tokens are bit for bit those of kivi_sample_rows on the fp32 logits the rule gives.
+ * A record outside the contract degrades and never faults: n_list is clamped to [0, min(KIVI_SAMPLE_MAX_LIST, list_stride)]; a
+ * NaN value reads as 0; only bits 0-19 of an entry's word are read as its token, and an id >= V matches nothing; for an unsorted or
+ * duplicated list which entry applies to a token is unspecified; nothing is read outside the row's list, mask, logits or table.
+ * Refusals (nothing enqueued): everything kivi_sample_rows refuses; KIVI_EINVAL for a null con, exactly one of pen / seen null,
+ * seen_stride < V (with a table), allow_stride < ceil(V / 32) (with allow), list_stride outside [0, KIVI_SAMPLE_MAX_LIST];
+ * KIVI_EALIGN for pen not 4-byte, seen not 16-byte aligned, seen_stride not a multiple of 8, con not 8-byte, allow not 16-byte
+ * aligned, allow_stride not a multiple of 4 (with allow), list not 8-byte aligned.
+ */
+#define KIVI_SAMPLE_MAX_LIST 1024
+#define KIVI_CONSTRAINT_MASK 1u          /* kivi_sample_constraint.flags: the row's allow mask is in force */
+#define KIVI_LIST_TOKEN 0x000FFFFFu      /* kivi_sample_list_entry.word: bits 0-19, the token id */
+#define KIVI_LIST_SUPPRESS 0x80000000u   /* kivi_sample_list_entry.word: bit 31, masked while draw_index < suppress_until */
+typedef struct {             /* 32 bytes, 8-byte aligned */
+    uint32_t flags;          /* KIVI_CONSTRAINT_* */
+    int32_t n_list;          /* live entries of the row's list */
+    int64_t suppress_until;  /* SUPPRESS entries mask their token while draw_index < this */
+    uint32_t reserved[4];    /* 0 */
+} kivi_sample_constraint;
+typedef struct {             /* 8 bytes */
+    uint32_t word;           /* KIVI_LIST_TOKEN | KIVI_LIST_SUPPRESS; the other bits 0 */
+    float value;             /* any fp32 but NaN, +-inf included */
+} kivi_sample_list_entry;
+int kivi_sample_rows_con(const void* logits, int logits_bits, int64_t row_stride, int B, int V, const kivi_sample_row* rows,
+                         int64_t* draw_index, const kivi_sample_penalty* pen, uint16_t* seen, int64_t seen_stride,
+                         const kivi_sample_constraint* con, const uint32_t* allow, int64_t allow_stride,
+                         const kivi_sample_list_entry* list, int64_t list_stride, int64_t* out_tokens, int64_t out_stride,
+                         kivi_stream_t stream);
+/*
+ * kivi_allow_mark: writes rows of the allow masks of kivi_sample_rows_con from lists of token ids; kivi_seen_mark's sibling.  Entry i
+ * of the call (i < n) serves mask row rows[i] (int32[n] in device memory, distinct, each a row of the masks -- the caller's duty; a
+ * negative one is skipped; null: row i) with the ids tokens[i * tok_row_stride + t], t in [0, len[i]) (len: int32[n] in device
+ * memory, clamped to [0, T] on the device and never read on the host; null: T).
+ *   KIVI_ALLOW_NONE   the row's ceil(V / 32) words are zeroed first     KIVI_ALLOW_ALL    ... set to all ones first
+ *   KIVI_ALLOW_SET    the bit of every id is set (an atomic OR)         KIVI_ALLOW_UNSET  ... cleared (an atomic AND)
+ * At most one of NONE / ALL and one of SET / UNSET; a fence and a barrier put the marks after the fill.  Ids outside [0, V) are
+ * skipped.  The words of a row beyond ceil(V / 32) and the rows not named are never written.  T == 0 (or no SET / UNSET) with a fill
+ * only fills (tokens may then be null); without one it enqueues nothing.  One launch, n workgroups.
+ * KIVI_EINVAL (nothing enqueued) for flags 0, unknown, NONE | ALL or SET | UNSET, V outside [1, KIVI_SAMPLE_MAX_V], n outside
+ * [1, KIVI_SAMPLE_MAX_B], T < 0, a null allow, allow_stride < ceil(V / 32), null tokens with marks and T > 0, tok_row_stride < T
+ * (n > 1); KIVI_EALIGN for allow not 16-byte aligned, allow_stride not a multiple of 4, rows or len not 4-byte, tokens not 8-byte
+ * aligned.
+ */
+#define KIVI_ALLOW_NONE 1
+#define KIVI_ALLOW_ALL 2
+#define KIVI_ALLOW_SET 4
+#define KIVI_ALLOW_UNSET 8
+int kivi_allow_mark(uint32_t* allow, int64_t allow_stride, int V, const int32_t* rows, int n, const int64_t* tokens,
+                    int64_t tok_row_stride, int T, const int32_t* len, int flags, kivi_stream_t stream);
 /*
  * kivi_stop_rows: the finish tracker of a decode batch, advanced by one token per row: stop token ids, stop
  * sequences and a length limit per row, state in device memory, so that a captured step knows which rows are live without asking the

@@ -123,6 +123,7 @@ REORDER_MAX_SLABS = 32    # include/kivi_hip.h: KIVI_REORDER_MAX_SLABS
 REORDER_MAX_GROUP = 1024
 SAMPLE_MAX_B = 65535      # include/kivi_hip.h: KIVI_SAMPLE_MAX_B, KIVI_SAMPLE_MAX_V
 SAMPLE_MAX_V = 1 << 20
+SAMPLE_MAX_LIST = 1024      # include/kivi_hip.h: KIVI_SAMPLE_MAX_LIST
 STOP_MAX_IDS, STOP_MAX_SEQS, STOP_MAX_LEN = 16, 8, 16    # include/kivi_hip.h: KIVI_STOP_MAX_*
 
 
@@ -202,6 +203,8 @@ SIGNATURES = {
     "kivi_sample_rows": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "kivi_sample_rows_pen": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "kivi_seen_mark": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp]),
+    "kivi_sample_rows_con": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "kivi_allow_mark": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _i64, _i32, _vp, _i32, _vp]),
     "kivi_stop_rows": (_i32, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp]),
     "kivi_token_logprob": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "kivi_token_top_logprobs": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),

@@ -19,6 +19,8 @@
 // memory; a greedy flag per row; each block advances its own row's draw index.
 // kivi_sample_rows_pen: the row kernel with repetition / presence / frequency penalties read from a per-row
 // history table where the logit is read (PenRow), the token counted in the table where it is written; kivi_seen_mark fills the table.
+// kivi_sample_rows_con: the same again with a constraint record per row -- an allow mask, a sorted list of
+// biased or suppressed tokens -- applied by the reader ConRow; kivi_allow_mark writes mask rows from id lists.
 #include "kivi_common.h"
 
 namespace {
@@ -414,6 +416,174 @@ __global__ __launch_bounds__(kThreads) void sample_rows_pen_kernel(const T* __re
     }
 }
 
+// The reader of kivi_sample_rows_con: the rule of include/kivi_hip.h -- the list entry's bias or suppression,
+// PenRow's penalised logit, the allow mask -- then Row's score.  MASK: the row's allow mask is in force; its word is loaded from
+// global memory beside the logit, before anything depends on either (the 64 tokens of a wave's run are two words, which every later
+// pass finds in the cache).  LIST: the row has a list or a penalty.  `marks` is then the chunk bitmap of PenRow as 32-bit words with
+// the chunks of the listed tokens folded in, and `first[c]` the number of list entries below token 64 c: in a wave whose run of 64
+// tokens holds a listed or seen token -- a wave-uniform branch -- the run's entries are list[first[c] .. first[c + 1]), usually one or
+// two, compared one by one (three dependent LDS reads under the logit's load, where a binary search per token was ten).  The scan is
+// bounded by n_list whatever the list holds.  A token of such a chunk without an entry and with a zero history word only has a
+// zero subtracted, as in PenRow.
+// PenRow under another name for sample_rows_con_kernel: the row functions it instantiates are then its own, and those of
+// sample_rows_pen_kernel keep their single caller -- and with it the code the compiler gave them before.
+template <typename T>
+struct ConPenRow : PenRow<T> {};
+struct ListEnt {
+    uint32_t word, bits;                             // kivi_sample_list_entry with the value as its bits
+};
+template <typename T, bool MASK, bool LIST>
+struct ConRow {
+    const T* p;
+    float temp;
+    bool div;
+    PenRow<T> pen;                                   // (its p / temp / div / marks are not used)
+    bool penalised;
+    const uint32_t* marks;                           // LDS
+    const uint16_t* first;                           // LDS
+    const ListEnt* list;                             // LDS; NaN values already 0
+    bool suppress;                                   // draw_index < suppress_until
+    const uint32_t* allow;                           // the row's mask (MASK)
+    __device__ __forceinline__ float s(int e) const {
+#pragma clang fp contract(off)
+        float x = (float)p[e];
+        uint32_t aw = 0xFFFFFFFFu;
+        if (MASK) aw = allow[e >> 5];
+        bool masked = false;
+        if (LIST && ((marks[e >> 11] >> ((e >> 6) & 31)) & 1)) {
+            const int lo = first[e >> 6], hi = first[(e >> 6) + 1];
+            int at = -1;
+            for (int j = lo; j < hi; ++j)
+                if (at < 0 && (int)(list[j].word & KIVI_LIST_TOKEN) == e) at = j;
+            if (at >= 0) {
+                const ListEnt ent = list[at];
+                if ((ent.word & KIVI_LIST_SUPPRESS) && suppress) masked = true;
+                else x = x + __builtin_bit_cast(float, ent.bits);
+            }
+            if (penalised) x = pen.penalised(x, pen.seen[e]);
+        }
+        if (!((aw >> (e & 31)) & 1)) masked = true;
+        if (masked) x = -__builtin_inff();
+        return (div ? x / temp : x) + 0.0f;
+    }
+};
+
+// kivi_sample_rows_con: the block of sample_rows_pen_kernel with the row's constraint record.  A block whose
+// record is neutral -- no mask in force, an empty list; a block-uniform fact -- does exactly what sample_rows_pen_kernel does (or,
+// without a table, sample_rows_kernel) and reads neither masks nor lists.  A block with a mask alone runs the row body over
+// ConRow<MASK>.  Any other copies its list into LDS (n_list clamped, NaN values zeroed), builds the chunk bitmap -- zeroed, then
+// mark_chunks over the history if the row is penalised, then an LDS atomic OR per listed token below V -- and the table first[]
+// (one binary search of the list per chunk, once per launch), and runs the row body over ConRow<., LIST>.  Thread 0's count and the
+// draw_index store stay where they were.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void sample_rows_con_kernel(const T* __restrict__ logits, int64_t row_stride, int V, int BS,
+                                                                   const kivi_sample_row* __restrict__ rows, int64_t* draw_index,
+                                                                   const kivi_sample_penalty* __restrict__ pen, uint16_t* seen,
+                                                                   int64_t seen_stride, const kivi_sample_constraint* __restrict__ con,
+                                                                   const uint32_t* __restrict__ allow, int64_t allow_stride,
+                                                                   const kivi_sample_list_entry* __restrict__ lists, int64_t list_stride,
+                                                                   int64_t* __restrict__ out, int64_t out_stride) {
+    __shared__ Shared sh;
+    __shared__ uint32_t marks[KIVI_SAMPLE_MAX_V / 2048];
+    __shared__ ListEnt lst[KIVI_SAMPLE_MAX_LIST];
+    __shared__ uint16_t first[KIVI_SAMPLE_MAX_V / 64 + 2];
+    const int b = blockIdx.x;
+    const kivi_sample_row r = rows[b];
+    const int64_t n = draw_index[b];
+    float theta = 1.0f, pres = 0.0f, freq = 0.0f;
+    if (seen) {
+        theta = pen[b].repetition, pres = pen[b].presence, freq = pen[b].frequency;
+        if (!(theta > 0.0f) || !__builtin_isfinite(theta)) theta = 1.0f;
+        if (!__builtin_isfinite(pres)) pres = 0.0f;
+        if (!__builtin_isfinite(freq)) freq = 0.0f;
+    }
+    const bool penalised = !(theta == 1.0f && pres == 0.0f && freq == 0.0f);
+    const kivi_sample_constraint c = con[b];
+    const int n_list = lists ? min(max(c.n_list, 0), min(KIVI_SAMPLE_MAX_LIST, (int)list_stride)) : 0;
+    const uint32_t* mask = (allow && (c.flags & KIVI_CONSTRAINT_MASK)) ? allow + (int64_t)b * allow_stride : nullptr;
+    const T* row = logits + (int64_t)b * row_stride;
+    uint16_t* hist = seen ? seen + (int64_t)b * seen_stride : nullptr;
+    int64_t* dst = out + (int64_t)b * out_stride;
+    const PenRow<T> pr{row, 1.0f, false, hist, theta, pres, freq, reinterpret_cast<const uint8_t*>(marks)};
+    int tok;
+    if (!mask && n_list == 0) {
+        if (!penalised) {
+            tok = rows_token(sh, Row<T>{row, 1.0f, false}, r, V, BS, n, dst);
+        } else {
+            mark_chunks(reinterpret_cast<uint8_t*>(marks), hist, V);
+            __syncthreads();
+            tok = rows_token(sh, ConPenRow<T>{pr}, r, V, BS, n, dst);
+        }
+    } else if (n_list == 0 && !penalised) {
+        tok = rows_token(sh, ConRow<T, true, false>{row, 1.0f, false, pr, false, marks, first, lst, false, mask}, r, V, BS, n, dst);
+    } else {
+        const int tid = threadIdx.x;
+        if (tid < KIVI_SAMPLE_MAX_V / 2048) marks[tid] = 0;
+        const kivi_sample_list_entry* src = lists + (int64_t)b * list_stride;
+        for (int i = tid; i < n_list; i += kThreads) {
+            const kivi_sample_list_entry ent = src[i];
+            lst[i] = ListEnt{ent.word, __builtin_isnan(ent.value) ? 0u : __builtin_bit_cast(uint32_t, ent.value)};
+        }
+        __syncthreads();
+        if (penalised) {
+            mark_chunks(reinterpret_cast<uint8_t*>(marks), hist, V);
+            __syncthreads();
+        }
+        for (int i = tid; i < n_list; i += kThreads) {
+            const uint32_t id = lst[i].word & KIVI_LIST_TOKEN;
+            if (id < (uint32_t)V) atomicOr(&marks[id >> 11], 1u << ((id >> 6) & 31));
+        }
+        for (int ch = tid; ch <= (V + 63) / 64; ch += kThreads) {           // first[ch]: the entries below token 64 ch (in [0, n_list])
+            int lo = 0, hi = n_list;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if ((int)(lst[mid].word & KIVI_LIST_TOKEN) < ch * 64) lo = mid + 1;
+                else hi = mid;
+            }
+            first[ch] = (uint16_t)lo;
+        }
+        __syncthreads();
+        const bool sup = n < c.suppress_until;
+        if (mask)
+            tok = rows_token(sh, ConRow<T, true, true>{row, 1.0f, false, pr, penalised, marks, first, lst, sup, mask}, r, V, BS, n, dst);
+        else
+            tok = rows_token(sh, ConRow<T, false, true>{row, 1.0f, false, pr, penalised, marks, first, lst, sup, mask}, r, V, BS, n, dst);
+    }
+    if (threadIdx.x == 0) {
+        draw_index[b] = n + 1;
+        if (hist) {
+            const uint16_t w = hist[tok];                               // tok in [0, V), V <= seen_stride
+            if ((w & 0x7FFFu) != 0x7FFFu) hist[tok] = (uint16_t)(w + 1);
+        }
+    }
+}
+
+// kivi_allow_mark: block i serves mask row rows[i] (null: i).  NONE / ALL store the row's ceil(V / 32) words; a fence and a barrier
+// put the marks of the same block after them.  A mark is an atomic OR (SET) or AND (UNSET) on the token's 32-bit word.
+__global__ __launch_bounds__(256) void allow_mark_kernel(uint32_t* allow, int64_t allow_stride, int V, const int32_t* __restrict__ rows,
+                                                         const int64_t* __restrict__ tokens, int64_t tok_row_stride, int T,
+                                                         const int32_t* __restrict__ len, int flags) {
+    const int i = blockIdx.x;
+    const int64_t d = rows ? (int64_t)rows[i] : (int64_t)i;
+    if (d < 0) return;                                                  // (block-uniform)
+    uint32_t* row = allow + d * allow_stride;
+    if (flags & (KIVI_ALLOW_NONE | KIVI_ALLOW_ALL)) {
+        const uint32_t fill = (flags & KIVI_ALLOW_ALL) ? 0xFFFFFFFFu : 0u;
+        for (int j = threadIdx.x; j < (V + 31) / 32; j += blockDim.x) row[j] = fill;
+        __threadfence();
+        __syncthreads();
+    }
+    if (!(flags & (KIVI_ALLOW_SET | KIVI_ALLOW_UNSET))) return;
+    const int t1 = len ? min(max(len[i], 0), T) : T;
+    const int64_t* tk = tokens + (int64_t)i * tok_row_stride;
+    for (int t = threadIdx.x; t < t1; t += blockDim.x) {
+        const int64_t id = tk[t];
+        if (id < 0 || id >= V) continue;
+        if (flags & KIVI_ALLOW_SET) atomicOr(row + (id >> 5), 1u << (id & 31));
+        else atomicAnd(row + (id >> 5), ~(1u << (id & 31)));
+    }
+}
+
 // kivi_seen_mark: block i serves destination row rows[i] (null: i).  CLEAR zeroes the row's seen_stride words with 16-byte stores;
 // a fence and a barrier put the marks of the same block after them.  Two tokens share a 32-bit word of the table, so a mark is an
 // atomic on that word: an OR of bit 15 (PROMPT), or a compare-and-swap that adds 1 to the 15-bit count unless it is 32767 (OUTPUT;
@@ -568,4 +738,74 @@ extern "C" int kivi_seen_mark(uint16_t* seen, int64_t seen_stride, int V, const 
     KIVI_LAUNCH(seen_mark_kernel, dim3(n), dim3(256), (hipStream_t)stream, seen, seen_stride, V, rows, tokens, tok_row_stride,
                 mark ? T : 0, lead, mark ? flags : KIVI_SEEN_CLEAR);
     return kivi_launch_status("kivi_seen_mark");
+}
+
+extern "C" int kivi_sample_rows_con(const void* logits, int logits_bits, int64_t row_stride, int B, int V, const kivi_sample_row* rows,
+                                    int64_t* draw_index, const kivi_sample_penalty* pen, uint16_t* seen, int64_t seen_stride,
+                                    const kivi_sample_constraint* con, const uint32_t* allow, int64_t allow_stride,
+                                    const kivi_sample_list_entry* list, int64_t list_stride, int64_t* out_tokens, int64_t out_stride,
+                                    kivi_stream_t stream) {
+    KIVI_REQUIRE(logits_bits == 16 || logits_bits == 32, KIVI_EINVAL, "kivi_sample_rows_con: logits_bits=%d (16: fp16, 32: fp32)",
+                 logits_bits);
+    KIVI_REQUIRE(B >= 1 && B <= KIVI_SAMPLE_MAX_B, KIVI_EINVAL, "kivi_sample_rows_con: B=%d (1 <= B <= %d)", B, KIVI_SAMPLE_MAX_B);
+    KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "kivi_sample_rows_con: V=%d (1 <= V <= %d)", V, KIVI_SAMPLE_MAX_V);
+    KIVI_REQUIRE(row_stride >= V || B == 1, KIVI_EINVAL, "kivi_sample_rows_con: row_stride=%lld below V=%d", (long long)row_stride, V);
+    KIVI_REQUIRE(out_stride >= 1 || B == 1, KIVI_EINVAL, "kivi_sample_rows_con: out_stride=%lld", (long long)out_stride);
+    KIVI_REQUIRE(logits && rows && draw_index && out_tokens && con, KIVI_EINVAL, "kivi_sample_rows_con: null pointer");
+    KIVI_REQUIRE(!pen == !seen, KIVI_EINVAL, "kivi_sample_rows_con: pen and seen have to be both given or both null");
+    KIVI_REQUIRE(!seen || seen_stride >= V, KIVI_EINVAL, "kivi_sample_rows_con: seen_stride=%lld below V=%d", (long long)seen_stride, V);
+    KIVI_REQUIRE(!allow || allow_stride >= (V + 31) / 32, KIVI_EINVAL, "kivi_sample_rows_con: allow_stride=%lld below ceil(V / 32)=%d",
+                 (long long)allow_stride, (V + 31) / 32);
+    KIVI_REQUIRE(list_stride >= 0 && list_stride <= KIVI_SAMPLE_MAX_LIST, KIVI_EINVAL,
+                 "kivi_sample_rows_con: list_stride=%lld (0 <= list_stride <= %d)", (long long)list_stride, KIVI_SAMPLE_MAX_LIST);
+    const int esz = logits_bits / 8;
+    KIVI_REQUIRE((uintptr_t)logits % esz == 0 && (uintptr_t)rows % 8 == 0 && (uintptr_t)draw_index % 8 == 0 &&
+                     (uintptr_t)out_tokens % 8 == 0,
+                 KIVI_EALIGN, "kivi_sample_rows_con: misaligned logits (%d-byte elements), rows, draw_index or out_tokens (8 bytes)",
+                 esz);
+    KIVI_REQUIRE((uintptr_t)pen % 4 == 0 && (uintptr_t)seen % 16 == 0 && (!seen || seen_stride % 8 == 0), KIVI_EALIGN,
+                 "kivi_sample_rows_con: misaligned pen (4 bytes) or seen (16 bytes), or seen_stride=%lld not a multiple of 8",
+                 (long long)seen_stride);
+    KIVI_REQUIRE((uintptr_t)con % 8 == 0 && (uintptr_t)allow % 16 == 0 && (!allow || allow_stride % 4 == 0) && (uintptr_t)list % 8 == 0,
+                 KIVI_EALIGN,
+                 "kivi_sample_rows_con: misaligned con or list (8 bytes) or allow (16 bytes), or allow_stride=%lld not a multiple of 4",
+                 (long long)allow_stride);
+    int BS;                                          // the bucket of kivi_sample: a power of two, at most 1024 buckets per row
+    for (BS = KIVI_WAVE; (int64_t)BS * 1024 < V;) BS <<= 1;
+    const hipStream_t s = (hipStream_t)stream;
+    if (logits_bits == 16)
+        KIVI_LAUNCH(sample_rows_con_kernel<f16>, dim3(B), dim3(kThreads), s, (const f16*)logits, row_stride, V, BS, rows, draw_index,
+                    pen, seen, seen_stride, con, allow, allow_stride, list, list_stride, out_tokens, out_stride);
+    else
+        KIVI_LAUNCH(sample_rows_con_kernel<float>, dim3(B), dim3(kThreads), s, (const float*)logits, row_stride, V, BS, rows,
+                    draw_index, pen, seen, seen_stride, con, allow, allow_stride, list, list_stride, out_tokens, out_stride);
+    return kivi_launch_status("kivi_sample_rows_con");
+}
+
+extern "C" int kivi_allow_mark(uint32_t* allow, int64_t allow_stride, int V, const int32_t* rows, int n, const int64_t* tokens,
+                               int64_t tok_row_stride, int T, const int32_t* len, int flags, kivi_stream_t stream) {
+    const int fill = flags & (KIVI_ALLOW_NONE | KIVI_ALLOW_ALL), marks = flags & (KIVI_ALLOW_SET | KIVI_ALLOW_UNSET);
+    KIVI_REQUIRE(flags != 0 && !(flags & ~(KIVI_ALLOW_NONE | KIVI_ALLOW_ALL | KIVI_ALLOW_SET | KIVI_ALLOW_UNSET)) &&
+                     fill != (KIVI_ALLOW_NONE | KIVI_ALLOW_ALL) && marks != (KIVI_ALLOW_SET | KIVI_ALLOW_UNSET),
+                 KIVI_EINVAL,
+                 "kivi_allow_mark: flags=%d (at most one of KIVI_ALLOW_NONE / KIVI_ALLOW_ALL and one of KIVI_ALLOW_SET / KIVI_ALLOW_UNSET)",
+                 flags);
+    KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "kivi_allow_mark: V=%d (1 <= V <= %d)", V, KIVI_SAMPLE_MAX_V);
+    KIVI_REQUIRE(n >= 1 && n <= KIVI_SAMPLE_MAX_B, KIVI_EINVAL, "kivi_allow_mark: n=%d (1 <= n <= %d)", n, KIVI_SAMPLE_MAX_B);
+    KIVI_REQUIRE(T >= 0, KIVI_EINVAL, "kivi_allow_mark: T=%d", T);
+    KIVI_REQUIRE(allow, KIVI_EINVAL, "kivi_allow_mark: null allow");
+    KIVI_REQUIRE(allow_stride >= (V + 31) / 32, KIVI_EINVAL, "kivi_allow_mark: allow_stride=%lld below ceil(V / 32)=%d",
+                 (long long)allow_stride, (V + 31) / 32);
+    KIVI_REQUIRE(tokens || T == 0 || !marks, KIVI_EINVAL, "kivi_allow_mark: null tokens with T=%d", T);
+    KIVI_REQUIRE(tok_row_stride >= T || n == 1, KIVI_EINVAL, "kivi_allow_mark: tok_row_stride=%lld below T=%d",
+                 (long long)tok_row_stride, T);
+    KIVI_REQUIRE((uintptr_t)allow % 16 == 0 && allow_stride % 4 == 0, KIVI_EALIGN,
+                 "kivi_allow_mark: misaligned allow (16 bytes), or allow_stride=%lld not a multiple of 4", (long long)allow_stride);
+    KIVI_REQUIRE((uintptr_t)rows % 4 == 0 && (uintptr_t)len % 4 == 0 && (uintptr_t)tokens % 8 == 0, KIVI_EALIGN,
+                 "kivi_allow_mark: misaligned rows or len (4 bytes) or tokens (8 bytes)");
+    const bool mark = marks && T > 0;
+    if (!mark && !fill) return 0;                                       // nothing to do, nothing enqueued
+    KIVI_LAUNCH(allow_mark_kernel, dim3(n), dim3(256), (hipStream_t)stream, allow, allow_stride, V, rows, tokens, tok_row_stride,
+                mark ? T : 0, len, mark ? flags : fill);
+    return kivi_launch_status("kivi_allow_mark");
 }

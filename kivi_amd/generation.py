@@ -114,7 +114,7 @@ class _PaddedBatch:
 
 def resolve_sampler(device, B: int, num_return_sequences: int, num_beams: int, do_sample: bool, temperature, top_k, top_p, min_p,
                     seed, sampling, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                    vocab_size: Optional[int] = None):
+                    vocab_size: Optional[int] = None, logit_bias=None, allowed_token_ids=None, min_new_tokens: int = 0):
     """The sampler of a generate / generate_graphed call -> (pick, fan): `pick(logits) -> tokens` is a Sampler (`do_sample=True`), a
     RowSampler (`sampling=`: B requests with `fan` = num_return_sequences samples each, row b * fan + j is request b with Philox
     stream j) or None (greedy); without `sampling=` fan is 1.  Every argument is checked before anything runs on a device.
@@ -122,15 +122,22 @@ def resolve_sampler(device, B: int, num_return_sequences: int, num_beams: int, d
     RowSampler of B identical rows with streams 0..B-1 and the call's seed -- by the identity of kivi_sample_rows what the Sampler
     would have drawn from the penalised logits --, greedy rows when `do_sample=False`; not with beams.  With `sampling=` the penalties
     come from the SamplingParams, the three arguments have to be neutral.  `vocab_size`: the width of the history table of a
-    RowSampler made here for penalised rows."""
-    from .sampling import NEUTRAL, RowSampler, Sampler, SamplingParams, check_penalties
+    RowSampler made here for penalised or constrained rows.
+    `logit_bias` / `allowed_token_ids` / `min_new_tokens` route like the penalties: non-neutral values without
+    `sampling=` make that RowSampler of identical rows, with constraint state; with `sampling=` they come from the SamplingParams and
+    the three arguments stay neutral; not with beams.  The ids `min_new_tokens` suppresses are bound later, once the call's finish
+    conditions are resolved (bind_suppress)."""
+    from .sampling import NEUTRAL, UNCONSTRAINED, RowSampler, Sampler, SamplingParams, check_constraints, check_penalties
     check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
     penalised = (float(repetition_penalty), float(presence_penalty), float(frequency_penalty)) != NEUTRAL
-    if sampling is None and penalised:
+    constrained = check_constraints(logit_bias, allowed_token_ids, min_new_tokens) != UNCONSTRAINED
+    if sampling is None and (penalised or constrained):
         if num_beams != 1:
-            raise ValueError(f"repetition / presence / frequency penalties with beam search (num_beams={num_beams}) are not supported")
+            raise ValueError(f"repetition / presence / frequency penalties, logit_bias, allowed_token_ids and min_new_tokens with beam "
+                             f"search (num_beams={num_beams}) are not supported")
         p = RowSampler._bind(SamplingParams(bool(do_sample), temperature, top_k, top_p, min_p, seed, repetition_penalty=repetition_penalty,
-                                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty))
+                                            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                                            logit_bias=logit_bias, allowed_token_ids=allowed_token_ids, min_new_tokens=min_new_tokens))
         return RowSampler([p] * B, device, list(range(B)), vocab_size=vocab_size), 1
     if sampling is None:
         if not do_sample:
@@ -139,10 +146,11 @@ def resolve_sampler(device, B: int, num_return_sequences: int, num_beams: int, d
             raise ValueError(f"beam sampling (do_sample=True with num_beams={num_beams}) is not supported")
         return Sampler(temperature, top_k, top_p, min_p, seed, device), 1
     n = num_return_sequences
-    if do_sample or temperature != 1.0 or top_k != 50 or top_p != 1.0 or min_p is not None or seed is not None or penalised:
+    if do_sample or temperature != 1.0 or top_k != 50 or top_p != 1.0 or min_p is not None or seed is not None or penalised \
+            or constrained:
         raise ValueError("sampling= carries the parameters of every row: it cannot be combined with do_sample=True or with "
-                         "temperature / top_k / top_p / min_p / seed / repetition_penalty / presence_penalty / frequency_penalty "
-                         "arguments")
+                         "temperature / top_k / top_p / min_p / seed / repetition_penalty / presence_penalty / frequency_penalty / "
+                         "logit_bias / allowed_token_ids / min_new_tokens arguments")
     if num_beams != 1:
         raise ValueError(f"sampling= with beam search (num_beams={num_beams}) is not supported")
     if isinstance(n, bool) or not isinstance(n, int) or n < 1:
@@ -159,7 +167,21 @@ def resolve_sampler(device, B: int, num_return_sequences: int, num_beams: int, d
         raise ValueError(f"{len(sampling)} SamplingParams for a batch of {B} requests")
     bound = [RowSampler._bind(p) for p in sampling]          # one seed per request, shared by its n streams
     return RowSampler([p for p in bound for _ in range(n)], device, [j for _ in bound for j in range(n)],
-                      vocab_size=vocab_size if any(p.penalised for p in bound) else None), n
+                      vocab_size=vocab_size if any(p.penalised or p.constrained for p in bound) else None), n
+
+
+def bind_suppress(pick, sampling, stops, eos_token_id) -> None:
+    """A generate call hands the RowSampler it has made (not a caller's, which is used as it is) the ids that `min_new_tokens`
+    suppresses: per row its eos ids and the stop token ids of its StopParams -- `stops`, resolve_stopping's result (None: the one int
+    `eos_token_id` of the torch path, or nothing).  Stop sequences are not suppressed: they may still end a request early."""
+    if pick is None or pick is sampling or getattr(pick, "_con", None) is None:
+        return
+    from .stopping import stop_ids
+    if stops is None:
+        ids = [stop_ids(eos_token_id, None)] * pick.B
+    else:
+        ids = [p.stop_token_ids for p in (stops if isinstance(stops, (list, tuple)) else stops.rows)]
+    pick.bind_suppress(ids)
 
 
 def observe_prompts(pick, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], fan: int = 1) -> None:

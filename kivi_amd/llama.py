@@ -28,7 +28,7 @@ from . import admit
 from .attention import KiviLayerCacheMF, LlamaAttention_KIVI
 from .beam import beam_search
 from .generation import (PADS_LEFT, DecodeLead, EagerStepper, _PaddedBatch, decode_loop, leading_pads, left_pad,  # noqa: F401
-                         padding_key_row, padding_position_ids, padding_prompt_mask, observe_prompts,
+                         padding_key_row, padding_position_ids, padding_prompt_mask, observe_prompts, bind_suppress,
                          resolve_sampler)
 from .graph import DecodeGraphs
 from .prefill import left_padded
@@ -277,7 +277,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
     def generate_continuous(self, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
                             pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False, compact: Optional[int] = None,
                             short_admissions: bool = False, return_logprobs: bool = False, top_logprobs: int = 0, stopping=None,
-                            return_finish: bool = False):
+                            return_finish: bool = False, allowed_fn=None):
         """Continuous batching over a queue of requests (kivi_amd/serving.py: generate_continuous): a batch of `batch_size` rows whose
         finished rows are taken over by the waiting prompts.  -> the generated tokens of every request, in request order.
         `compact`: None, or the fewest leading tokens worth dropping from the living caches between two steps (rebase_).
@@ -286,10 +286,12 @@ class LlamaForCausalLM_KIVI(nn.Module):
         `return_logprobs` / `top_logprobs=k`: -> (tokens, logprobs[, top_ids, top_logprobs]), each a list with one tensor per request
         (DESIGN.md section 23).
         `eos_token_id`: an int or a list; `stopping`: None, one StopParams, or one per request (stop ids, stop sequences, a limit of
-        its own); `return_finish`: the result gains a list of (reason, index) per request."""
+        its own); `return_finish`: the result gains a list of (reason, index) per request.
+        Per-request constraints (logit_bias, allowed_token_ids, min_new_tokens) come with `sampling`; `allowed_fn`: None, one callable
+        or one per request, asked before every pick for the ids or the bitmask the request may emit next."""
         from .serving import generate_continuous
         return generate_continuous(self, prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, graphed, compact,
-                                   short_admissions, return_logprobs, top_logprobs, stopping, return_finish)
+                                   short_admissions, return_logprobs, top_logprobs, stopping, return_finish, allowed_fn)
 
     # ------------------------------------------------------------------ rebase (DESIGN.md section 17)
     @classmethod
@@ -447,7 +449,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
                  temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
                  seed: Optional[int] = None, return_logprobs: bool = False, sampling=None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, top_logprobs: int = 0, stop_token_ids=None,
-                 stop_sequences=None, stopping=None):
+                 stop_sequences=None, stopping=None, logit_bias=None, allowed_token_ids=None, min_new_tokens: int = 0):
         """Greedy decoding (the recipe of the reference's mem_spd_test.py / example.py), or sampling with `do_sample=True`.
         With `past_key_values` (the caches of an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one
         pass (kivi_attention_extend) and decoding continues from there; the caches are advanced in place.  `attention_mask`:
@@ -503,14 +505,23 @@ class LlamaForCausalLM_KIVI(nn.Module):
         step's one synchronisation is the read of its live count): a finished row emits `pad_token_id`, which is required, and the
         stop itself stays in the output, as `eos_token_id` does; a call whose rows have all finished -- by their `max_new_tokens` too
         -- ends without the pass after the last token.  Beam search keeps its own handling of ONE `eos_token_id` and refuses the
-        rest.  The plain call with one int `eos_token_id` is what it was."""
+        rest.  The plain call with one int `eos_token_id` is what it was.
+
+        `logit_bias` (a dict from token id to an additive bias, +-inf allowed; -inf bans the token), `allowed_token_ids` (the only
+        ids the call may emit) and `min_new_tokens` (every row's eos ids and stop token ids are masked for its first so many
+        tokens): applied inside the fused sampler (kivi_sample_rows_con), before the penalties and the
+        temperature, greedy rows included.  They route like the penalties: non-neutral values make the call's sampler a RowSampler
+        of identical rows; with `sampling=` they come from the SamplingParams (a list may constrain every request differently) and
+        the three arguments stay neutral.  Not with beams.  `min_new_tokens` does not hold back stop SEQUENCES, which may still end
+        a row early, and a caller's RowSampler is used as it is (bind its suppressed ids with `suppress=`).  `return_logprobs` /
+        `top_logprobs` stay under the RAW distribution: a token the constraints forbid can appear among the top ids."""
         if return_logprobs and num_beams > 1:
             raise ValueError("return_logprobs is for greedy decoding and sampling; beam search (num_beams > 1) returns its "
                              "sequences_scores with return_scores=True")
         check_top_logprobs(top_logprobs, return_logprobs, num_beams, self.config.vocab_size)
         pick, fan = resolve_sampler(input_ids.device, input_ids.shape[0], num_return_sequences, num_beams, do_sample, temperature,
                                     top_k, top_p, min_p, seed, sampling, repetition_penalty, presence_penalty, frequency_penalty,
-                                    self.config.vocab_size)
+                                    self.config.vocab_size, logit_bias, allowed_token_ids, min_new_tokens)
         if eos_token_id is not None and pad_token_id is None:
             raise ValueError("eos_token_id needs a pad_token_id for the rows that have finished")
         if sampling is None and (num_beams < 1 or num_return_sequences < 1 or num_return_sequences > num_beams):
@@ -519,6 +530,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
             raise ValueError("return_scores: sequences_scores exist for beam search (num_beams > 1) only")
         stops = resolve_stopping(input_ids.shape[0], max_new_tokens, eos_token_id, pad_token_id, stop_token_ids, stop_sequences,
                                  stopping, num_beams, self.config.vocab_size, fan)
+        bind_suppress(pick, sampling, stops, eos_token_id)
         stepper = EagerStepper(self, input_ids, past_key_values, attention_mask, max_new_tokens, max(num_beams, fan))
         observe_prompts(pick, input_ids, attention_mask, fan)
         if stops is not None:
@@ -629,7 +641,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
                          seed: Optional[int] = None, sampling=None, repetition_penalty: float = 1.0,
                          presence_penalty: float = 0.0, frequency_penalty: float = 0.0, return_logprobs: bool = False,
                          top_logprobs: int = 0, eos_token_id=None, pad_token_id: Optional[int] = None, stop_token_ids=None,
-                         stop_sequences=None, stopping=None, sync_every: Optional[int] = SYNC_EVERY):
+                         stop_sequences=None, stopping=None, sync_every: Optional[int] = SYNC_EVERY, logit_bias=None,
+                         allowed_token_ids=None, min_new_tokens: int = 0):
         """generate() with the dense part of every decode step replayed from hipGraphs (kivi_amd.graph.DecodeGraphs).
         `attention_mask`: HF's 2D (B, T) mask of left-padded prompts (1 = real token).  Greedy, or sampling with `do_sample=True`
         and the parameters of generate() (the draw inside the graph; the same tokens as generate() with the same seed).  Beams
@@ -646,15 +659,19 @@ class LlamaForCausalLM_KIVI(nn.Module):
         the at most sync_every - 1 steps that ran past that point are cut off -- the caches of a graphed call die with it, nothing
         else observes them -- and the scores of a finished row's pads are masked from the tracker's lengths (0, id -1).  With the
         keyword forms the model keeps one tracker per (B, device, pad) and rebinds its rows, so another call with other stops
-        replays the graphs that exist; a StopRows passed as `stopping=` is used as it is and keys the graphs by its own buffers."""
+        replays the graphs that exist; a StopRows passed as `stopping=` is used as it is and keys the graphs by its own buffers.
+        `logit_bias` / `allowed_token_ids` / `min_new_tokens`: as in generate(); the constrained draw is
+        inside the captured step, and so is the advance towards the end of the suppression."""
         if sampling is None and num_beams != 1 and not do_sample:
             raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
         check_top_logprobs(top_logprobs, return_logprobs, num_beams, self.config.vocab_size)
         pick, _ = resolve_sampler(input_ids.device, input_ids.shape[0], 1, num_beams, do_sample, temperature, top_k, top_p, min_p,
-                                  seed, sampling, repetition_penalty, presence_penalty, frequency_penalty, self.config.vocab_size)
+                                  seed, sampling, repetition_penalty, presence_penalty, frequency_penalty, self.config.vocab_size,
+                                  logit_bias, allowed_token_ids, min_new_tokens)
         check_sync_every(sync_every)
         stops = resolve_stopping(input_ids.shape[0], max_new_tokens, eos_token_id, pad_token_id, stop_token_ids, stop_sequences,
                                  stopping, 1, self.config.vocab_size, torch_eos=False)
+        bind_suppress(pick, sampling, stops, eos_token_id)
         logits, pasts = self.forward(input_ids, padding_mask=attention_mask)
         observe_prompts(pick, input_ids, attention_mask)
         if attention_mask is not None:

@@ -44,6 +44,12 @@ The policy is fixed (tests restate it):
     kivi_token_top_logprobs launch beside the pick (graphed: inside the captured step).  The values are read where the tokens are
     read, so a step keeps its one synchronisation.  Eager, the rows with nothing to do score the ignore index; the captured step
     scores every row and the host drops what no request owns.
+  * Constraints: when a request's SamplingParams carry a logit_bias, allowed_token_ids or min_new_tokens, or
+    an `allowed_fn` is given, both samplers get constraint state.  The ids a request's min_new_tokens suppresses are its stop ids
+    (the eos ids first); the batch's row is bound with set_row(..., draw_index=1, generated=[the first token], suppress=<those>), so
+    its suppression ends min_new_tokens draws after the request's first.  Before every pick the scheduler calls a request's
+    `allowed_fn` with the tokens the request has so far -- it holds them on the host anyway -- and uploads the answer with
+    set_allowed; the captured step reads the mask buffer and is not captured again.
 """
 from __future__ import annotations
 
@@ -63,7 +69,7 @@ def _positive_int(x) -> bool:
 
 
 def check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, vocab_size: Optional[int] = None,
-                    compact: Optional[int] = None, short_admissions: bool = False):
+                    compact: Optional[int] = None, short_admissions: bool = False, allowed_fn=None):
     """-> (prompts as 1-D int64 CPU tensors, max_new_tokens per request, bound SamplingParams per request or None); ValueError for
     anything generate_continuous cannot serve (no device work)."""
     if compact is not None and not _positive_int(compact):
@@ -100,7 +106,17 @@ def check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token
             raise ValueError("sampling has to be None (greedy), a SamplingParams, or a list with one SamplingParams per request")
         if len(sampling) != N:
             raise ValueError(f"{len(sampling)} SamplingParams for {N} requests")
+        for p in sampling:
+            p.check_vocab(vocab_size)
         params = [RowSampler._bind(p) for p in sampling]          # one seed per request, whichever row it lands on
+    if allowed_fn is not None:
+        fns = [allowed_fn] * N if callable(allowed_fn) else allowed_fn
+        if not isinstance(fns, (list, tuple)) or not all(f is None or callable(f) for f in fns):
+            raise ValueError("allowed_fn has to be None, a callable, or a list with one callable or None per request")
+        if len(fns) != N:
+            raise ValueError(f"{len(fns)} allowed_fn entries for {N} requests")
+        if params is None:                                        # greedy requests: the masks still need a RowSampler
+            params = [RowSampler._bind(SamplingParams(do_sample=False)) for _ in range(N)]
     return seqs, limits, params
 
 
@@ -147,7 +163,7 @@ def admission_offset(L: int, longest_prompt: int, R: int, quantum: int) -> int:
 def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
                         pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False,
                         compact: Optional[int] = None, short_admissions: bool = False, return_logprobs: bool = False,
-                        top_logprobs: int = 0, stopping=None, return_finish: bool = False):
+                        top_logprobs: int = 0, stopping=None, return_finish: bool = False, allowed_fn=None):
     """`prompts`: a list of token id sequences, possibly more than `batch_size`; `max_new_tokens`: an int or one per request;
     `sampling`: None (greedy), one SamplingParams, or one per request.  -> the generated tokens of every request as 1-D int64
     tensors, in request order, ending with `eos_token_id` where it was produced.  The policy: the module docstring.
@@ -165,10 +181,16 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
     `eos_token_id`: an int or a list of ids; `stopping`: None, one StopParams or one per request -- stop ids (after the eos ids),
     stop sequences, and a max_new_tokens of its own (the smaller of the two limits holds).  A request's tokens end with the stop that
     finished it.  `return_finish=True`: the result (a tuple in any case then) gains a last element, a list of (reason, index) per
-    request -- kivi_amd.stopping: TOKEN / SEQUENCE / LENGTH and the position of the id or sequence that matched (-1 for LENGTH)."""
+    request -- kivi_amd.stopping: TOKEN / SEQUENCE / LENGTH and the position of the id or sequence that matched (-1 for LENGTH).
+    Constraints come with `sampling`: a request's logit_bias, allowed_token_ids and min_new_tokens, which
+    holds back the request's eos and stop token ids (not its stop sequences).  `allowed_fn`: None, one callable, or one callable or
+    None per request -- before every pick it is called with the list of the request's generated ids and answers token ids, an int32
+    bitmask (RowSampler.set_allowed) or None (the request's own allowed_token_ids, or no mask): the mask of that one pick."""
     prompts, limits, params = check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling,
-                                              model.config.vocab_size, compact, short_admissions)
-    finish = [StopState(p) for p in check_stopping(limits, eos_token_id, pad_token_id, stopping, model.config.vocab_size)]
+                                              model.config.vocab_size, compact, short_admissions, allowed_fn)
+    stops = check_stopping(limits, eos_token_id, pad_token_id, stopping, model.config.vocab_size)
+    finish = [StopState(p) for p in stops]
+    fns = None if allowed_fn is None else ([allowed_fn] * len(prompts) if callable(allowed_fn) else list(allowed_fn))
     check_top_logprobs(top_logprobs, return_logprobs, 1, model.config.vocab_size)
     k = top_logprobs
     pad = 0 if pad_token_id is None else pad_token_id
@@ -179,8 +201,10 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
 
     ids, mask = left_pad(prompts[:B], pad, device, length=L)
     logits, pasts = model.forward(ids, padding_mask=mask)
-    table = model.config.vocab_size if params is not None and any(p.penalised for p in params) else None
-    sampler = None if params is None else RowSampler(params[:B], device, vocab_size=table)
+    con = params is not None and (fns is not None or any(p.constrained for p in params))
+    table = model.config.vocab_size if params is not None and (con or any(p.penalised for p in params)) else None
+    sampler = None if params is None else RowSampler(params[:B], device, vocab_size=table, constraints=con,
+                                                     suppress=[stops[r].stop_token_ids for r in range(B)])
     if table is not None:
         sampler.observe_prompt(ids, attention_mask=mask)
 
@@ -197,13 +221,22 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
         res = score_top(lg, k, t)
         return res.target_logprob, res.ids, res.logprobs
 
+    out: List[List[int]] = [[] for _ in range(N)]
+
+    def bind_masks(rows_sampler, pairs) -> None:
+        """Every (row of `rows_sampler`, request) pair whose request has an allowed_fn gets the mask of its next pick."""
+        for b, r in pairs:
+            if fns is not None and fns[r] is not None:
+                answer = fns[r](list(out[r]))
+                rows_sampler.set_allowed(b, params[r].allowed_token_ids if answer is None else answer)
+
+    bind_masks(sampler, [(b, b) for b in range(B)])
     tok = pick(logits, sampler)
     scores = score(logits, tok) if return_logprobs else None
     mask2d = torch.ones((B, 2 * L + 64), dtype=torch.long, device=device)      # column t: 1 = cache token t of the row is real
     mask2d[:, :L] = mask
     owner: List[Optional[int]] = list(range(B))                                # the request of every row (None: nothing to do)
     lead = [L - prompts[r].numel() for r in range(B)]                          # leading pads of every row (host side, no device read)
-    out: List[List[int]] = [[] for _ in range(N)]
     out_scores: List[List[list]] = [[[] for _ in range(N)] for _ in range(3)]      # logprob, top ids, top logprobs of every token
     waiting = B
 
@@ -245,9 +278,11 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
             if off:
                 mask2d[rows, :off] = 0                                             # the zeroed lead is masked like any pad
             mask2d[rows, off:L] = new_mask
-            first_sampler = None if params is None else RowSampler([params[r] for r in reqs], device, vocab_size=table)
+            first_sampler = None if params is None else RowSampler([params[r] for r in reqs], device, vocab_size=table, constraints=con,
+                                                                   suppress=[stops[r].stop_token_ids for r in reqs])
             if table is not None:
                 first_sampler.observe_prompt(new_ids, attention_mask=new_mask)
+            bind_masks(first_sampler, list(enumerate(reqs)))
             first = pick(lg, first_sampler)                                                                 # draw 0 of each
             first_scores = score(lg, first) if return_logprobs else None
             tok[rows] = first
@@ -257,7 +292,8 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
                 owner[b] = r
                 lead[b] = L - prompts[r].numel()
                 if sampler is not None:
-                    sampler.set_row(b, params[r], draw_index=1, prompt=prompts[r], generated=[t])
+                    sampler.set_row(b, params[r], draw_index=1, prompt=prompts[r], generated=[t],
+                                    suppress=stops[r].stop_token_ids if con else None)
                 record(b, t, fsc, i)
         if all(r is None for r in owner):
             break
@@ -267,6 +303,7 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
         if L + 1 > mask2d.shape[1]:
             mask2d = torch.cat([mask2d, torch.ones_like(mask2d)], dim=1)
         m = mask2d[:, : L + 1]                                                 # the fed token is real in every row
+        bind_masks(sampler, [(b, owner[b]) for b in range(B) if owner[b] is not None])
         if graphed and return_logprobs:
             _, *scores = model.decode_graphed(tok, pasts, L, 1, attention_mask=m, sampling=sampler, logprobs=k)
             tok = model.graphs.tok.clone()
