@@ -16,11 +16,11 @@
 // The row is read from memory in every pass (an L2 hit after the first); nothing is staged, so any V up to KIVI_SAMPLE_MAX_V works.
 // kivi_sample: a second, one-thread launch advances the draw counter n of the RNG state after the sampler has read it.
 // kivi_sample_rows: the same row body with parameters, seed, stream and draw index read per row from device
-// memory; a greedy flag per row; each block advances its own row's draw index.
-// kivi_sample_rows_pen: the row kernel with repetition / presence / frequency penalties read from a per-row
-// history table where the logit is read (PenRow), the token counted in the table where it is written; kivi_seen_mark fills the table.
-// kivi_sample_rows_con: the same again with a constraint record per row -- an allow mask, a sorted list of
-// biased or suppressed tokens -- applied by the reader ConRow; kivi_allow_mark writes mask rows from id lists.
+// memory; a greedy flag per row; each block advances its own row's draw index.  kivi_sample_rows_pen (section 22) and
+// kivi_sample_rows_con (section 25) launch the same kernel, sample_rows_kernel, with more of its optional state: a per-row history
+// table and penalty record -- repetition / presence / frequency penalties applied where the logit is read (PenRow), the token counted
+// in the table where it is written; kivi_seen_mark fills the table -- and a constraint record per row -- an allow mask, a sorted list
+// of biased or suppressed tokens -- applied by the reader ConRow; kivi_allow_mark writes mask rows from id lists.
 #include "kivi_common.h"
 
 namespace {
@@ -97,7 +97,7 @@ struct Row {
     }
 };
 
-// The reader of kivi_sample_rows_pen: the penalised logit of include/kivi_hip.h from the row's history word (bit 15: in the prompt;
+// The reader of a penalised row: the penalised logit of include/kivi_hip.h from the row's history word (bit 15: in the prompt;
 // bits 0-14: times emitted), then Row's score.  Every operation is one correctly rounded fp32 operation, none contracted into an
 // fma, so a torch fp32 restatement gives the same bits (kivi_amd/sampling.py: reference_penalise).
 template <typename T>
@@ -221,8 +221,8 @@ __device__ uint32_t radix_select(Shared& sh, const Reader& row, int e0, int e1, 
 
 // One row, by the whole workgroup: the body of both kernels.  Every branch below is on values that are the same for all threads of
 // the block (the row's parameters, V, BS), so every __syncthreads() is reached by all 1024 threads on every path.
-// Counter word 0 of the draw is `c0`, the key `seed`, the draw index `n`.  `row`: the reader of the row's scores (Row, or PenRow with
-// the penalties of kivi_sample_rows_pen).  Returns the token (every thread).
+// Counter word 0 of the draw is `c0`, the key `seed`, the draw index `n`.  `row`: the reader of the row's scores (Row, PenRow or
+// ConRow).  Returns the token (every thread).
 template <class R>
 __device__ __forceinline__ int sample_row(Shared& sh, const R& row, int V, int BS, int top_k, float top_p, float min_p, uint32_t c0,
                                           uint64_t seed, int64_t n, int64_t* __restrict__ out) {
@@ -331,9 +331,9 @@ __global__ __launch_bounds__(kThreads) void sample_kernel(const T* __restrict__ 
                (uint64_t)state[0], state[1], out + (int64_t)blockIdx.x * out_stride);
 }
 
-// The row body of sample_rows_kernel (below, kept as it was) over any reader, for sample_rows_pen_kernel: the greedy or the sampling
-// path -- a block-uniform choice -- over `row`, whose temp / div this sets, with the same clamps of a record outside the contract.
-// Returns the token on thread 0.
+// The row body of sample_rows_kernel over any reader: the greedy or the sampling path -- a block-uniform choice -- over `row`, whose
+// temp / div this sets, with the clamps of a record outside the contract (include/kivi_hip.h): it never loops and never indexes
+// outside the row.  Returns the token on thread 0.
 template <class R>
 __device__ __forceinline__ int rows_token(Shared& sh, R row, const kivi_sample_row& r, int V, int BS, int64_t n,
                                           int64_t* __restrict__ dst) {
@@ -349,74 +349,7 @@ __device__ __forceinline__ int rows_token(Shared& sh, R row, const kivi_sample_r
     return sample_row(sh, row, V, BS, top_k, top_p, min_p, r.stream, (uint64_t)r.seed, n, dst);
 }
 
-// Per-row parameters and RNG streams (kivi_sample_rows): block b reads rows[b] and draw_index[b], takes the greedy or the sampling
-// path -- a block-uniform choice -- and then stores draw_index[b] + 1 itself (one lane, a plain vector store): no second launch.
-// Every thread has read n before the first barrier of either path, and the store comes after the last one.
-// Records outside the contract degrade as the header says: they never loop and never index outside the row.
-template <typename T>
-__global__ __launch_bounds__(kThreads) void sample_rows_kernel(const T* __restrict__ logits, int64_t row_stride, int V, int BS,
-                                                               const kivi_sample_row* __restrict__ rows, int64_t* draw_index,
-                                                               int64_t* __restrict__ out, int64_t out_stride) {
-    __shared__ Shared sh;
-    const int b = blockIdx.x;
-    const kivi_sample_row r = rows[b];
-    const int64_t n = draw_index[b];
-    const T* row = logits + (int64_t)b * row_stride;
-    int64_t* dst = out + (int64_t)b * out_stride;
-    const bool greedy = (r.flags & KIVI_SAMPLE_ROW_GREEDY) || !(r.temperature > 0.0f) || !__builtin_isfinite(r.temperature);
-    if (greedy) {
-        greedy_row(sh, Row<T>{row, 1.0f, false}, V, dst);
-    } else {
-        const int top_k = max(r.top_k, 0);
-        float top_p = r.top_p <= 1.0f ? r.top_p : 1.0f;                 // NaN and > 1: off
-        if (!(top_p > 0.0f)) top_p = 1.17549435e-38f;                   // <= 0: the smallest (0, 1] value, the top class alone
-        float min_p = r.min_p >= 0.0f ? r.min_p : 0.0f;                 // NaN and < 0: off
-        if (min_p >= 1.0f) min_p = 0.99999994f;                         // the largest value below 1: the maximum stays
-        sample_row(sh, Row<T>{row, r.temperature, r.temperature != 1.0f}, V, BS, top_k, top_p, min_p, r.stream, (uint64_t)r.seed, n,
-                   dst);
-    }
-    if (threadIdx.x == 0) draw_index[b] = n + 1;
-}
-
-// kivi_sample_rows_pen: the same block per row, with the row's penalty record and its row of the history
-// table.  A block whose record is neutral after the clamps of the header -- a block-uniform fact -- takes the reader of
-// sample_rows_kernel and loads nothing from the table; any other first folds the row's history into a bitmap of 64-token chunks in
-// LDS (mark_chunks), so that the passes touch the table only where something is marked.  Either way thread 0 then counts the token it has just written: one 16-bit
-// load, one plain 16-bit vector store, after the last barrier of the row body, so after every read of the table by this block; no
-// other block reads or writes this row of the table.
-template <typename T>
-__global__ __launch_bounds__(kThreads) void sample_rows_pen_kernel(const T* __restrict__ logits, int64_t row_stride, int V, int BS,
-                                                                   const kivi_sample_row* __restrict__ rows, int64_t* draw_index,
-                                                                   const kivi_sample_penalty* __restrict__ pen, uint16_t* seen,
-                                                                   int64_t seen_stride, int64_t* __restrict__ out, int64_t out_stride) {
-    __shared__ Shared sh;
-    __shared__ uint8_t marks[KIVI_SAMPLE_MAX_V / 512];
-    const int b = blockIdx.x;
-    const kivi_sample_row r = rows[b];
-    const int64_t n = draw_index[b];
-    float theta = pen[b].repetition, pres = pen[b].presence, freq = pen[b].frequency;
-    if (!(theta > 0.0f) || !__builtin_isfinite(theta)) theta = 1.0f;
-    if (!__builtin_isfinite(pres)) pres = 0.0f;
-    if (!__builtin_isfinite(freq)) freq = 0.0f;
-    const T* row = logits + (int64_t)b * row_stride;
-    uint16_t* hist = seen + (int64_t)b * seen_stride;
-    int64_t* dst = out + (int64_t)b * out_stride;
-    int tok;
-    if (theta == 1.0f && pres == 0.0f && freq == 0.0f) {
-        tok = rows_token(sh, Row<T>{row, 1.0f, false}, r, V, BS, n, dst);
-    } else {
-        mark_chunks(marks, hist, V);
-        __syncthreads();
-        tok = rows_token(sh, PenRow<T>{row, 1.0f, false, hist, theta, pres, freq, marks}, r, V, BS, n, dst);
-    }
-    if (threadIdx.x == 0) {
-        draw_index[b] = n + 1;
-        const uint16_t w = hist[tok];                                   // tok in [0, V), V <= seen_stride
-        if ((w & 0x7FFFu) != 0x7FFFu) hist[tok] = (uint16_t)(w + 1);
-    }
-}
-
-// The reader of kivi_sample_rows_con: the rule of include/kivi_hip.h -- the list entry's bias or suppression,
+// The reader of a constrained row: the rule of include/kivi_hip.h -- the list entry's bias or suppression,
 // PenRow's penalised logit, the allow mask -- then Row's score.  MASK: the row's allow mask is in force; its word is loaded from
 // global memory beside the logit, before anything depends on either (the 64 tokens of a wave's run are two words, which every later
 // pass finds in the cache).  LIST: the row has a list or a penalty.  `marks` is then the chunk bitmap of PenRow as 32-bit words with
@@ -425,10 +358,6 @@ __global__ __launch_bounds__(kThreads) void sample_rows_pen_kernel(const T* __re
 // two, compared one by one (three dependent LDS reads under the logit's load, where a binary search per token was ten).  The scan is
 // bounded by n_list whatever the list holds.  A token of such a chunk without an entry and with a zero history word only has a
 // zero subtracted, as in PenRow.
-// PenRow under another name for sample_rows_con_kernel: the row functions it instantiates are then its own, and those of
-// sample_rows_pen_kernel keep their single caller -- and with it the code the compiler gave them before.
-template <typename T>
-struct ConPenRow : PenRow<T> {};
 struct ListEnt {
     uint32_t word, bits;                             // kivi_sample_list_entry with the value as its bits
 };
@@ -468,86 +397,104 @@ struct ConRow {
     }
 };
 
-// kivi_sample_rows_con: the block of sample_rows_pen_kernel with the row's constraint record.  A block whose
-// record is neutral -- no mask in force, an empty list; a block-uniform fact -- does exactly what sample_rows_pen_kernel does (or,
-// without a table, sample_rows_kernel) and reads neither masks nor lists.  A block with a mask alone runs the row body over
-// ConRow<MASK>.  Any other copies its list into LDS (n_list clamped, NaN values zeroed), builds the chunk bitmap -- zeroed, then
-// mark_chunks over the history if the row is penalised, then an LDS atomic OR per listed token below V -- and the table first[]
-// (one binary search of the list per chunk, once per launch), and runs the row body over ConRow<., LIST>.  Thread 0's count and the
-// draw_index store stay where they were.
-template <typename T>
-__global__ __launch_bounds__(kThreads) void sample_rows_con_kernel(const T* __restrict__ logits, int64_t row_stride, int V, int BS,
-                                                                   const kivi_sample_row* __restrict__ rows, int64_t* draw_index,
-                                                                   const kivi_sample_penalty* __restrict__ pen, uint16_t* seen,
-                                                                   int64_t seen_stride, const kivi_sample_constraint* __restrict__ con,
-                                                                   const uint32_t* __restrict__ allow, int64_t allow_stride,
-                                                                   const kivi_sample_list_entry* __restrict__ lists, int64_t list_stride,
-                                                                   int64_t* __restrict__ out, int64_t out_stride) {
+// The row kernel of kivi_sample_rows, kivi_sample_rows_pen and kivi_sample_rows_con: block b reads rows[b] and draw_index[b], takes
+// the greedy or the sampling path and then stores draw_index[b] + 1 itself (one lane, a plain vector store): no second launch.  Every
+// thread has read n before the first barrier of either path, and the store comes after the last one.
+// The state beyond the records is optional, and every choice below is block-uniform.  `seen` (with `pen`): the
+// row's penalty record, clamped as the header says, and its row of the history table; null reads as the neutral record.  `con`
+// (section 25): the row's constraint record, with `allow` and `lists`; null reads as the neutral record (flags 0, n_list 0).
+// STATE = false is the instantiation for a launch with none of it (kivi_sample_rows): the first line of the table alone, without the
+// LDS arrays and record loads of the others, which cost a 32-row launch about 1 % when it carried them.
+//   neutral record, not penalised   Row: nothing is loaded from table, masks or lists
+//   neutral record, penalised       PenRow, after the row's history is folded into a bitmap of 64-token chunks in LDS (mark_chunks),
+//                                   so that the passes touch the table only where something is marked
+//   a mask alone                    ConRow<MASK>
+//   any other                       ConRow<., LIST>: the list is copied into LDS (n_list clamped, NaN values zeroed), the chunk bitmap
+//                                   built -- zeroed, then mark_chunks over the history if the row is penalised, then an LDS atomic OR
+//                                   per listed token below V -- and the table first[] (one binary search of the list per chunk)
+// With a table thread 0 then counts the token it has just written: one 16-bit load, one plain 16-bit vector store, after the last
+// barrier of the row body, so after every read of the table by this block; no other block reads or writes this row of the table.
+template <typename T, bool STATE>
+__global__ __launch_bounds__(kThreads) void sample_rows_kernel(const T* __restrict__ logits, int64_t row_stride, int V, int BS,
+                                                               const kivi_sample_row* __restrict__ rows, int64_t* draw_index,
+                                                               const kivi_sample_penalty* __restrict__ pen, uint16_t* seen,
+                                                               int64_t seen_stride, const kivi_sample_constraint* __restrict__ con,
+                                                               const uint32_t* __restrict__ allow, int64_t allow_stride,
+                                                               const kivi_sample_list_entry* __restrict__ lists, int64_t list_stride,
+                                                               int64_t* __restrict__ out, int64_t out_stride) {
     __shared__ Shared sh;
-    __shared__ uint32_t marks[KIVI_SAMPLE_MAX_V / 2048];
-    __shared__ ListEnt lst[KIVI_SAMPLE_MAX_LIST];
-    __shared__ uint16_t first[KIVI_SAMPLE_MAX_V / 64 + 2];
     const int b = blockIdx.x;
     const kivi_sample_row r = rows[b];
     const int64_t n = draw_index[b];
-    float theta = 1.0f, pres = 0.0f, freq = 0.0f;
-    if (seen) {
-        theta = pen[b].repetition, pres = pen[b].presence, freq = pen[b].frequency;
-        if (!(theta > 0.0f) || !__builtin_isfinite(theta)) theta = 1.0f;
-        if (!__builtin_isfinite(pres)) pres = 0.0f;
-        if (!__builtin_isfinite(freq)) freq = 0.0f;
-    }
-    const bool penalised = !(theta == 1.0f && pres == 0.0f && freq == 0.0f);
-    const kivi_sample_constraint c = con[b];
-    const int n_list = lists ? min(max(c.n_list, 0), min(KIVI_SAMPLE_MAX_LIST, (int)list_stride)) : 0;
-    const uint32_t* mask = (allow && (c.flags & KIVI_CONSTRAINT_MASK)) ? allow + (int64_t)b * allow_stride : nullptr;
     const T* row = logits + (int64_t)b * row_stride;
-    uint16_t* hist = seen ? seen + (int64_t)b * seen_stride : nullptr;
+    uint16_t* hist = (STATE && seen) ? seen + (int64_t)b * seen_stride : nullptr;
     int64_t* dst = out + (int64_t)b * out_stride;
-    const PenRow<T> pr{row, 1.0f, false, hist, theta, pres, freq, reinterpret_cast<const uint8_t*>(marks)};
     int tok;
-    if (!mask && n_list == 0) {
-        if (!penalised) {
-            tok = rows_token(sh, Row<T>{row, 1.0f, false}, r, V, BS, n, dst);
-        } else {
-            mark_chunks(reinterpret_cast<uint8_t*>(marks), hist, V);
-            __syncthreads();
-            tok = rows_token(sh, ConPenRow<T>{pr}, r, V, BS, n, dst);
-        }
-    } else if (n_list == 0 && !penalised) {
-        tok = rows_token(sh, ConRow<T, true, false>{row, 1.0f, false, pr, false, marks, first, lst, false, mask}, r, V, BS, n, dst);
+    if constexpr (!STATE) {
+        tok = rows_token(sh, Row<T>{row, 1.0f, false}, r, V, BS, n, dst);
     } else {
-        const int tid = threadIdx.x;
-        if (tid < KIVI_SAMPLE_MAX_V / 2048) marks[tid] = 0;
-        const kivi_sample_list_entry* src = lists + (int64_t)b * list_stride;
-        for (int i = tid; i < n_list; i += kThreads) {
-            const kivi_sample_list_entry ent = src[i];
-            lst[i] = ListEnt{ent.word, __builtin_isnan(ent.value) ? 0u : __builtin_bit_cast(uint32_t, ent.value)};
+        __shared__ uint32_t marks[KIVI_SAMPLE_MAX_V / 2048];
+        __shared__ ListEnt lst[KIVI_SAMPLE_MAX_LIST];
+        __shared__ uint16_t first[KIVI_SAMPLE_MAX_V / 64 + 2];
+        float theta = 1.0f, pres = 0.0f, freq = 0.0f;
+        if (seen) {
+            theta = pen[b].repetition, pres = pen[b].presence, freq = pen[b].frequency;
+            if (!(theta > 0.0f) || !__builtin_isfinite(theta)) theta = 1.0f;
+            if (!__builtin_isfinite(pres)) pres = 0.0f;
+            if (!__builtin_isfinite(freq)) freq = 0.0f;
         }
-        __syncthreads();
-        if (penalised) {
-            mark_chunks(reinterpret_cast<uint8_t*>(marks), hist, V);
-            __syncthreads();
-        }
-        for (int i = tid; i < n_list; i += kThreads) {
-            const uint32_t id = lst[i].word & KIVI_LIST_TOKEN;
-            if (id < (uint32_t)V) atomicOr(&marks[id >> 11], 1u << ((id >> 6) & 31));
-        }
-        for (int ch = tid; ch <= (V + 63) / 64; ch += kThreads) {           // first[ch]: the entries below token 64 ch (in [0, n_list])
-            int lo = 0, hi = n_list;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if ((int)(lst[mid].word & KIVI_LIST_TOKEN) < ch * 64) lo = mid + 1;
-                else hi = mid;
+        const bool penalised = !(theta == 1.0f && pres == 0.0f && freq == 0.0f);
+        kivi_sample_constraint c = {};
+        if (con) c = con[b];
+        const int n_list = lists ? min(max(c.n_list, 0), min(KIVI_SAMPLE_MAX_LIST, (int)list_stride)) : 0;
+        const uint32_t* mask = (allow && (c.flags & KIVI_CONSTRAINT_MASK)) ? allow + (int64_t)b * allow_stride : nullptr;
+        const PenRow<T> pr{row, 1.0f, false, hist, theta, pres, freq, reinterpret_cast<const uint8_t*>(marks)};
+        if (!mask && n_list == 0) {
+            if (!penalised) {
+                tok = rows_token(sh, Row<T>{row, 1.0f, false}, r, V, BS, n, dst);
+            } else {
+                mark_chunks(reinterpret_cast<uint8_t*>(marks), hist, V);
+                __syncthreads();
+                tok = rows_token(sh, pr, r, V, BS, n, dst);
             }
-            first[ch] = (uint16_t)lo;
+        } else if (n_list == 0 && !penalised) {
+            const ConRow<T, true, false> cr{row, 1.0f, false, pr, false, marks, first, lst, false, mask};
+            tok = rows_token(sh, cr, r, V, BS, n, dst);
+        } else {
+            const int tid = threadIdx.x;
+            if (tid < KIVI_SAMPLE_MAX_V / 2048) marks[tid] = 0;
+            const kivi_sample_list_entry* src = lists + (int64_t)b * list_stride;
+            for (int i = tid; i < n_list; i += kThreads) {
+                const kivi_sample_list_entry ent = src[i];
+                lst[i] = ListEnt{ent.word, __builtin_isnan(ent.value) ? 0u : __builtin_bit_cast(uint32_t, ent.value)};
+            }
+            __syncthreads();
+            if (penalised) {
+                mark_chunks(reinterpret_cast<uint8_t*>(marks), hist, V);
+                __syncthreads();
+            }
+            for (int i = tid; i < n_list; i += kThreads) {
+                const uint32_t id = lst[i].word & KIVI_LIST_TOKEN;
+                if (id < (uint32_t)V) atomicOr(&marks[id >> 11], 1u << ((id >> 6) & 31));
+            }
+            for (int ch = tid; ch <= (V + 63) / 64; ch += kThreads) {       // first[ch]: the entries below token 64 ch (in [0, n_list])
+                int lo = 0, hi = n_list;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if ((int)(lst[mid].word & KIVI_LIST_TOKEN) < ch * 64) lo = mid + 1;
+                    else hi = mid;
+                }
+                first[ch] = (uint16_t)lo;
+            }
+            __syncthreads();
+            const bool sup = n < c.suppress_until;
+            if (mask)
+                tok = rows_token(sh, ConRow<T, true, true>{row, 1.0f, false, pr, penalised, marks, first, lst, sup, mask}, r, V, BS, n,
+                                 dst);
+            else
+                tok = rows_token(sh, ConRow<T, false, true>{row, 1.0f, false, pr, penalised, marks, first, lst, sup, mask}, r, V, BS, n,
+                                 dst);
         }
-        __syncthreads();
-        const bool sup = n < c.suppress_until;
-        if (mask)
-            tok = rows_token(sh, ConRow<T, true, true>{row, 1.0f, false, pr, penalised, marks, first, lst, sup, mask}, r, V, BS, n, dst);
-        else
-            tok = rows_token(sh, ConRow<T, false, true>{row, 1.0f, false, pr, penalised, marks, first, lst, sup, mask}, r, V, BS, n, dst);
     }
     if (threadIdx.x == 0) {
         draw_index[b] = n + 1;
@@ -627,6 +574,13 @@ __global__ void advance_kernel(int64_t* state) { state[1] += 1; }
 
 }  // namespace
 
+// The bucket of the draw: a power of two, at most 1024 buckets per row.
+static int bucket_size(int V) {
+    int BS = KIVI_WAVE;
+    while ((int64_t)BS * 1024 < V) BS <<= 1;
+    return BS;
+}
+
 extern "C" int kivi_sample(const void* logits, int logits_bits, int64_t row_stride, int B, int V, float temperature, int top_k,
                            float top_p, float min_p, int64_t* rng_state, int64_t* out_tokens, int64_t out_stride,
                            kivi_stream_t stream) {
@@ -644,8 +598,7 @@ extern "C" int kivi_sample(const void* logits, int logits_bits, int64_t row_stri
     const int esz = logits_bits / 8;
     KIVI_REQUIRE((uintptr_t)logits % esz == 0 && (uintptr_t)rng_state % 8 == 0 && (uintptr_t)out_tokens % 8 == 0, KIVI_EALIGN,
                  "kivi_sample: misaligned logits (%d-byte elements), rng_state or out_tokens (8 bytes)", esz);
-    int BS = KIVI_WAVE;                              // bucket of the draw: a power of two, at most 1024 buckets per row
-    while ((int64_t)BS * 1024 < V) BS <<= 1;
+    const int BS = bucket_size(V);
     const hipStream_t s = (hipStream_t)stream;
     if (logits_bits == 16)
         KIVI_LAUNCH(sample_kernel<f16>, dim3(B), dim3(kThreads), s, (const f16*)logits, row_stride, V, BS, temperature, top_k, top_p,
@@ -659,60 +612,72 @@ extern "C" int kivi_sample(const void* logits, int logits_bits, int64_t row_stri
     return kivi_launch_status("kivi_sample (advance)");
 }
 
-extern "C" int kivi_sample_rows(const void* logits, int logits_bits, int64_t row_stride, int B, int V, const kivi_sample_row* rows,
-                                int64_t* draw_index, int64_t* out_tokens, int64_t out_stride, kivi_stream_t stream) {
-    KIVI_REQUIRE(logits_bits == 16 || logits_bits == 32, KIVI_EINVAL, "kivi_sample_rows: logits_bits=%d (16: fp16, 32: fp32)",
-                 logits_bits);
-    KIVI_REQUIRE(B >= 1 && B <= KIVI_SAMPLE_MAX_B, KIVI_EINVAL, "kivi_sample_rows: B=%d (1 <= B <= %d)", B, KIVI_SAMPLE_MAX_B);
-    KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "kivi_sample_rows: V=%d (1 <= V <= %d)", V, KIVI_SAMPLE_MAX_V);
-    KIVI_REQUIRE(row_stride >= V || B == 1, KIVI_EINVAL, "kivi_sample_rows: row_stride=%lld below V=%d", (long long)row_stride, V);
-    KIVI_REQUIRE(out_stride >= 1 || B == 1, KIVI_EINVAL, "kivi_sample_rows: out_stride=%lld", (long long)out_stride);
-    KIVI_REQUIRE(logits && rows && draw_index && out_tokens, KIVI_EINVAL, "kivi_sample_rows: null pointer");
+// The checks and the launch of the three row entries.  `name`: the entry, in front of every message; `required`: whether the
+// pointers this entry cannot do without -- beyond logits, rows, draw_index and out_tokens -- are there.  An entry without a table
+// or without constraint state passes null pointers and zero strides, which every check from the fourth on lets through.
+static int launch_rows(const char* name, bool required, const void* logits, int logits_bits, int64_t row_stride, int B, int V,
+                       const kivi_sample_row* rows, int64_t* draw_index, const kivi_sample_penalty* pen, uint16_t* seen,
+                       int64_t seen_stride, const kivi_sample_constraint* con, const uint32_t* allow, int64_t allow_stride,
+                       const kivi_sample_list_entry* list, int64_t list_stride, int64_t* out_tokens, int64_t out_stride,
+                       kivi_stream_t stream) {
+    KIVI_REQUIRE(logits_bits == 16 || logits_bits == 32, KIVI_EINVAL, "%s: logits_bits=%d (16: fp16, 32: fp32)", name, logits_bits);
+    KIVI_REQUIRE(B >= 1 && B <= KIVI_SAMPLE_MAX_B, KIVI_EINVAL, "%s: B=%d (1 <= B <= %d)", name, B, KIVI_SAMPLE_MAX_B);
+    KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "%s: V=%d (1 <= V <= %d)", name, V, KIVI_SAMPLE_MAX_V);
+    KIVI_REQUIRE(row_stride >= V || B == 1, KIVI_EINVAL, "%s: row_stride=%lld below V=%d", name, (long long)row_stride, V);
+    KIVI_REQUIRE(out_stride >= 1 || B == 1, KIVI_EINVAL, "%s: out_stride=%lld", name, (long long)out_stride);
+    KIVI_REQUIRE(logits && rows && draw_index && out_tokens && required, KIVI_EINVAL, "%s: null pointer", name);
+    KIVI_REQUIRE(!pen == !seen, KIVI_EINVAL, "%s: pen and seen have to be both given or both null", name);
+    KIVI_REQUIRE(!seen || seen_stride >= V, KIVI_EINVAL, "%s: seen_stride=%lld below V=%d", name, (long long)seen_stride, V);
+    KIVI_REQUIRE(!allow || allow_stride >= (V + 31) / 32, KIVI_EINVAL, "%s: allow_stride=%lld below ceil(V / 32)=%d", name,
+                 (long long)allow_stride, (V + 31) / 32);
+    KIVI_REQUIRE(list_stride >= 0 && list_stride <= KIVI_SAMPLE_MAX_LIST, KIVI_EINVAL, "%s: list_stride=%lld (0 <= list_stride <= %d)",
+                 name, (long long)list_stride, KIVI_SAMPLE_MAX_LIST);
     const int esz = logits_bits / 8;
     KIVI_REQUIRE((uintptr_t)logits % esz == 0 && (uintptr_t)rows % 8 == 0 && (uintptr_t)draw_index % 8 == 0 &&
                      (uintptr_t)out_tokens % 8 == 0,
-                 KIVI_EALIGN, "kivi_sample_rows: misaligned logits (%d-byte elements), rows, draw_index or out_tokens (8 bytes)", esz);
-    int BS = KIVI_WAVE;                              // as kivi_sample
-    while ((int64_t)BS * 1024 < V) BS <<= 1;
+                 KIVI_EALIGN, "%s: misaligned logits (%d-byte elements), rows, draw_index or out_tokens (8 bytes)", name, esz);
+    KIVI_REQUIRE((uintptr_t)pen % 4 == 0 && (uintptr_t)seen % 16 == 0 && (!seen || seen_stride % 8 == 0), KIVI_EALIGN,
+                 "%s: misaligned pen (4 bytes) or seen (16 bytes), or seen_stride=%lld not a multiple of 8", name, (long long)seen_stride);
+    KIVI_REQUIRE((uintptr_t)con % 8 == 0 && (uintptr_t)allow % 16 == 0 && (!allow || allow_stride % 4 == 0) && (uintptr_t)list % 8 == 0,
+                 KIVI_EALIGN, "%s: misaligned con or list (8 bytes) or allow (16 bytes), or allow_stride=%lld not a multiple of 4", name,
+                 (long long)allow_stride);
+    const int BS = bucket_size(V);
     const hipStream_t s = (hipStream_t)stream;
-    if (logits_bits == 16)
-        KIVI_LAUNCH(sample_rows_kernel<f16>, dim3(B), dim3(kThreads), s, (const f16*)logits, row_stride, V, BS, rows, draw_index,
-                    out_tokens, out_stride);
-    else
-        KIVI_LAUNCH(sample_rows_kernel<float>, dim3(B), dim3(kThreads), s, (const float*)logits, row_stride, V, BS, rows, draw_index,
-                    out_tokens, out_stride);
-    return kivi_launch_status("kivi_sample_rows");
+    const bool state = seen || con;                  // neither: the instantiation without their LDS arrays and record loads
+#define ROWS_LAUNCH(T, STATE)                                                                                                 \
+    KIVI_LAUNCH((sample_rows_kernel<T, STATE>), dim3(B), dim3(kThreads), s, (const T*)logits, row_stride, V, BS, rows, draw_index, pen, \
+                seen, seen_stride, con, allow, allow_stride, list, list_stride, out_tokens, out_stride)
+    if (logits_bits == 16) {
+        if (state) ROWS_LAUNCH(f16, true);
+        else ROWS_LAUNCH(f16, false);
+    } else {
+        if (state) ROWS_LAUNCH(float, true);
+        else ROWS_LAUNCH(float, false);
+    }
+#undef ROWS_LAUNCH
+    return kivi_launch_status(name);
+}
+
+extern "C" int kivi_sample_rows(const void* logits, int logits_bits, int64_t row_stride, int B, int V, const kivi_sample_row* rows,
+                                int64_t* draw_index, int64_t* out_tokens, int64_t out_stride, kivi_stream_t stream) {
+    return launch_rows("kivi_sample_rows", true, logits, logits_bits, row_stride, B, V, rows, draw_index, nullptr, nullptr, 0, nullptr,
+                       nullptr, 0, nullptr, 0, out_tokens, out_stride, stream);
 }
 
 extern "C" int kivi_sample_rows_pen(const void* logits, int logits_bits, int64_t row_stride, int B, int V, const kivi_sample_row* rows,
                                     int64_t* draw_index, const kivi_sample_penalty* pen, uint16_t* seen, int64_t seen_stride,
                                     int64_t* out_tokens, int64_t out_stride, kivi_stream_t stream) {
-    KIVI_REQUIRE(logits_bits == 16 || logits_bits == 32, KIVI_EINVAL, "kivi_sample_rows_pen: logits_bits=%d (16: fp16, 32: fp32)",
-                 logits_bits);
-    KIVI_REQUIRE(B >= 1 && B <= KIVI_SAMPLE_MAX_B, KIVI_EINVAL, "kivi_sample_rows_pen: B=%d (1 <= B <= %d)", B, KIVI_SAMPLE_MAX_B);
-    KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "kivi_sample_rows_pen: V=%d (1 <= V <= %d)", V, KIVI_SAMPLE_MAX_V);
-    KIVI_REQUIRE(row_stride >= V || B == 1, KIVI_EINVAL, "kivi_sample_rows_pen: row_stride=%lld below V=%d", (long long)row_stride, V);
-    KIVI_REQUIRE(out_stride >= 1 || B == 1, KIVI_EINVAL, "kivi_sample_rows_pen: out_stride=%lld", (long long)out_stride);
-    KIVI_REQUIRE(logits && rows && draw_index && out_tokens && pen && seen, KIVI_EINVAL, "kivi_sample_rows_pen: null pointer");
-    KIVI_REQUIRE(seen_stride >= V, KIVI_EINVAL, "kivi_sample_rows_pen: seen_stride=%lld below V=%d", (long long)seen_stride, V);
-    const int esz = logits_bits / 8;
-    KIVI_REQUIRE((uintptr_t)logits % esz == 0 && (uintptr_t)rows % 8 == 0 && (uintptr_t)draw_index % 8 == 0 &&
-                     (uintptr_t)out_tokens % 8 == 0,
-                 KIVI_EALIGN, "kivi_sample_rows_pen: misaligned logits (%d-byte elements), rows, draw_index or out_tokens (8 bytes)",
-                 esz);
-    KIVI_REQUIRE((uintptr_t)pen % 4 == 0 && (uintptr_t)seen % 16 == 0 && seen_stride % 8 == 0, KIVI_EALIGN,
-                 "kivi_sample_rows_pen: misaligned pen (4 bytes) or seen (16 bytes), or seen_stride=%lld not a multiple of 8",
-                 (long long)seen_stride);
-    int BS = KIVI_WAVE;                              // as kivi_sample
-    while ((int64_t)BS * 1024 < V) BS <<= 1;
-    const hipStream_t s = (hipStream_t)stream;
-    if (logits_bits == 16)
-        KIVI_LAUNCH(sample_rows_pen_kernel<f16>, dim3(B), dim3(kThreads), s, (const f16*)logits, row_stride, V, BS, rows, draw_index,
-                    pen, seen, seen_stride, out_tokens, out_stride);
-    else
-        KIVI_LAUNCH(sample_rows_pen_kernel<float>, dim3(B), dim3(kThreads), s, (const float*)logits, row_stride, V, BS, rows,
-                    draw_index, pen, seen, seen_stride, out_tokens, out_stride);
-    return kivi_launch_status("kivi_sample_rows_pen");
+    return launch_rows("kivi_sample_rows_pen", pen && seen, logits, logits_bits, row_stride, B, V, rows, draw_index, pen, seen,
+                       seen_stride, nullptr, nullptr, 0, nullptr, 0, out_tokens, out_stride, stream);
+}
+
+extern "C" int kivi_sample_rows_con(const void* logits, int logits_bits, int64_t row_stride, int B, int V, const kivi_sample_row* rows,
+                                    int64_t* draw_index, const kivi_sample_penalty* pen, uint16_t* seen, int64_t seen_stride,
+                                    const kivi_sample_constraint* con, const uint32_t* allow, int64_t allow_stride,
+                                    const kivi_sample_list_entry* list, int64_t list_stride, int64_t* out_tokens, int64_t out_stride,
+                                    kivi_stream_t stream) {
+    return launch_rows("kivi_sample_rows_con", con != nullptr, logits, logits_bits, row_stride, B, V, rows, draw_index, pen, seen,
+                       seen_stride, con, allow, allow_stride, list, list_stride, out_tokens, out_stride, stream);
 }
 
 extern "C" int kivi_seen_mark(uint16_t* seen, int64_t seen_stride, int V, const int32_t* rows, int n, const int64_t* tokens,
@@ -738,48 +703,6 @@ extern "C" int kivi_seen_mark(uint16_t* seen, int64_t seen_stride, int V, const 
     KIVI_LAUNCH(seen_mark_kernel, dim3(n), dim3(256), (hipStream_t)stream, seen, seen_stride, V, rows, tokens, tok_row_stride,
                 mark ? T : 0, lead, mark ? flags : KIVI_SEEN_CLEAR);
     return kivi_launch_status("kivi_seen_mark");
-}
-
-extern "C" int kivi_sample_rows_con(const void* logits, int logits_bits, int64_t row_stride, int B, int V, const kivi_sample_row* rows,
-                                    int64_t* draw_index, const kivi_sample_penalty* pen, uint16_t* seen, int64_t seen_stride,
-                                    const kivi_sample_constraint* con, const uint32_t* allow, int64_t allow_stride,
-                                    const kivi_sample_list_entry* list, int64_t list_stride, int64_t* out_tokens, int64_t out_stride,
-                                    kivi_stream_t stream) {
-    KIVI_REQUIRE(logits_bits == 16 || logits_bits == 32, KIVI_EINVAL, "kivi_sample_rows_con: logits_bits=%d (16: fp16, 32: fp32)",
-                 logits_bits);
-    KIVI_REQUIRE(B >= 1 && B <= KIVI_SAMPLE_MAX_B, KIVI_EINVAL, "kivi_sample_rows_con: B=%d (1 <= B <= %d)", B, KIVI_SAMPLE_MAX_B);
-    KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "kivi_sample_rows_con: V=%d (1 <= V <= %d)", V, KIVI_SAMPLE_MAX_V);
-    KIVI_REQUIRE(row_stride >= V || B == 1, KIVI_EINVAL, "kivi_sample_rows_con: row_stride=%lld below V=%d", (long long)row_stride, V);
-    KIVI_REQUIRE(out_stride >= 1 || B == 1, KIVI_EINVAL, "kivi_sample_rows_con: out_stride=%lld", (long long)out_stride);
-    KIVI_REQUIRE(logits && rows && draw_index && out_tokens && con, KIVI_EINVAL, "kivi_sample_rows_con: null pointer");
-    KIVI_REQUIRE(!pen == !seen, KIVI_EINVAL, "kivi_sample_rows_con: pen and seen have to be both given or both null");
-    KIVI_REQUIRE(!seen || seen_stride >= V, KIVI_EINVAL, "kivi_sample_rows_con: seen_stride=%lld below V=%d", (long long)seen_stride, V);
-    KIVI_REQUIRE(!allow || allow_stride >= (V + 31) / 32, KIVI_EINVAL, "kivi_sample_rows_con: allow_stride=%lld below ceil(V / 32)=%d",
-                 (long long)allow_stride, (V + 31) / 32);
-    KIVI_REQUIRE(list_stride >= 0 && list_stride <= KIVI_SAMPLE_MAX_LIST, KIVI_EINVAL,
-                 "kivi_sample_rows_con: list_stride=%lld (0 <= list_stride <= %d)", (long long)list_stride, KIVI_SAMPLE_MAX_LIST);
-    const int esz = logits_bits / 8;
-    KIVI_REQUIRE((uintptr_t)logits % esz == 0 && (uintptr_t)rows % 8 == 0 && (uintptr_t)draw_index % 8 == 0 &&
-                     (uintptr_t)out_tokens % 8 == 0,
-                 KIVI_EALIGN, "kivi_sample_rows_con: misaligned logits (%d-byte elements), rows, draw_index or out_tokens (8 bytes)",
-                 esz);
-    KIVI_REQUIRE((uintptr_t)pen % 4 == 0 && (uintptr_t)seen % 16 == 0 && (!seen || seen_stride % 8 == 0), KIVI_EALIGN,
-                 "kivi_sample_rows_con: misaligned pen (4 bytes) or seen (16 bytes), or seen_stride=%lld not a multiple of 8",
-                 (long long)seen_stride);
-    KIVI_REQUIRE((uintptr_t)con % 8 == 0 && (uintptr_t)allow % 16 == 0 && (!allow || allow_stride % 4 == 0) && (uintptr_t)list % 8 == 0,
-                 KIVI_EALIGN,
-                 "kivi_sample_rows_con: misaligned con or list (8 bytes) or allow (16 bytes), or allow_stride=%lld not a multiple of 4",
-                 (long long)allow_stride);
-    int BS;                                          // the bucket of kivi_sample: a power of two, at most 1024 buckets per row
-    for (BS = KIVI_WAVE; (int64_t)BS * 1024 < V;) BS <<= 1;
-    const hipStream_t s = (hipStream_t)stream;
-    if (logits_bits == 16)
-        KIVI_LAUNCH(sample_rows_con_kernel<f16>, dim3(B), dim3(kThreads), s, (const f16*)logits, row_stride, V, BS, rows, draw_index,
-                    pen, seen, seen_stride, con, allow, allow_stride, list, list_stride, out_tokens, out_stride);
-    else
-        KIVI_LAUNCH(sample_rows_con_kernel<float>, dim3(B), dim3(kThreads), s, (const float*)logits, row_stride, V, BS, rows,
-                    draw_index, pen, seen, seen_stride, con, allow, allow_stride, list, list_stride, out_tokens, out_stride);
-    return kivi_launch_status("kivi_sample_rows_con");
 }
 
 extern "C" int kivi_allow_mark(uint32_t* allow, int64_t allow_stride, int V, const int32_t* rows, int n, const int64_t* tokens,

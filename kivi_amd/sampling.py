@@ -303,6 +303,11 @@ def _penalty_record(p: SamplingParams) -> torch.Tensor:
     return torch.tensor(np.frombuffer(bytes(rec), dtype=np.float32))
 
 
+def _upload(dst: torch.Tensor, host: torch.Tensor) -> None:
+    """A CPU tensor into `dst` by an asynchronous copy on the current stream (from pinned memory when `dst` is on a device)."""
+    dst.copy_(host.pin_memory() if dst.is_cuda else host, non_blocking=True)
+
+
 def _token_rows(tokens, device) -> Optional[torch.Tensor]:
     """Token ids (a sequence, a 1-D or a 2-D tensor) as (n, T) int64 on `device` with unit inner stride; None when there are none."""
     if tokens is None:
@@ -464,8 +469,18 @@ class RowSampler:
         return _constraint_record(CONSTRAINT_MASK if c["mask"] else 0, len(c["list"]), c["until"])
 
     def _write_constraint(self, b: int) -> None:
-        rec = self._con_record(self._con[b])
-        self.constraint[b].copy_(rec.pin_memory() if self.constraint.is_cuda else rec, non_blocking=True)
+        _upload(self.constraint[b], self._con_record(self._con[b]))
+
+    def _bind_constraint(self, b: int, allowed_ids=False) -> None:
+        """Row b's constraint state from self._con[b], on the current stream: its list words, its mask row -- the ids it allows (None:
+        every token; False: the row stays as it is) -- and its record."""
+        entries = self._con[b]["list"]
+        if entries:
+            _upload(self.bias_list[b, : len(entries)], _list_words(entries))
+        if allowed_ids is not False:
+            _upload(self.allowed[b], torch.full((self.allowed.shape[1],), -1, dtype=torch.int32) if allowed_ids is None else
+                    allow_bitmask(allowed_ids, self.vocab_size))
+        self._write_constraint(b)
 
     def _require_constraints(self, what: str) -> None:
         if self._con is None:
@@ -481,12 +496,8 @@ class RowSampler:
             raise ValueError(f"{len(suppress)} lists of suppressed ids for {self.B} rows")
         for b, (p, ids) in enumerate(zip(self.params, suppress)):
             if p.min_new_tokens > 0:
-                entries = constraint_list(p, [int(t) for t in ids])
-                self._con[b]["list"] = entries
-                if entries:
-                    words = _list_words(entries)
-                    self.bias_list[b, : len(entries)].copy_(words.pin_memory() if self.bias_list.is_cuda else words, non_blocking=True)
-                self._write_constraint(b)
+                self._con[b]["list"] = constraint_list(p, [int(t) for t in ids])
+                self._bind_constraint(b)
 
     def set_allowed(self, b: int, allowed=None) -> None:
         """Row b's allow mask, on the current stream (ordered after the calls already enqueued there); nothing is captured again.
@@ -512,8 +523,7 @@ class RowSampler:
                 torch.tensor([b], dtype=torch.int32).to(allowed.device)), 1, _lib.ptr(ids) if ids.numel() else None, ids.shape[1],
                 ids.shape[1], None, ALLOW_NONE | ALLOW_SET, _lib.stream_ptr(self.allowed)), "kivi_allow_mark")
         else:
-            bits = allow_bitmask(allowed.tolist() if torch.is_tensor(allowed) else allowed, self.vocab_size)
-            row.copy_(bits.pin_memory() if row.is_cuda else bits, non_blocking=True)
+            _upload(row, allow_bitmask(allowed.tolist() if torch.is_tensor(allowed) else allowed, self.vocab_size))
         if self._con[b]["mask"] != (allowed is not None):
             self._con[b]["mask"] = allowed is not None
             self._write_constraint(b)
@@ -605,27 +615,17 @@ class RowSampler:
             entries = constraint_list(params, () if suppress is None else
                                       [int(t) for t in (suppress.tolist() if torch.is_tensor(suppress) else suppress)])
         p = self._bind(params)
-        rec = _record(p, stream)
-        if self.records.is_cuda:
-            rec = rec.pin_memory()
-        self.records[b].copy_(rec, non_blocking=True)
+        _upload(self.records[b], _record(p, stream))
         self.draw_index[b: b + 1].fill_(draw_index)
         if self.seen is not None:
-            pen = _penalty_record(p)
-            self.penalties[b].copy_(pen.pin_memory() if self.penalties.is_cuda else pen, non_blocking=True)
+            _upload(self.penalties[b], _penalty_record(p))
             self._mark(SEEN_CLEAR | SEEN_PROMPT, prompt, rows=[b])
             self._mark(SEEN_OUTPUT, generated, rows=[b])
         if self._con is not None:
             done = 0 if generated is None else int(torch.as_tensor(generated).numel())
             self._con[b] = dict(mask=p.allowed_token_ids is not None, list=entries, min_new=p.min_new_tokens,
                                 until=max(draw_index - done, 0) + p.min_new_tokens)
-            if entries:
-                words = _list_words(entries)
-                self.bias_list[b, : len(entries)].copy_(words.pin_memory() if self.bias_list.is_cuda else words, non_blocking=True)
-            bits = torch.full((self.allowed.shape[1],), -1, dtype=torch.int32) if p.allowed_token_ids is None else \
-                allow_bitmask(p.allowed_token_ids, self.vocab_size)
-            self.allowed[b].copy_(bits.pin_memory() if self.allowed.is_cuda else bits, non_blocking=True)
-            self._write_constraint(b)
+            self._bind_constraint(b, p.allowed_token_ids)
         self.params[b], self.streams[b] = p, stream
 
     def reset(self) -> None:
@@ -664,29 +664,26 @@ class RowSampler:
         when the sampler has a history table -- kivi_sample_rows_pen, which also counts the tokens in the table, or -- exactly when
         it has constraint state -- kivi_sample_rows_con, which does that too."""
         logits, out = _call_args(logits, out, self)
-        B, V = logits.shape
-        lib = _lib.load()
-        bits, out_stride = 16 if logits.dtype == torch.float16 else 32, out.stride(0) if out.dim() else 1
-        if self.seen is None:
-            _lib.check(lib.kivi_sample_rows(_lib.ptr(logits), bits, logits.stride(0), B, V, _lib.ptr(self.records),
-                                            _lib.ptr(self.draw_index), _lib.ptr(out), out_stride, _lib.stream_ptr(logits)),
-                       "kivi_sample_rows")
-            return out
-        if V > self.vocab_size:
-            raise ValueError(f"logits of {V} tokens do not fit the history table of this RowSampler (vocab_size={self.vocab_size})")
-        if self._con is not None:
-            _lib.check(lib.kivi_sample_rows_con(_lib.ptr(logits), bits, logits.stride(0), B, V, _lib.ptr(self.records),
-                                                _lib.ptr(self.draw_index), _lib.ptr(self.penalties), _lib.ptr(self.seen),
-                                                self.seen.stride(0), _lib.ptr(self.constraint), _lib.ptr(self.allowed),
-                                                self.allowed.stride(0), _lib.ptr(self.bias_list), self.bias_list.stride(0) // 2,
-                                                _lib.ptr(out), out_stride, _lib.stream_ptr(logits)),
-                       "kivi_sample_rows_con")
-            return out
-        _lib.check(lib.kivi_sample_rows_pen(_lib.ptr(logits), bits, logits.stride(0), B, V, _lib.ptr(self.records),
-                                            _lib.ptr(self.draw_index), _lib.ptr(self.penalties), _lib.ptr(self.seen),
-                                            self.seen.stride(0), _lib.ptr(out), out_stride, _lib.stream_ptr(logits)),
-                   "kivi_sample_rows_pen")
+        if self.seen is not None and logits.shape[1] > self.vocab_size:
+            raise ValueError(f"logits of {logits.shape[1]} tokens do not fit the history table of this RowSampler "
+                             f"(vocab_size={self.vocab_size})")
+        name, args = self.entry(logits, out)
+        _lib.check(getattr(_lib.load(), name)(*args), name)
         return out
+
+    def entry(self, logits: torch.Tensor, out: torch.Tensor):
+        """(the name of the entry a call goes through, its arguments) for checked `logits` (B, V) and `out`, on the current stream:
+        the common arguments, then the penalty records and the history table when there is one, then the constraint records, allow
+        masks and lists when there are any."""
+        B, V = logits.shape
+        name, args = "kivi_sample_rows", (_lib.ptr(logits), 16 if logits.dtype == torch.float16 else 32, logits.stride(0), B, V,
+                                          _lib.ptr(self.records), _lib.ptr(self.draw_index))
+        if self.seen is not None:
+            name, args = "kivi_sample_rows_pen", args + (_lib.ptr(self.penalties), _lib.ptr(self.seen), self.seen.stride(0))
+        if self._con is not None:
+            name, args = "kivi_sample_rows_con", args + (_lib.ptr(self.constraint), _lib.ptr(self.allowed), self.allowed.stride(0),
+                                                         _lib.ptr(self.bias_list), self.bias_list.stride(0) // 2)
+        return name, args + (_lib.ptr(out), out.stride(0) if out.dim() else 1, _lib.stream_ptr(logits))
 
 
 # ------------------------------------------------------------------ CPU restatement (tests, tools)

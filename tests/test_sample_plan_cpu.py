@@ -57,9 +57,13 @@ def test_plan_is_consistent(V):
 
 
 def test_the_kernel_source_states_the_same_geometry():
-    """The three entries size the bucket with the same loop, and the row body derives buckets and segments as plan() does."""
+    """Every entry sizes the bucket with the one loop of bucket_size() -- kivi_sample itself, the three row entries through their one
+    launch function -- and the row body derives buckets and segments as plan() does."""
     src = open(os.path.join(ROOT, "kivi_amd", "csrc", "kivi_sample.hip")).read()
-    assert len(re.findall(r"int BS = KIVI_WAVE;[^\n]*\n\s*while \(\(int64_t\)BS \* 1024 < V\) BS <<= 1;", src)) == 3
+    assert len(re.findall(r"int BS = KIVI_WAVE;[^\n]*\n\s*while \(\(int64_t\)BS \* 1024 < V\) BS <<= 1;", src)) == 1
+    assert len(re.findall(r"BS\s*<<=", src)) == 1 and len(re.findall(r"const int BS = bucket_size\(V\);", src)) == 2
+    for entry in ("kivi_sample_rows", "kivi_sample_rows_pen", "kivi_sample_rows_con"):
+        assert re.search(r'extern "C" int %s\([^{]*\{\s*return launch_rows\("%s",' % (entry, entry), src)
     assert "constexpr int kThreads = 1024;" in src and "constexpr int kWaves = kThreads / KIVI_WAVE;" in src
     assert "const int nbk = (V + BS - 1) / BS, bpw = (nbk + kWaves - 1) / kWaves;" in src
     assert "const int bk0 = min(nbk, wave * bpw), bk1 = min(nbk, (wave + 1) * bpw);" in src

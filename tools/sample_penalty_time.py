@@ -18,7 +18,6 @@ figures per form, medians (minimums) over the rounds: the CALL time (eager, Pyth
 `--parent-lib`: a libkivi_hip.so built from the parent commit; kivi_sample_rows is then timed through both libraries by the same
 raw ctypes call on the same buffers, alternating, to show that (a) is the instantiation it was."""
 import argparse
-import ctypes
 import os
 import statistics
 import sys
@@ -29,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from sample_rows_time import _events, _graph  # noqa: E402
+from sample_rows_time import _events, _graph, other_lib, raw_call  # noqa: E402
 
 SHAPES = [(32, 32000), (64, 128256)]
 PEN = dict(repetition_penalty=1.3, presence_penalty=0.6, frequency_penalty=0.25)
@@ -49,13 +48,6 @@ def _torch_form(logits, plain, hist_ids, counts, out):
         plain(x, out=out)
         counts.scatter_add_(1, out, ones)
     return fn
-
-
-def _raw_rows(lib, logits, rs, out):
-    from kivi_amd import _lib
-    B, V = logits.shape
-    args = (_lib.ptr(logits), 16, logits.stride(0), B, V, _lib.ptr(rs.records), _lib.ptr(rs.draw_index), _lib.ptr(out), 1)
-    return lambda: lib.kivi_sample_rows(*args, _lib.stream_ptr(logits))
 
 
 def rows(rounds, iters, shapes, parent_lib):
@@ -84,11 +76,10 @@ def rows(rounds, iters, shapes, parent_lib):
                ("(c) rows_pen, penalised", lambda: pen(logits, out=out)),
                ("(d) torch penalties + rows", _torch_form(logits, under, hist_ids, counts, out))]
         if parent_lib:
-            other = ctypes.CDLL(parent_lib)
-            other.kivi_sample_rows.restype, other.kivi_sample_rows.argtypes = _lib.SIGNATURES["kivi_sample_rows"]
+            this, other = _lib.load(), other_lib(parent_lib)
             raw = RowSampler(SamplingParams(**base), "cuda", streams=streams)
-            fns += [("(a) raw call, this library", _raw_rows(_lib.load(), logits, raw, out)),
-                    ("(a) raw call, parent library", _raw_rows(other, logits, raw, out))]
+            fns += [("(a) raw call, this library", lambda: raw_call(this, raw, logits, out)),
+                    ("(a) raw call, parent library", lambda: raw_call(other, raw, logits, out))]
         saved = [t.clone() for t in (neutral.seen, pen.seen, counts)]
 
         def restore():

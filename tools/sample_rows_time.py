@@ -49,6 +49,22 @@ def _graph(fn, iters):
     return g.replay
 
 
+def other_lib(path):
+    """A second libkivi_hip.so (e.g. the parent commit's) with the signatures of the three row entries."""
+    import ctypes
+    from kivi_amd import _lib
+    lib = ctypes.CDLL(path)
+    for name in ("kivi_sample_rows", "kivi_sample_rows_pen", "kivi_sample_rows_con"):
+        getattr(lib, name).restype, getattr(lib, name).argtypes = _lib.SIGNATURES[name]
+    return lib
+
+
+def raw_call(lib, rs, logits, out):
+    """What RowSampler `rs` calls for `logits` and `out` -- its entry, its arguments, the current stream -- through `lib`, unchecked."""
+    name, args = rs.entry(logits, out)
+    return getattr(lib, name)(*args)
+
+
 def rows(rounds, iters, shapes):
     from kivi_amd.sampling import RowSampler, Sampler, SamplingParams
     lines = []
