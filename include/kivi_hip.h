@@ -982,6 +982,29 @@ int kivi_prefill_attention(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_
                            int64_t k_st, const void* v, int64_t v_sb, int64_t v_sh, int64_t v_st, void* out, int64_t o_sb,
                            int64_t o_sh, int64_t o_st, const int32_t* lead, int B, int nh, int nh_kv, int T, int D, float scale,
                            kivi_stream_t stream);
+/*
+ * kivi_qk_rope: a layer's q and k projections made ready for the attention in one launch -- the optional
+ * per-head RMSNorm (HF's Qwen3RMSNorm), the rotary embedding, and the placement into the head-major layout, the nh / nh_kv = R query
+ * heads of every kv head padded to Rp >= R by zero heads (a group of R heads then runs as the matrix-pipe layout's ratio Rp).
+ *   q_in   (B, Q, nh, D), k_in (B, Q, nh_kv, D) fp16 by their strides (batch, token, head) in elements, channel stride 1: the views of
+ *          the projections' outputs go in as they are
+ *   cos, sin   (Bc, Q, D) fp16 tables, batch stride cs_sb (0: one table for every row) and token stride cs_st in elements
+ *   q_weight, k_weight   D fp16 each, or null: no head norm;  eps: its epsilon
+ *   q_out  (B, nh_kv * Rp, Q, D), k_out (B, nh_kv, Q, D) fp16, contiguous.  Query head kv * R + r lands at kv * Rp + r; the heads
+ *          kv * Rp + [R, Rp) are written as zeros on every call.  Every element of both outputs is written once, nothing else is.
+ * Arithmetic, per head x (D channels): with a weight, y = fp16(w * fp16(x * rsqrt(mean(x^2) + eps))), the inner value evaluated in
+ * fp64 and rounded once (HF evaluates it in fp32: about one element in a thousand then sits an fp16 ulp off this, the formula's
+ * own value), else y = x; then out = fp16(fp16(y * cos) + fp16(rot(y) * sin)), rot(y)[i] = -y[i + 64], rot(y)[i + 64] = y[i] -- each
+ * product and the sum rounded to fp16 on its own, which is what torch computes for `y * cos + rotate_half(y) * sin` on fp16 tensors,
+ * bit for bit.  One wave per (row, token, head).
+ * KIVI_EINVAL (nothing enqueued) for D != 128; B, Q, nh or nh_kv < 1; nh not a multiple of nh_kv; Rp outside [R, 64]; a null q_in /
+ * k_in / cos / sin / q_out / k_out; a negative stride; eps negative or not finite; 2^31 blocks or more.  KIVI_EALIGN for a pointer
+ * off 2 bytes.
+ */
+int kivi_qk_rope(const void* q_in, int64_t q_sb, int64_t q_st, int64_t q_sh, const void* k_in, int64_t k_sb, int64_t k_st,
+                 int64_t k_sh, const void* cos, const void* sin, int64_t cs_sb, int64_t cs_st, const void* q_weight,
+                 const void* k_weight, float eps, void* q_out, void* k_out, int B, int Q, int nh, int nh_kv, int Rp, int D,
+                 kivi_stream_t stream);
 /* geometry class of a step (-1: bad arguments): the super-block counts of both stores and whether the step flushes a value; the
  * launch plan (one launch / S slices / two launches) is a function of the class and of constants of the call (shape, bits, flags) */
 int64_t kivi_mf_step_key(const kivi_mf_step* step, int B, int nh, int nh_kv, int residual_length, int flags);

@@ -210,6 +210,8 @@ SIGNATURES = {
     "kivi_token_top_logprobs": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "kivi_prefill_attention": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
                                       _i32, _i32, _i32, _i32, _i32, ctypes.c_float, _vp]),
+    "kivi_qk_rope": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, ctypes.c_float, _vp, _vp,
+                            _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "kivi_mf_step_key": (_i64, [ctypes.POINTER(MfStep), _i32, _i32, _i32, _i32, _i32]),
     "kivi_mf_step_advance": (_i32, [ctypes.POINTER(MfStep), _i32, _i64]),
     "kivi_mf_step_upload": (_i32, [ctypes.POINTER(MfStep), _vp, _vp]),

@@ -18,14 +18,15 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _tuning
+from . import _lib, _tuning
 from . import generation as _generation
 from . import prefill as _prefill
+from . import qkrope as _qkrope
 from .cache import KiviCacheTuple, KiviConfig, KiviLayerCache, KiviPerformanceWarning  # noqa: F401
-from .cache_mf import KiviLayerCacheMF, make_layer_cache, supported as _mf_supported
+from .cache_mf import KiviLayerCacheMF, make_layer_cache, padded_heads as _padded_heads, supported as _mf_supported
 
 __all__ = ["kivi_attention_decode", "kivi_attention_prefill", "LlamaAttention_KIVI", "LlamaFlashAttention_KIVI",
-           "MistralAttention_KIVI", "MistralFlashAttention_KIVI",
+           "MistralAttention_KIVI", "MistralFlashAttention_KIVI", "QwenAttention_KIVI",
            "KiviConfig", "KiviLayerCache", "KiviLayerCacheMF", "make_layer_cache"]
 
 
@@ -188,32 +189,75 @@ class LlamaAttention_KIVI(nn.Module):
         self.v_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=bias)
         self.o_proj = nn.Linear(self.num_heads * self.head_dim, self.hidden_size, bias=bias)
         self.register_buffer("inv_freq", _rope_inv_freq(config, self.head_dim, self.rope_theta), persistent=False)
+        # config.kivi_qk_kernel (off by default): q / k are prepared by one kivi_qk_rope launch, and a query-group
+        # ratio the matrix-pipe layout does not serve runs on it padded: `cache_heads` query heads, nh_kv * the padded ratio
+        self.qk_kernel = bool(getattr(config, "kivi_qk_kernel", False))
+        self.cache_heads = self.num_heads
+        if self.qk_kernel:
+            self.cache_heads = _padded_heads(self.kivi, self.head_dim, self.num_heads, self.num_key_value_heads) or self.num_heads
+        self.q_norm = self.k_norm = None            # the per-head RMSNorm of q and k before RoPE (QwenAttention_KIVI)
 
     def _rope(self, q, k, position_ids):
         cos, sin = (x[:, None] for x in rope_cos_sin(self.inv_freq, position_ids, q.dtype))   # (B, 1, T, D)
         return q * cos + _rotate_half(q) * sin, k * cos + _rotate_half(k) * sin
 
+    def _step_cos_sin(self, device, dtype, past_len: int, q_len: int):
+        """cos / sin (1, 1, q_len, D) of consecutive positions from past_len on: the same for every layer of a step, so kept."""
+        key = (device, dtype, self.head_dim, self.rope_theta, repr(getattr(self.config, "rope_scaling", None)), past_len, q_len)
+        cs = _ROPE_CACHE.get(key)
+        if cs is None:
+            pos = torch.arange(past_len, past_len + q_len, device=device)[None]
+            cs = tuple(x[:, None] for x in rope_cos_sin(self.inv_freq, pos, dtype))
+            _ROPE_CACHE.clear()
+            _ROPE_CACHE[key] = cs
+        return cs
+
+    def _prepared_qkv(self, hidden_states, position_ids, past_len: int, heads: int):
+        """q, k, v of config.kivi_qk_kernel and of the classes with a head norm: head norm, RoPE and the
+        head-major placement in one kivi_qk_rope launch, the query groups padded to `heads` query heads in all -- or, with the
+        option off or outside what the kernel serves, the torch chain of the same formula (which cannot pad)."""
+        bsz, q_len, _ = hidden_states.size()
+        q_in = self.q_proj(hidden_states).view(bsz, q_len, self.num_heads, self.head_dim)
+        k_in = self.k_proj(hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
+        v = self.v_proj(hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim).transpose(1, 2)
+        if position_ids is None:
+            cos, sin = (x[:, 0] for x in self._step_cos_sin(hidden_states.device, q_in.dtype, past_len, q_len))
+        else:
+            cos, sin = rope_cos_sin(self.inv_freq, position_ids, q_in.dtype)                    # (B, T, D)
+        return self.prepare_qk(q_in, k_in, cos, sin, heads) + (v,)
+
+    def prepare_qk(self, q_in, k_in, cos, sin, heads: int, q_out=None, k_out=None):
+        """q_in (B, Q, nh, D), k_in (B, Q, nh_kv, D), cos / sin (1 or B, Q, D) -> q (B, heads, Q, D), k (B, nh_kv, Q, D), in
+        `q_out` / `k_out` when given (the static buffers of a captured step)."""
+        qw, kw, eps = (None, None, 0.0) if self.q_norm is None else (self.q_norm.weight, self.k_norm.weight, self.q_norm.eps)
+        if self.qk_kernel and _qkrope.usable(q_in, self.head_dim):
+            return _qkrope.qk_rope(q_in, k_in, cos, sin, heads // self.num_key_value_heads, qw, kw, eps, q_out, k_out)
+        if heads != self.num_heads:
+            raise _lib.KiviHipError("padded query groups need kivi_qk_rope: fp16 tensors on the GPU")
+        q, k = _qkrope.qk_rope_torch(q_in, k_in, cos, sin, qw, kw, eps)
+        return (q, k) if q_out is None else (q_out.copy_(q), k_out.copy_(k))
+
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 position_ids: Optional[torch.LongTensor] = None, past_key_value=None, output_attentions: bool = False,
                 use_cache: bool = False, **kwargs) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[tuple]]:
         bsz, q_len, _ = hidden_states.size()
-        q = self.q_proj(hidden_states).view(bsz, q_len, self.num_heads, self.head_dim).transpose(1, 2)
-        k = self.k_proj(hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim).transpose(1, 2)
-        v = self.v_proj(hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim).transpose(1, 2)
         past_len = 0 if past_key_value is None else int(past_key_value[-1])
-        if position_ids is None:   # consecutive positions: cos / sin are the same for every layer of this step
-            key = (hidden_states.device, q.dtype, self.head_dim, self.rope_theta, repr(getattr(self.config, "rope_scaling", None)),
-                   past_len, q_len)
-            cs = _ROPE_CACHE.get(key)
-            if cs is None:
-                pos = torch.arange(past_len, past_len + q_len, device=hidden_states.device)[None]
-                cs = tuple(x[:, None] for x in rope_cos_sin(self.inv_freq, pos, q.dtype))
-                _ROPE_CACHE.clear()
-                _ROPE_CACHE[key] = cs
-            cos, sin = cs
-            q, k = q * cos + _rotate_half(q) * sin, k * cos + _rotate_half(k) * sin
+        if self.qk_kernel or self.q_norm is not None:
+            heads = self.num_heads                  # the prompt pass launches nothing over the cache with q: no pad heads
+            if isinstance(past_key_value, KiviCacheTuple):      # over a cache: as many query heads as it was built for
+                heads = getattr(past_key_value.layer, "nh", self.num_heads)
+            elif past_key_value is not None:                    # a plain tuple: the cache made of it below
+                heads = self.cache_heads
+            q, k, v = self._prepared_qkv(hidden_states, position_ids, past_len, heads)
         else:
-            q, k = self._rope(q, k, position_ids)
+            q = self.q_proj(hidden_states).view(bsz, q_len, self.num_heads, self.head_dim).transpose(1, 2)
+            k = self.k_proj(hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim).transpose(1, 2)
+            v = self.v_proj(hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim).transpose(1, 2)
+            if position_ids is None:   # consecutive positions: cos / sin are the same for every layer of this step
+                cos, sin = self._step_cos_sin(hidden_states.device, q.dtype, past_len, q_len)
+                q, k = q * cos + _rotate_half(q) * sin, k * cos + _rotate_half(k) * sin
+            else:
+                q, k = self._rope(q, k, position_ids)
 
         if past_key_value is not None:
             if isinstance(past_key_value, KiviCacheTuple):
@@ -225,8 +269,8 @@ class LlamaAttention_KIVI(nn.Module):
                         f"stale KIVI past_key_value: the tuple was issued at kv length {past_len}, its cache has since "
                         f"advanced to {layer.kv_seq_len}. In-place cache tuples are single-use; clone the cache "
                         f"(KiviLayerCache.clone()) to continue one prefix twice.")
-            elif _mf_supported(self.kivi, self.head_dim, self.num_heads, self.num_key_value_heads):
-                layer = KiviLayerCacheMF.from_tuple(self.kivi, past_key_value, self._capacity(past_len + q_len), self.num_heads)
+            elif _mf_supported(self.kivi, self.head_dim, self.cache_heads, self.num_key_value_heads):
+                layer = KiviLayerCacheMF.from_tuple(self.kivi, past_key_value, self._capacity(past_len + q_len), self.cache_heads)
             else:  # a plain reference-style tuple: adopt it once
                 layer = KiviLayerCache.from_tuple(self.kivi, past_key_value, self._capacity(past_len + q_len))
             if isinstance(attention_mask, _generation.DecodeLead):   # config.kivi_decode_lead: the key row travels with its lead
@@ -240,7 +284,7 @@ class LlamaAttention_KIVI(nn.Module):
                 attn_output = kivi_attention_decode(q, k, v, layer, attention_mask)
         else:
             layer = make_layer_cache(self.kivi, bsz, self.num_key_value_heads, self.head_dim, self._capacity(q_len),
-                                     hidden_states.device, q.dtype, num_heads=self.num_heads)
+                                     hidden_states.device, q.dtype, num_heads=self.cache_heads)
             mask = attention_mask if self._prefill_uses_mask else None
             if isinstance(attention_mask, _prefill.PromptLead):
                 attn_output = kivi_attention_prefill(q, k, v, layer, None, lead=attention_mask.lead, kernel=True)
@@ -249,7 +293,10 @@ class LlamaAttention_KIVI(nn.Module):
             else:                                          # the option is off: the call as it always was
                 attn_output = kivi_attention_prefill(q, k, v, layer, mask)
         past = layer.as_tuple() if use_cache else None                                     # :454-455
-        attn_output = attn_output.transpose(1, 2).reshape(bsz, q_len, self.num_heads * self.head_dim)
+        if attn_output.shape[1] != self.num_heads:       # padded query groups: the pad heads' outputs stay behind
+            attn_output = _qkrope.unpad(attn_output, self.num_key_value_heads, self.num_key_value_groups)
+        else:
+            attn_output = attn_output.transpose(1, 2).reshape(bsz, q_len, self.num_heads * self.head_dim)
         return self.o_proj(attn_output), None, past
 
     def _capacity(self, needed: int) -> int:
@@ -285,6 +332,38 @@ class MistralAttention_KIVI(LlamaAttention_KIVI):
             config = SimpleNamespace(**{**vars(config), "attention_bias": False})
         super().__init__(config, layer_idx)
         self.sliding_window = getattr(config, "sliding_window", None)
+
+
+class HeadRMSNorm(nn.Module):
+    """HF's Qwen3RMSNorm over head_dim, applied to every head of q / k before RoPE.  With config.kivi_qk_kernel its weight and eps go
+    to kivi_qk_rope; forward() is the torch path of the same formula."""
+
+    def __init__(self, dim: int, eps: float):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(dim))
+        self.eps = eps
+
+    def forward(self, x):
+        return _qkrope.head_norm(x, self.weight, self.eps)
+
+
+class QwenAttention_KIVI(LlamaAttention_KIVI):
+    """The attention block of HF's Qwen2 / Qwen3 around the same cache hook.  Against the Llama block:
+      * `o_proj` never carries a bias; q / k / v carry one when `config.attention_bias` says so (Qwen2ForCausalLM_KIVI sets it:
+        HF's Qwen2 always biases the three);
+      * `config.kivi_head_norm` (Qwen3): `q_norm` / `k_norm`, an RMSNorm over head_dim with a weight of its own on every head of
+        q and of k, before RoPE;
+      * a sliding window is refused: the quantised history has no window here."""
+
+    def __init__(self, config, layer_idx: Optional[int] = None):
+        if getattr(config, "use_sliding_window", False):
+            raise ValueError("use_sliding_window=True: the quantised KV history has no sliding window; load the model with "
+                             "use_sliding_window=false (full attention) or do not use this cache")
+        super().__init__(config, layer_idx)
+        self.o_proj = nn.Linear(self.num_heads * self.head_dim, self.hidden_size, bias=False)
+        if getattr(config, "kivi_head_norm", False):
+            eps = getattr(config, "rms_norm_eps", 1e-6)
+            self.q_norm, self.k_norm = HeadRMSNorm(self.head_dim, eps), HeadRMSNorm(self.head_dim, eps)
 
 
 class MistralFlashAttention_KIVI(MistralAttention_KIVI):

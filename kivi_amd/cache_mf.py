@@ -46,6 +46,18 @@ def supported(cfg: KiviConfig, head_dim: int, num_heads: int, num_kv_heads: int)
         and cfg.residual_length <= 128
 
 
+def padded_heads(cfg: KiviConfig, head_dim: int, num_heads: int, num_kv_heads: int):
+    """The query-head count a model that `supported` turns away can run this layout with, or None: every kv head's nh / nh_kv query
+    heads padded to the next ratio the layout serves (mfma.padded_ratio) by zero heads.  The caller pads q
+    (kivi_qk_rope) and cuts the pad heads' outputs off."""
+    if num_heads % num_kv_heads or supported(cfg, head_dim, num_heads, num_kv_heads):
+        return None
+    rp = mfma.padded_ratio(cfg.k_bits, cfg.v_bits, num_heads // num_kv_heads)
+    if rp is None or not supported(cfg, head_dim, num_kv_heads * rp, num_kv_heads):
+        return None
+    return num_kv_heads * rp
+
+
 def _scratch(device, B: int, nh: int, nh_kv: int, pitch: int, nseg: int, slices: int):
     stream = torch.cuda.current_stream(device).cuda_stream if torch.device(device).type == "cuda" else 0
     d = _SCRATCH.setdefault((str(device), stream), {})

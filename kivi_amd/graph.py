@@ -32,6 +32,7 @@ from . import _lib
 from .attention import _rotate_half, kivi_attention_decode, rope_cos_sin
 from .cache_mf import SB, KiviLayerCacheMF
 from .generation import _MIN16, leading_pads
+from .qkrope import unpad
 from .scoring import score_into
 
 
@@ -164,7 +165,9 @@ class DecodeGraphs:
 
     In eager mode the host needs longer to enqueue the ~30 small launches of a layer's dense part than the GPU to run them.  Here
     they read and write static buffers (`tok`, `cos` / `sin`, `x`, `qkv`, `attn`) through two bodies: `pre(i)`, block input (layer 0:
-    the embedding of `tok`) to the rotated q / k / v, and `post(i)`, attention output to block output (last layer: on to the head and
+    the embedding of `tok`) to the rotated q / k / v (with config.kivi_qk_kernel: one kivi_qk_rope launch into `qkv` buffers sized
+    for the padded query groups, which post() cuts back), and `post(i)`, attention output to block output
+    (last layer: on to the head and
     the next token in `tok`).  Same kernels, same results as forward().  Per-layer form: pre(i) and post(i) are captured once, here,
     and the KIVI step between them stays one eager call per layer (its lengths change every step).  Whole-step form (`whole`: every
     cache in the matrix-pipe layout): the attention launches read their lengths from device memory (MfStepDriver), so GraphedDecode
@@ -203,8 +206,9 @@ class DecodeGraphs:
         self.tok = zeros(B, 1, dtype=torch.long)
         self.cos, self.sin = (zeros(B if padded else 1, 1, 1, D) for _ in range(2))
         self.x = [zeros(B, 1, cfg.hidden_size) for _ in range(len(layers) + 1)]
-        self.attn = zeros(B, nh, 1, D)
-        self.qkv = [(zeros(B, nh, 1, D), zeros(B, nkv, 1, D), zeros(B, nkv, 1, D)) for _ in layers]
+        nhp = layers[0].self_attn.cache_heads       # nh, or nh_kv * the padded ratio (config.kivi_qk_kernel)
+        self.attn = zeros(B, nhp, 1, D)
+        self.qkv = [(zeros(B, nhp, 1, D), zeros(B, nkv, 1, D), zeros(B, nkv, 1, D)) for _ in layers]
         self.mask = self.pos = self.driver = self.graphed = self.stats = None
         self.lead = zeros(B, dtype=torch.int32) if padded and lead else None
         self.logprobs = logprobs
@@ -227,6 +231,11 @@ class DecodeGraphs:
         if i == 0:
             self.x[0].copy_(self.model.model.embed_tokens(self.tok))
         h = layer.input_layernorm(self.x[i])
+        if a.qk_kernel or a.q_norm is not None:      # one kivi_qk_rope launch: head norm, RoPE, the padded head layout
+            v.copy_(a.v_proj(h).view(self.B, 1, -1, a.head_dim).transpose(1, 2))
+            a.prepare_qk(a.q_proj(h).view(self.B, 1, -1, a.head_dim), a.k_proj(h).view(self.B, 1, -1, a.head_dim),
+                         self.cos.view(-1, 1, a.head_dim), self.sin.view(-1, 1, a.head_dim), q.shape[1], q, k)
+            return
         for dst, proj in ((q, a.q_proj), (k, a.k_proj), (v, a.v_proj)):
             t = proj(h).view(self.B, 1, -1, a.head_dim).transpose(1, 2)
             dst.copy_(t if dst is v else t * self.cos + _rotate_half(t) * self.sin)
@@ -234,7 +243,11 @@ class DecodeGraphs:
     def post(self, i: int, draw: bool = True) -> None:
         """`draw=False`: the next token by argmax whatever the sampler (a warm-up must not consume a draw)."""
         layer = self.model.model.layers[i]
-        x = self.x[i] + layer.self_attn.o_proj(self.attn.transpose(1, 2).reshape(self.B, 1, -1))
+        a = layer.self_attn
+        if self.attn.shape[1] != a.num_heads:       # padded query groups: the pad heads' outputs stay behind
+            x = self.x[i] + a.o_proj(unpad(self.attn, a.num_key_value_heads, a.num_key_value_groups))
+        else:
+            x = self.x[i] + a.o_proj(self.attn.transpose(1, 2).reshape(self.B, 1, -1))
         self.x[i + 1].copy_(x + layer.mlp(layer.post_attention_layernorm(x)))
         if i == len(self.x) - 2:
             logits = self.model.lm_head(self.model.model.norm(self.x[i + 1]))

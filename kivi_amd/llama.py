@@ -39,11 +39,13 @@ from .stopping import SYNC_EVERY, StopRows, check_sync_every, resolve_stopping
 
 
 def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32, residual_length: int = 32,
-                max_cache_len: Optional[int] = None, prefill_kernel: bool = False, decode_lead: bool = False) -> SimpleNamespace:
+                max_cache_len: Optional[int] = None, prefill_kernel: bool = False, decode_lead: bool = False,
+                qk_kernel: bool = False) -> SimpleNamespace:
     """HF config.json fields (+ the four KIVI fields) -> the namespace the modules read.  `prefill_kernel`: the prompt pass's
     attention runs kivi_prefill_attention, and every attention class serves left-padded prompts.
     `decode_lead`: the decode steps of a padded batch hand the kernels every row's leading pads, and the row kernels skip the packed
-    K and V under them."""
+    K and V under them.  `qk_kernel`: q and k are prepared by one kivi_qk_rope launch per layer, and a model
+    whose nh / nh_kv the matrix-pipe layout does not serve runs on it with padded query groups."""
     hidden, heads = d["hidden_size"], d["num_attention_heads"]
     return SimpleNamespace(
         hidden_size=hidden, num_attention_heads=heads, num_key_value_heads=d.get("num_key_value_heads", heads),
@@ -55,7 +57,8 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
         k_bits=d.get("k_bits", k_bits), v_bits=d.get("v_bits", v_bits), group_size=d.get("group_size", group_size),
         residual_length=d.get("residual_length", residual_length),
         kivi_max_cache_len=max_cache_len,   # opt-in reservation; by default the cache starts prompt-sized and doubles
-        kivi_prefill_kernel=bool(prefill_kernel), kivi_decode_lead=bool(decode_lead))
+        kivi_prefill_kernel=bool(prefill_kernel), kivi_decode_lead=bool(decode_lead), kivi_qk_kernel=bool(qk_kernel),
+        model_type=d.get("model_type"), use_sliding_window=bool(d.get("use_sliding_window", False)))
 
 
 class RMSNorm(nn.Module):
@@ -109,6 +112,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
     Prompts of different lengths are left-padded (`left_pad`) and described by HF's 2D mask (1 = real token): `padding_mask`
     of forward(), `attention_mask` of generate() / generate_graphed() / decode_graphed().  Pads are ordinary cache tokens
     that every query masks; a mask without a pad takes the unmasked path unchanged."""
+
+    _QK_KERNEL = False          # from_pretrained's default of `qk_kernel` for the class
 
     def __init__(self, config, attention_cls=LlamaAttention_KIVI):
         super().__init__()
@@ -735,9 +740,14 @@ class LlamaForCausalLM_KIVI(nn.Module):
     @classmethod
     def from_pretrained(cls, path: str, device="cuda", dtype=torch.float16, **kivi):
         """`path`: a local HF checkpoint directory (config.json + *.safetensors).  `kivi`: k_bits, v_bits, group_size,
-        residual_length, max_cache_len, prefill_kernel, decode_lead."""
+        residual_length, max_cache_len, prefill_kernel, decode_lead, qk_kernel (default: the class's, on for the Qwen classes).
+        Called on LlamaForCausalLM_KIVI, a config.json whose `model_type` is qwen2 / qwen3 builds that family's class."""
         from safetensors.torch import load_file
-        cfg = make_config(json.load(open(os.path.join(path, "config.json"))), **kivi)
+        d = json.load(open(os.path.join(path, "config.json")))
+        if cls is LlamaForCausalLM_KIVI:
+            cls = {"qwen2": Qwen2ForCausalLM_KIVI, "qwen3": Qwen3ForCausalLM_KIVI}.get(d.get("model_type"), cls)
+        kivi.setdefault("qk_kernel", cls._QK_KERNEL)
+        cfg = make_config(d, **kivi)
         with torch.device(device):
             prev = torch.get_default_dtype()
             torch.set_default_dtype(dtype)
@@ -763,3 +773,27 @@ class MistralForCausalLM_KIVI(LlamaForCausalLM_KIVI):
     def __init__(self, config, attention_cls=None):
         from .attention import MistralAttention_KIVI
         super().__init__(config, attention_cls or MistralAttention_KIVI)
+
+
+class Qwen2ForCausalLM_KIVI(LlamaForCausalLM_KIVI):
+    """HF's Qwen2ForCausalLM (Qwen2 / Qwen2.5) around QwenAttention_KIVI: a bias on q_proj / k_proj / v_proj and none on o_proj,
+    `config.head_dim` when given, tied embeddings as the Llama class has them.  Their query-group ratios (7, 5, 6) are not the
+    matrix-pipe layout's: with `qk_kernel` -- the default of these classes in from_pretrained, and of a config without the field --
+    the groups run padded to 8.  `use_sliding_window=True` raises."""
+
+    _QK_KERNEL = True
+    _HEAD_NORM = False
+
+    def __init__(self, config, attention_cls=None):
+        from .attention import QwenAttention_KIVI
+        fields = {**vars(config), "kivi_head_norm": self._HEAD_NORM, "kivi_qk_kernel": getattr(config, "kivi_qk_kernel", True)}
+        if not self._HEAD_NORM:
+            fields["attention_bias"] = True         # HF's Qwen2 has no such field: q / k / v always carry a bias
+        super().__init__(SimpleNamespace(**fields), attention_cls or QwenAttention_KIVI)
+
+
+class Qwen3ForCausalLM_KIVI(Qwen2ForCausalLM_KIVI):
+    """HF's Qwen3ForCausalLM: as Qwen2 with `attention_bias` read from the config (default: none) and `q_norm` / `k_norm`, an RMSNorm
+    over head_dim on every head of q and k before RoPE (checkpoint names self_attn.q_norm.weight / self_attn.k_norm.weight)."""
+
+    _HEAD_NORM = True

@@ -28,6 +28,15 @@ def supported(k_bits: int, v_bits: int, group_size: int, head_dim: int, residual
     return (k_bits == 2 and ratio in (1, 4, 8)) or (k_bits == 4 and ratio in (1, 4))
 
 
+def padded_ratio(k_bits: int, v_bits: int, ratio: int):
+    """The smallest nh / nh_kv the layout serves at these bits that is >= `ratio`, or None: a group of `ratio` query heads can run as
+    that one with zero query heads in the slots left over -- the heads of a group share every code, so the pad
+    costs no cache traffic."""
+    if k_bits != v_bits or ratio < 1:
+        return None
+    return next((r for r in {2: (1, 4, 8), 4: (1, 4)}.get(k_bits, ()) if r >= ratio), None)
+
+
 def _flag_words(B: int, nh_kv: int) -> int:
     return (B * nh_kv + 63) // 64 * 64          # the flags take whole 256-byte lines behind the super-blocks
 
