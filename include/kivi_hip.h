@@ -680,17 +680,25 @@ int kivi_mf_store_admit(void* dst, int64_t dst_sb, int64_t dst_sh, int64_t dst_s
  * keep a token when the probability mass strictly above it is < top_p (whole tie classes; 1: off); keep p >= min_p * p_max (0: off);
  * then the first token in vocabulary order whose inclusive running sum of kept probabilities exceeds u * (kept mass).
  * Probabilities are integer weights floor(exp(s - max) * 2^40), so every sum is exact and the token is reproducible bit for bit.
- *   logits      row b at logits + b * row_stride (elements); fp16 (logits_bits 16) or fp32 (32); any V-long row, e.g. the
+ *   logits      row b at logits + b * row_stride (elements); fp16 (logits_bits 16), fp32 (32) or bf16 (KIVI_LOGITS_BF16, below); any
+ *               V-long row, e.g. the
  *               (B, 1, V) output of lm_head read in place
  *   rng_state   two int64 in device memory, {seed, n}.  u = (x0 >> 8) * 2^-24 with x0 the first word of Philox4x32-10 at
  *               key (seed low 32 bits, seed high 32 bits), counter (b, 0, n low 32 bits, n high 32 bits).  A second one-thread
  *               launch of the same call adds 1 to n after the draw: a captured graph replays without host writes.
  *   out_tokens  int64, token of row b at out_tokens[b * out_stride]
  * -inf logits are legal and never drawn; a row that is all -inf or holds NaN / +inf gets some token in [0, V).
- * KIVI_EINVAL (nothing enqueued) for logits_bits not 16 / 32, B outside [1, KIVI_SAMPLE_MAX_B], V outside [1, KIVI_SAMPLE_MAX_V],
+ * KIVI_EINVAL (nothing enqueued) for a logits_bits that is none of the three, B outside [1, KIVI_SAMPLE_MAX_B], V outside [1, KIVI_SAMPLE_MAX_V],
  * row_stride < V or out_stride < 1 (B > 1), temperature not finite and > 0, top_k < 0, top_p outside (0, 1], min_p outside [0, 1),
  * a null pointer; KIVI_EALIGN for logits not aligned to its element, rng_state or out_tokens not 8-byte aligned.
+ *
+ * KIVI_LOGITS_BF16: a third value of `logits_bits`, here and in every entry below that takes one
+ * (kivi_sample_rows / _pen / _con, kivi_token_logprob, kivi_token_top_logprobs): the rows are bf16, 2-byte elements.  float(logit) of
+ * a bf16 element is its exact fp32 image (its 16 bits over 16 zero bits), so every result -- tokens, history-table updates,
+ * log-probabilities, lse, ranks, top-k ids -- holds the bits the same entry gives with logits_bits 32 on the row converted to fp32.
+ * 16 and 32 keep their meaning; any other value is KIVI_EINVAL.
  */
+#define KIVI_LOGITS_BF16 0x110 /* 16-bit elements, bit 8: the brain-float layout */
 #define KIVI_SAMPLE_MAX_B 65535
 #define KIVI_SAMPLE_MAX_V (1 << 20)
 int kivi_sample(const void* logits, int logits_bits, int64_t row_stride, int B, int V, float temperature, int top_k, float top_p,
@@ -715,7 +723,7 @@ int kivi_sample(const void* logits, int logits_bits, int64_t row_stride, int B, 
  * outside the contract degrades, it never loops and never indexes outside its row:  top_k < 0 is read as 0 (off);  top_p is clamped
  * into (0, 1] (NaN or > 1: 1, off; <= 0: the smallest positive float, the top tie class alone);  min_p is clamped into [0, 1) (NaN
  * or < 0: 0, off; >= 1: the largest float below 1);  a temperature that is not finite or is <= 0 makes the row greedy.
- * KIVI_EINVAL (nothing enqueued) for logits_bits not 16 / 32, B outside [1, KIVI_SAMPLE_MAX_B], V outside [1, KIVI_SAMPLE_MAX_V],
+ * KIVI_EINVAL (nothing enqueued) for a logits_bits that is none of the three, B outside [1, KIVI_SAMPLE_MAX_B], V outside [1, KIVI_SAMPLE_MAX_V],
  * row_stride < V or out_stride < 1 (B > 1), a null logits / rows / draw_index / out_tokens; KIVI_EALIGN for logits not aligned to
  * its element, rows, draw_index or out_tokens not 8-byte aligned.
  */
@@ -924,11 +932,12 @@ int kivi_stop_rows(int64_t* tokens, int64_t tok_stride, const kivi_stop_params* 
  *   lse = m + log(S * 2^-40);  out_logprob[r] = x_t - lse;  out_lse[r] = lse (when given);
  *   out_rank[r] (when given) = #{j : x_j > x_t, or x_j == x_t and j < t}: 0 exactly when argmax of the row is t.
  *   t == ignore_index: logprob 0, rank -1, lse written.  Any other t outside [0, V): logprob NaN, rank -1, lse written.
- *   logits      fp16 (logits_bits 16) or fp32 (32); row r starts at logits + r * row_stride elements and is contiguous
+ *   logits      fp16 (logits_bits 16), fp32 (32) or bf16 (KIVI_LOGITS_BF16); row r starts at logits + r * row_stride elements and is
+ *               contiguous
  *   targets     int64;  out_logprob / out_lse fp32 and out_rank int32, N contiguous entries each; out_lse and out_rank may be null
  * -inf logits are legal and weigh 0; a target on one gives -inf.  A row that is all -inf or holds NaN / +inf gets some value.
  * One 1024-thread workgroup per row, rows taken grid-stride: N is not bounded by the grid.
- * KIVI_EINVAL (nothing enqueued) for logits_bits not 16 / 32, N < 1, V outside [1, KIVI_SAMPLE_MAX_V], row_stride < V or
+ * KIVI_EINVAL (nothing enqueued) for a logits_bits that is none of the three, N < 1, V outside [1, KIVI_SAMPLE_MAX_V], row_stride < V or
  * target_stride < 1 (N > 1), a null logits / targets / out_logprob; KIVI_EALIGN for logits not aligned to its element, targets not
  * 8-byte aligned, an output not 4-byte aligned.
  */
@@ -950,7 +959,7 @@ int kivi_token_logprob(const void* logits, int logits_bits, int64_t row_stride, 
  *   out_top_ids int64, out_top_logprobs fp32: k entries per row, rows top_stride elements apart; nothing else is written
  * A row that is all -inf or holds NaN / +inf gets some value.  The same row gives the same bits strided or contiguous, at any
  * element alignment, eager or replayed: integer LDS atomics only, every output element written by one lane.
- * One 1024-thread workgroup per row, rows taken grid-stride; the row is read 3 (fp16) or 4 (fp32) times, 2 more when the tie class
+ * One 1024-thread workgroup per row, rows taken grid-stride; the row is read 3 (fp16, bf16) or 4 (fp32) times, 2 more when the tie class
  * at the k-th place straddles the cut.
  * KIVI_EINVAL (nothing enqueued) for every case of kivi_token_logprob (targets only when given), k outside
  * [1, min(V, KIVI_TOP_LOGPROBS_MAX)], top_stride < k (N > 1), a null out_top_ids / out_top_logprobs, out_logprob or out_rank
@@ -1005,6 +1014,29 @@ int kivi_qk_rope(const void* q_in, int64_t q_sb, int64_t q_st, int64_t q_sh, con
                  int64_t k_sh, const void* cos, const void* sin, int64_t cs_sb, int64_t cs_st, const void* q_weight,
                  const void* k_weight, float eps, void* q_out, void* k_out, int B, int Q, int nh, int nh_kv, int Rp, int D,
                  kivi_stream_t stream);
+/*
+ * kivi_qkv_rope_bf16: the way into the fp16 attention for a model whose dense layers run in bf16 -- what
+ * kivi_qk_rope does to q and k, and the placement of v, from bf16 projections to fp16 tensors in one launch.
+ *   q_in   (B, Q, nh, D), k_in, v_in (B, Q, nh_kv, D) bf16 by their strides (batch, token, head) in elements, channel stride 1
+ *   cos, sin   (Bc, Q, D) FP32 tables, batch stride cs_sb (0: one table for every row) and token stride cs_st in elements
+ *   q_weight, k_weight   D bf16 each, or null: no head norm;  eps: its epsilon
+ *   q_out  (B, nh_kv * Rp, Q, D), k_out, v_out (B, nh_kv, Q, D) fp16, contiguous.  Query head kv * R + r lands at kv * Rp + r; the
+ *          heads kv * Rp + [R, Rp) are written as zeros on every call.  Every element of the three outputs is written once, nothing
+ *          else is.
+ * Arithmetic, with every input taken as the exact number it holds: with a weight, y = w * x * rsqrt(mean(x^2) + eps), else y = x;
+ * out = y * cos + rot(y) * sin, rot(y)[i] = -y[i + 64], rot(y)[i + 64] = y[i]; the whole expression is evaluated in fp64 and rounded
+ * ONCE, to fp16 (round to nearest even): each element is the fp16 neighbour of the formula's value, whatever the order of the
+ * reduction.  v_out = fp16(v_in), round to nearest even.  A finite result beyond +-65504 is stored as +-65504; NaN stays NaN.
+ * (Not the operation sequence of a bf16 torch model, which rounds to bf16 after every step: nothing downstream is bf16.)
+ * One wave per (row, token, head slot); no LDS, no scratch.
+ * KIVI_EINVAL (nothing enqueued) for D != 128; B, Q, nh or nh_kv < 1; nh not a multiple of nh_kv; Rp outside [R, 64]; a null q_in /
+ * k_in / v_in / cos / sin / q_out / k_out / v_out; a negative stride; eps negative or not finite; 2^31 blocks or more.  KIVI_EALIGN
+ * for a 2-byte pointer off 2 bytes, cos or sin off 4.
+ */
+int kivi_qkv_rope_bf16(const void* q_in, int64_t q_sb, int64_t q_st, int64_t q_sh, const void* k_in, int64_t k_sb, int64_t k_st,
+                       int64_t k_sh, const void* v_in, int64_t v_sb, int64_t v_st, int64_t v_sh, const void* cos, const void* sin,
+                       int64_t cs_sb, int64_t cs_st, const void* q_weight, const void* k_weight, float eps, void* q_out, void* k_out,
+                       void* v_out, int B, int Q, int nh, int nh_kv, int Rp, int D, kivi_stream_t stream);
 /* geometry class of a step (-1: bad arguments): the super-block counts of both stores and whether the step flushes a value; the
  * launch plan (one launch / S slices / two launches) is a function of the class and of constants of the call (shape, bits, flags) */
 int64_t kivi_mf_step_key(const kivi_mf_step* step, int B, int nh, int nh_kv, int residual_length, int flags);

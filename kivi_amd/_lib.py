@@ -212,6 +212,8 @@ SIGNATURES = {
                                       _i32, _i32, _i32, _i32, _i32, ctypes.c_float, _vp]),
     "kivi_qk_rope": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, ctypes.c_float, _vp, _vp,
                             _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "kivi_qkv_rope_bf16": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp,
+                                  ctypes.c_float, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "kivi_mf_step_key": (_i64, [ctypes.POINTER(MfStep), _i32, _i32, _i32, _i32, _i32]),
     "kivi_mf_step_advance": (_i32, [ctypes.POINTER(MfStep), _i32, _i64]),
     "kivi_mf_step_upload": (_i32, [ctypes.POINTER(MfStep), _vp, _vp]),
@@ -289,6 +291,10 @@ def require_gpu(t: torch.Tensor, name: str) -> None:
 
 def ptr(t: torch.Tensor) -> ctypes.c_void_p:
     return ctypes.c_void_p(t.data_ptr())
+
+
+LOGITS_BF16 = 0x110   # include/kivi_hip.h: KIVI_LOGITS_BF16
+LOGITS_BITS = {torch.float16: 16, torch.float32: 32, torch.bfloat16: LOGITS_BF16}   # dtype -> `logits_bits` of the fused logits entries
 
 
 # --------------------------------------------------------------------------- tensors -> arguments of a layer step

@@ -237,12 +237,65 @@ class LlamaAttention_KIVI(nn.Module):
         q, k = _qkrope.qk_rope_torch(q_in, k_in, cos, sin, qw, kw, eps)
         return (q, k) if q_out is None else (q_out.copy_(q), k_out.copy_(k))
 
+    def inv_freq_exact(self, device) -> torch.Tensor:
+        """The rotary frequencies in fp32 whatever the module was cast to (`inv_freq` is a buffer: .bfloat16() rounds it to 8 bits):
+        what the boundary's fp32 tables are made from."""
+        t = self.__dict__.get("_inv_freq_exact")
+        if t is None or t.device != device:
+            t = self.__dict__["_inv_freq_exact"] = _rope_inv_freq(self.config, self.head_dim, self.rope_theta).to(device)
+        return t
+
+    def _boundary_qkv(self, hidden_states, position_ids, past_len: int, heads: int):
+        """q, k, v of a model whose hidden states are not fp16: fp16, by one kivi_qkv_rope_bf16 launch or the
+        torch restatement of its contract, from fp32 cos / sin tables."""
+        _lib.require_gpu(hidden_states, "hidden_states")    # (the cache behind the boundary has no CPU path)
+        bsz, q_len, _ = hidden_states.size()
+        q_in = self.q_proj(hidden_states).view(bsz, q_len, self.num_heads, self.head_dim)
+        k_in = self.k_proj(hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
+        v_in = self.v_proj(hidden_states).view(bsz, q_len, self.num_key_value_heads, self.head_dim)
+        device = hidden_states.device
+        if position_ids is None:
+            key = (device, "exact", self.head_dim, self.rope_theta, repr(getattr(self.config, "rope_scaling", None)), past_len, q_len)
+            cs = _ROPE_CACHE.get(key)
+            if cs is None:
+                pos = torch.arange(past_len, past_len + q_len, device=device)[None]
+                cs = rope_cos_sin(self.inv_freq_exact(device), pos)
+                _ROPE_CACHE.clear()
+                _ROPE_CACHE[key] = cs
+            cos, sin = cs
+        else:
+            cos, sin = rope_cos_sin(self.inv_freq_exact(device), position_ids)                  # (B, T, D) fp32
+        return self.boundary_qkv(q_in, k_in, v_in, cos, sin, heads)
+
+    def boundary_qkv(self, q_in, k_in, v_in, cos, sin, heads: int, q_out=None, k_out=None, v_out=None):
+        """q_in (B, Q, nh, D), k_in / v_in (B, Q, nh_kv, D) bf16 (fp32: the torch path), cos / sin (1 or B, Q, D) fp32 -> fp16
+        q (B, heads, Q, D), k, v (B, nh_kv, Q, D), in the `_out` buffers when given.  The kernel serves wherever it can, with
+        config.kivi_qk_kernel or without; only that option pads the query groups."""
+        qw, kw, eps = (None, None, 0.0) if self.q_norm is None else (self.q_norm.weight, self.k_norm.weight, self.q_norm.eps)
+        if _qkrope.boundary_usable(q_in, self.head_dim):
+            return _qkrope.qkv_rope_bf16(q_in, k_in, v_in, cos, sin, heads // self.num_key_value_heads, qw, kw, eps, q_out, k_out,
+                                         v_out)
+        q, k, v = _qkrope.qkv_rope_bf16_torch(q_in, k_in, v_in, cos, sin, qw, kw, eps)
+        if heads != self.num_heads:                 # (an fp32 model over padded caches: the zero heads by a copy)
+            q = _qkrope.pad_groups(q, self.num_key_value_heads, heads // self.num_key_value_heads)
+        return (q, k, v) if q_out is None else (q_out.copy_(q), k_out.copy_(k), v_out.copy_(v))
+
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 position_ids: Optional[torch.LongTensor] = None, past_key_value=None, output_attentions: bool = False,
                 use_cache: bool = False, **kwargs) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[tuple]]:
         bsz, q_len, _ = hidden_states.size()
         past_len = 0 if past_key_value is None else int(past_key_value[-1])
-        if self.qk_kernel or self.q_norm is not None:
+        # a bf16 model, or an fp32 one on the GPU (the dense reference of the tests): q, k, v cross into fp16 here, the output back
+        # below.  (fp32 modules off the GPU keep the path they had: host-side tests drive it over stand-in caches.)
+        boundary = hidden_states.dtype == torch.bfloat16 or (hidden_states.dtype != torch.float16 and hidden_states.is_cuda)
+        if boundary:
+            heads = self.num_heads
+            if isinstance(past_key_value, KiviCacheTuple):
+                heads = getattr(past_key_value.layer, "nh", self.num_heads)
+            elif past_key_value is not None:
+                heads = self.cache_heads
+            q, k, v = self._boundary_qkv(hidden_states, position_ids, past_len, heads)
+        elif self.qk_kernel or self.q_norm is not None:
             heads = self.num_heads                  # the prompt pass launches nothing over the cache with q: no pad heads
             if isinstance(past_key_value, KiviCacheTuple):      # over a cache: as many query heads as it was built for
                 heads = getattr(past_key_value.layer, "nh", self.num_heads)
@@ -293,7 +346,9 @@ class LlamaAttention_KIVI(nn.Module):
             else:                                          # the option is off: the call as it always was
                 attn_output = kivi_attention_prefill(q, k, v, layer, mask)
         past = layer.as_tuple() if use_cache else None                                     # :454-455
-        if attn_output.shape[1] != self.num_heads:       # padded query groups: the pad heads' outputs stay behind
+        if boundary:                                     # the way back: the one copy in front of o_proj casts too
+            attn_output = _qkrope.unpad(attn_output, self.num_key_value_heads, self.num_key_value_groups, hidden_states.dtype)
+        elif attn_output.shape[1] != self.num_heads:     # padded query groups: the pad heads' outputs stay behind
             attn_output = _qkrope.unpad(attn_output, self.num_key_value_heads, self.num_key_value_groups)
         else:
             attn_output = attn_output.transpose(1, 2).reshape(bsz, q_len, self.num_heads * self.head_dim)

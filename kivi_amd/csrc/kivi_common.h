@@ -8,6 +8,19 @@
 
 typedef _Float16 f16;
 typedef f16 f16x2 __attribute__((ext_vector_type(2)));
+
+// A bf16 element as the fused logits kernels read it (KIVI_LOGITS_BF16): its 16 bits, and the fp32 value they are the upper half of.
+// The conversion is exact -- a shift, also for subnormals, infinities and NaN -- so a bf16 row IS the fp32 row `logits.float()` holds.
+struct bf16 {
+    uint16_t bits;
+    __host__ __device__ __forceinline__ explicit operator float() const { return __builtin_bit_cast(float, (uint32_t)bits << 16); }
+};
+
+// logits_bits of the fused logits entries -> bytes per element (0: not a value of the header)
+static inline int kivi_logits_esz(int logits_bits) {
+    return logits_bits == 32 ? 4 : (logits_bits == 16 || logits_bits == KIVI_LOGITS_BF16) ? 2 : 0;
+}
+
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));

@@ -584,7 +584,8 @@ static int bucket_size(int V) {
 extern "C" int kivi_sample(const void* logits, int logits_bits, int64_t row_stride, int B, int V, float temperature, int top_k,
                            float top_p, float min_p, int64_t* rng_state, int64_t* out_tokens, int64_t out_stride,
                            kivi_stream_t stream) {
-    KIVI_REQUIRE(logits_bits == 16 || logits_bits == 32, KIVI_EINVAL, "kivi_sample: logits_bits=%d (16: fp16, 32: fp32)", logits_bits);
+    const int esz = kivi_logits_esz(logits_bits);
+    KIVI_REQUIRE(esz, KIVI_EINVAL, "kivi_sample: logits_bits=%d (16: fp16, 32: fp32, KIVI_LOGITS_BF16: bf16)", logits_bits);
     KIVI_REQUIRE(B >= 1 && B <= KIVI_SAMPLE_MAX_B, KIVI_EINVAL, "kivi_sample: B=%d (1 <= B <= %d)", B, KIVI_SAMPLE_MAX_B);
     KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "kivi_sample: V=%d (1 <= V <= %d)", V, KIVI_SAMPLE_MAX_V);
     KIVI_REQUIRE(row_stride >= V || B == 1, KIVI_EINVAL, "kivi_sample: row_stride=%lld below V=%d", (long long)row_stride, V);
@@ -595,7 +596,6 @@ extern "C" int kivi_sample(const void* logits, int logits_bits, int64_t row_stri
     KIVI_REQUIRE(top_p > 0.0f && top_p <= 1.0f, KIVI_EINVAL, "kivi_sample: top_p=%g (0 < top_p <= 1; 1 = off)", (double)top_p);
     KIVI_REQUIRE(min_p >= 0.0f && min_p < 1.0f, KIVI_EINVAL, "kivi_sample: min_p=%g (0 <= min_p < 1; 0 = off)", (double)min_p);
     KIVI_REQUIRE(logits && rng_state && out_tokens, KIVI_EINVAL, "kivi_sample: null pointer");
-    const int esz = logits_bits / 8;
     KIVI_REQUIRE((uintptr_t)logits % esz == 0 && (uintptr_t)rng_state % 8 == 0 && (uintptr_t)out_tokens % 8 == 0, KIVI_EALIGN,
                  "kivi_sample: misaligned logits (%d-byte elements), rng_state or out_tokens (8 bytes)", esz);
     const int BS = bucket_size(V);
@@ -603,6 +603,9 @@ extern "C" int kivi_sample(const void* logits, int logits_bits, int64_t row_stri
     if (logits_bits == 16)
         KIVI_LAUNCH(sample_kernel<f16>, dim3(B), dim3(kThreads), s, (const f16*)logits, row_stride, V, BS, temperature, top_k, top_p,
                     min_p, (const int64_t*)rng_state, out_tokens, out_stride);
+    else if (logits_bits == KIVI_LOGITS_BF16)
+        KIVI_LAUNCH(sample_kernel<bf16>, dim3(B), dim3(kThreads), s, (const bf16*)logits, row_stride, V, BS, temperature, top_k,
+                    top_p, min_p, (const int64_t*)rng_state, out_tokens, out_stride);
     else
         KIVI_LAUNCH(sample_kernel<float>, dim3(B), dim3(kThreads), s, (const float*)logits, row_stride, V, BS, temperature, top_k,
                     top_p, min_p, (const int64_t*)rng_state, out_tokens, out_stride);
@@ -620,7 +623,8 @@ static int launch_rows(const char* name, bool required, const void* logits, int 
                        int64_t seen_stride, const kivi_sample_constraint* con, const uint32_t* allow, int64_t allow_stride,
                        const kivi_sample_list_entry* list, int64_t list_stride, int64_t* out_tokens, int64_t out_stride,
                        kivi_stream_t stream) {
-    KIVI_REQUIRE(logits_bits == 16 || logits_bits == 32, KIVI_EINVAL, "%s: logits_bits=%d (16: fp16, 32: fp32)", name, logits_bits);
+    const int esz = kivi_logits_esz(logits_bits);
+    KIVI_REQUIRE(esz, KIVI_EINVAL, "%s: logits_bits=%d (16: fp16, 32: fp32, KIVI_LOGITS_BF16: bf16)", name, logits_bits);
     KIVI_REQUIRE(B >= 1 && B <= KIVI_SAMPLE_MAX_B, KIVI_EINVAL, "%s: B=%d (1 <= B <= %d)", name, B, KIVI_SAMPLE_MAX_B);
     KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "%s: V=%d (1 <= V <= %d)", name, V, KIVI_SAMPLE_MAX_V);
     KIVI_REQUIRE(row_stride >= V || B == 1, KIVI_EINVAL, "%s: row_stride=%lld below V=%d", name, (long long)row_stride, V);
@@ -632,7 +636,6 @@ static int launch_rows(const char* name, bool required, const void* logits, int 
                  (long long)allow_stride, (V + 31) / 32);
     KIVI_REQUIRE(list_stride >= 0 && list_stride <= KIVI_SAMPLE_MAX_LIST, KIVI_EINVAL, "%s: list_stride=%lld (0 <= list_stride <= %d)",
                  name, (long long)list_stride, KIVI_SAMPLE_MAX_LIST);
-    const int esz = logits_bits / 8;
     KIVI_REQUIRE((uintptr_t)logits % esz == 0 && (uintptr_t)rows % 8 == 0 && (uintptr_t)draw_index % 8 == 0 &&
                      (uintptr_t)out_tokens % 8 == 0,
                  KIVI_EALIGN, "%s: misaligned logits (%d-byte elements), rows, draw_index or out_tokens (8 bytes)", name, esz);
@@ -650,6 +653,9 @@ static int launch_rows(const char* name, bool required, const void* logits, int 
     if (logits_bits == 16) {
         if (state) ROWS_LAUNCH(f16, true);
         else ROWS_LAUNCH(f16, false);
+    } else if (logits_bits == KIVI_LOGITS_BF16) {
+        if (state) ROWS_LAUNCH(bf16, true);
+        else ROWS_LAUNCH(bf16, false);
     } else {
         if (state) ROWS_LAUNCH(float, true);
         else ROWS_LAUNCH(float, false);

@@ -26,8 +26,20 @@ __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int d) {
     return ((uint64_t)hi << 32) | lo;
 }
 
+// What a vector load of T carries per element: T itself, or for bf16 (a struct: no vector of it exists) its 16 bits.
 template <typename T>
-using vec16 = T __attribute__((ext_vector_type(16 / sizeof(T))));
+struct Lane {
+    using type = T;
+    static __device__ __forceinline__ float value(T v) { return (float)v; }
+};
+template <>
+struct Lane<bf16> {
+    using type = uint16_t;
+    static __device__ __forceinline__ float value(uint16_t v) { return (float)bf16{v}; }
+};
+
+template <typename T>
+using vec16 = typename Lane<T>::type __attribute__((ext_vector_type(16 / sizeof(T))));
 
 // f(j, x_j) for every j in [0, V) exactly once over the block: elements [0, head) and the tail one per thread, the rest as
 // 16-byte vectors (p + head is 16-byte aligned; head and the tail are shorter than a vector, so shorter than the block).
@@ -41,7 +53,7 @@ __device__ __forceinline__ void sweep(const T* __restrict__ p, int V, int head, 
     for (int i = tid; i < nvec; i += kThreads) {
         const vec16<T> v = pv[i];
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) f(head + i * VEC + j, (float)v[j]);
+        for (int j = 0; j < VEC; ++j) f(head + i * VEC + j, Lane<T>::value(v[j]));
     }
     const int e = head + nvec * VEC + tid;
     if (e < V) f(e, (float)p[e]);
@@ -260,7 +272,9 @@ __global__ __launch_bounds__(kThreads) void token_top_logprobs_kernel(const T* _
             });
             cls = pick_bin(sh, 10, 0, thr, rem);
         } else {
-            thr |= (thr & 0x80000000u) ? 0u : 1023u;              // an fp16 value's fp32 image: 13 zero bits at the bottom
+            // a 2-byte element's fp32 image has zero bits at the bottom, 13 (fp16) or 16 (bf16) -- x + 0.0f keeps them: an exact sum,
+            // and a NaN keeps its payload -- so the key's low 10 bits are all 0 (sign clear: key = u | 2^31) or all 1 (set: key = ~u)
+            thr |= (thr & 0x80000000u) ? 0u : 1023u;
         }
 
         // the class at the threshold straddles the cut: take its `rem` lowest indices (the largest of ~j, as 20 bits)
@@ -330,8 +344,8 @@ extern "C" int kivi_token_top_logprobs(const void* logits, int logits_bits, int6
                                        const int64_t* targets, int64_t target_stride, int64_t ignore_index, int64_t* out_top_ids,
                                        float* out_top_logprobs, int64_t top_stride, float* out_logprob, float* out_lse,
                                        int32_t* out_rank, kivi_stream_t stream) {
-    KIVI_REQUIRE(logits_bits == 16 || logits_bits == 32, KIVI_EINVAL, "kivi_token_top_logprobs: logits_bits=%d (16: fp16, 32: fp32)",
-                 logits_bits);
+    const int esz = kivi_logits_esz(logits_bits);
+    KIVI_REQUIRE(esz, KIVI_EINVAL, "kivi_token_top_logprobs: logits_bits=%d (16: fp16, 32: fp32, KIVI_LOGITS_BF16: bf16)", logits_bits);
     KIVI_REQUIRE(N >= 1, KIVI_EINVAL, "kivi_token_top_logprobs: N=%lld (N >= 1)", (long long)N);
     KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "kivi_token_top_logprobs: V=%d (1 <= V <= %d)", V, KIVI_SAMPLE_MAX_V);
     KIVI_REQUIRE(k >= 1 && k <= V && k <= KIVI_TOP_LOGPROBS_MAX, KIVI_EINVAL, "kivi_token_top_logprobs: k=%d (1 <= k <= min(V, %d))", k,
@@ -348,7 +362,6 @@ extern "C" int kivi_token_top_logprobs(const void* logits, int logits_bits, int6
     } else {
         KIVI_REQUIRE(!out_logprob && !out_rank, KIVI_EINVAL, "kivi_token_top_logprobs: out_logprob or out_rank without targets");
     }
-    const int esz = logits_bits / 8;
     KIVI_REQUIRE((uintptr_t)logits % esz == 0 && (uintptr_t)targets % 8 == 0 && (uintptr_t)out_top_ids % 8 == 0 &&
                      (uintptr_t)out_top_logprobs % 4 == 0 && (uintptr_t)out_logprob % 4 == 0 && (uintptr_t)out_lse % 4 == 0 &&
                      (uintptr_t)out_rank % 4 == 0,
@@ -359,6 +372,9 @@ extern "C" int kivi_token_top_logprobs(const void* logits, int logits_bits, int6
     if (logits_bits == 16)
         KIVI_LAUNCH(token_top_logprobs_kernel<f16>, grid, dim3(kThreads), s, (const f16*)logits, row_stride, N, V, k, targets,
                     target_stride, ignore_index, out_top_ids, out_top_logprobs, top_stride, out_logprob, out_lse, out_rank);
+    else if (logits_bits == KIVI_LOGITS_BF16)
+        KIVI_LAUNCH(token_top_logprobs_kernel<bf16>, grid, dim3(kThreads), s, (const bf16*)logits, row_stride, N, V, k, targets,
+                    target_stride, ignore_index, out_top_ids, out_top_logprobs, top_stride, out_logprob, out_lse, out_rank);
     else
         KIVI_LAUNCH(token_top_logprobs_kernel<float>, grid, dim3(kThreads), s, (const float*)logits, row_stride, N, V, k, targets,
                     target_stride, ignore_index, out_top_ids, out_top_logprobs, top_stride, out_logprob, out_lse, out_rank);
@@ -368,14 +384,13 @@ extern "C" int kivi_token_top_logprobs(const void* logits, int logits_bits, int6
 extern "C" int kivi_token_logprob(const void* logits, int logits_bits, int64_t row_stride, int64_t N, int V, const int64_t* targets,
                                   int64_t target_stride, int64_t ignore_index, float* out_logprob, float* out_lse,
                                   int32_t* out_rank, kivi_stream_t stream) {
-    KIVI_REQUIRE(logits_bits == 16 || logits_bits == 32, KIVI_EINVAL, "kivi_token_logprob: logits_bits=%d (16: fp16, 32: fp32)",
-                 logits_bits);
+    const int esz = kivi_logits_esz(logits_bits);
+    KIVI_REQUIRE(esz, KIVI_EINVAL, "kivi_token_logprob: logits_bits=%d (16: fp16, 32: fp32, KIVI_LOGITS_BF16: bf16)", logits_bits);
     KIVI_REQUIRE(N >= 1, KIVI_EINVAL, "kivi_token_logprob: N=%lld (N >= 1)", (long long)N);
     KIVI_REQUIRE(V >= 1 && V <= KIVI_SAMPLE_MAX_V, KIVI_EINVAL, "kivi_token_logprob: V=%d (1 <= V <= %d)", V, KIVI_SAMPLE_MAX_V);
     KIVI_REQUIRE(row_stride >= V || N == 1, KIVI_EINVAL, "kivi_token_logprob: row_stride=%lld below V=%d", (long long)row_stride, V);
     KIVI_REQUIRE(target_stride >= 1 || N == 1, KIVI_EINVAL, "kivi_token_logprob: target_stride=%lld", (long long)target_stride);
     KIVI_REQUIRE(logits && targets && out_logprob, KIVI_EINVAL, "kivi_token_logprob: null pointer");
-    const int esz = logits_bits / 8;
     KIVI_REQUIRE((uintptr_t)logits % esz == 0 && (uintptr_t)targets % 8 == 0 && (uintptr_t)out_logprob % 4 == 0 &&
                      (uintptr_t)out_lse % 4 == 0 && (uintptr_t)out_rank % 4 == 0,
                  KIVI_EALIGN, "kivi_token_logprob: misaligned logits (%d-byte elements), targets (8 bytes), out_logprob, out_lse or "
@@ -384,6 +399,9 @@ extern "C" int kivi_token_logprob(const void* logits, int logits_bits, int64_t r
     const dim3 grid((unsigned)(N < KIVI_SAMPLE_MAX_B ? N : KIVI_SAMPLE_MAX_B));
     if (logits_bits == 16)
         KIVI_LAUNCH(token_logprob_kernel<f16>, grid, dim3(kThreads), s, (const f16*)logits, row_stride, N, V, targets, target_stride,
+                    ignore_index, out_logprob, out_lse, out_rank);
+    else if (logits_bits == KIVI_LOGITS_BF16)
+        KIVI_LAUNCH(token_logprob_kernel<bf16>, grid, dim3(kThreads), s, (const bf16*)logits, row_stride, N, V, targets, target_stride,
                     ignore_index, out_logprob, out_lse, out_rank);
     else
         KIVI_LAUNCH(token_logprob_kernel<float>, grid, dim3(kThreads), s, (const float*)logits, row_stride, N, V, targets,

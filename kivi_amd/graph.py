@@ -204,11 +204,15 @@ class DecodeGraphs:
         self.sampler_key = None if sampler is None else sampler.key()
         self.stopper, self.stopper_key = stopper, None if stopper is None else stopper.key()
         self.tok = zeros(B, 1, dtype=torch.long)
-        self.cos, self.sin = (zeros(B if padded else 1, 1, 1, D) for _ in range(2))
+        # a model that is not fp16: x stays in its dtype; q / k / v, the attention output and the mask are fp16 as
+        # ever, cos / sin fp32, and pre() crosses with one kivi_qkv_rope_bf16 launch, post() back in the copy that feeds o_proj
+        self.boundary = dt != torch.float16
+        self.cos, self.sin = (zeros(B if padded else 1, 1, 1, D, dtype=torch.float32 if self.boundary else dt) for _ in range(2))
         self.x = [zeros(B, 1, cfg.hidden_size) for _ in range(len(layers) + 1)]
         nhp = layers[0].self_attn.cache_heads       # nh, or nh_kv * the padded ratio (config.kivi_qk_kernel)
-        self.attn = zeros(B, nhp, 1, D)
-        self.qkv = [(zeros(B, nhp, 1, D), zeros(B, nkv, 1, D), zeros(B, nkv, 1, D)) for _ in layers]
+        f16 = torch.float16 if self.boundary else dt
+        self.attn = zeros(B, nhp, 1, D, dtype=f16)
+        self.qkv = [(zeros(B, nhp, 1, D, dtype=f16), zeros(B, nkv, 1, D, dtype=f16), zeros(B, nkv, 1, D, dtype=f16)) for _ in layers]
         self.mask = self.pos = self.driver = self.graphed = self.stats = None
         self.lead = zeros(B, dtype=torch.int32) if padded and lead else None
         self.logprobs = logprobs
@@ -231,6 +235,11 @@ class DecodeGraphs:
         if i == 0:
             self.x[0].copy_(self.model.model.embed_tokens(self.tok))
         h = layer.input_layernorm(self.x[i])
+        if self.boundary:                            # one kivi_qkv_rope_bf16 launch: q, k and v cross into fp16
+            a.boundary_qkv(a.q_proj(h).view(self.B, 1, -1, a.head_dim), a.k_proj(h).view(self.B, 1, -1, a.head_dim),
+                           a.v_proj(h).view(self.B, 1, -1, a.head_dim), self.cos.view(-1, 1, a.head_dim),
+                           self.sin.view(-1, 1, a.head_dim), q.shape[1], q, k, v)
+            return
         if a.qk_kernel or a.q_norm is not None:      # one kivi_qk_rope launch: head norm, RoPE, the padded head layout
             v.copy_(a.v_proj(h).view(self.B, 1, -1, a.head_dim).transpose(1, 2))
             a.prepare_qk(a.q_proj(h).view(self.B, 1, -1, a.head_dim), a.k_proj(h).view(self.B, 1, -1, a.head_dim),
@@ -244,7 +253,9 @@ class DecodeGraphs:
         """`draw=False`: the next token by argmax whatever the sampler (a warm-up must not consume a draw)."""
         layer = self.model.model.layers[i]
         a = layer.self_attn
-        if self.attn.shape[1] != a.num_heads:       # padded query groups: the pad heads' outputs stay behind
+        if self.boundary:
+            x = self.x[i] + a.o_proj(unpad(self.attn, a.num_key_value_heads, a.num_key_value_groups, self.x[i].dtype))
+        elif self.attn.shape[1] != a.num_heads:     # padded query groups: the pad heads' outputs stay behind
             x = self.x[i] + a.o_proj(unpad(self.attn, a.num_key_value_heads, a.num_key_value_groups))
         else:
             x = self.x[i] + a.o_proj(self.attn.transpose(1, 2).reshape(self.B, 1, -1))
@@ -316,7 +327,8 @@ class DecodeGraphs:
 
     def step(self, position: int) -> None:
         """One decode step from `tok` at `position` (padded: every row's own); the next token is left in `tok`."""
-        inv_freq = self.model.model.layers[0].self_attn.inv_freq
+        a0 = self.model.model.layers[0].self_attn
+        inv_freq = a0.inv_freq_exact(self.cos.device) if self.boundary else a0.inv_freq
         for dst, src in zip((self.cos, self.sin), rope_cos_sin(inv_freq, self.pos if self.padded else position)):
             dst.copy_(src.view(-1, 1, 1, src.shape[-1]))
         caches = [c() for c in self._caches]

@@ -126,8 +126,8 @@ def _call_args(logits: torch.Tensor, out: Optional[torch.Tensor], rows: Optional
         if logits.shape[1] != 1:
             raise ValueError(f"logits (B, 1, V) expected, got {tuple(logits.shape)}")
         logits = logits[:, 0]
-    if logits.dim() != 2 or logits.dtype not in (torch.float16, torch.float32):
-        raise ValueError(f"logits must be (B, V) or (B, 1, V) fp16 / fp32, got {tuple(logits.shape)} {logits.dtype}")
+    if logits.dim() != 2 or logits.dtype not in _lib.LOGITS_BITS:
+        raise ValueError(f"logits must be (B, V) or (B, 1, V) fp16 / bf16 / fp32, got {tuple(logits.shape)} {logits.dtype}")
     B, V = logits.shape
     if rows is not None and (B != rows.B or logits.device != rows.records.device):
         raise ValueError(f"this RowSampler holds {rows.B} rows on {rows.records.device}, got logits of {B} rows on {logits.device}")
@@ -168,7 +168,7 @@ class Sampler:
         logits, out = _call_args(logits, out)
         B, V = logits.shape
         lib = _lib.load()
-        _lib.check(lib.kivi_sample(_lib.ptr(logits), 16 if logits.dtype == torch.float16 else 32, logits.stride(0), B, V,
+        _lib.check(lib.kivi_sample(_lib.ptr(logits), _lib.LOGITS_BITS[logits.dtype], logits.stride(0), B, V,
                                    self.temperature, self.top_k, self.top_p, self.min_p, _lib.ptr(self.state), _lib.ptr(out),
                                    out.stride(0) if out.dim() else 1, _lib.stream_ptr(logits)),
                    "kivi_sample")
@@ -676,7 +676,7 @@ class RowSampler:
         the common arguments, then the penalty records and the history table when there is one, then the constraint records, allow
         masks and lists when there are any."""
         B, V = logits.shape
-        name, args = "kivi_sample_rows", (_lib.ptr(logits), 16 if logits.dtype == torch.float16 else 32, logits.stride(0), B, V,
+        name, args = "kivi_sample_rows", (_lib.ptr(logits), _lib.LOGITS_BITS[logits.dtype], logits.stride(0), B, V,
                                           _lib.ptr(self.records), _lib.ptr(self.draw_index))
         if self.seen is not None:
             name, args = "kivi_sample_rows_pen", args + (_lib.ptr(self.penalties), _lib.ptr(self.seen), self.seen.stride(0))

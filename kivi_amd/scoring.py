@@ -39,14 +39,14 @@ def _row_stride(logits: torch.Tensor):
 
 def token_logprobs(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100, return_lse: bool = False,
                    return_rank: bool = False):
-    """log p(targets) under softmax(logits): logits (..., V) fp16 / fp32 on the GPU, targets int64 of the leading shape -> fp32 of
+    """log p(targets) under softmax(logits): logits (..., V) fp16 / bf16 / fp32 on the GPU, targets int64 of the leading shape -> fp32 of
     the leading shape [, lse fp32] [, rank int32].  The last dimension must be contiguous; leading dimensions are taken by stride
     when they collapse to one row stride ((B, T, V)[:, a:b] with B == 1, padded-vocabulary buffers, (B, 1, V) views) and copied
     otherwise.  Targets outside [0, V) other than `ignore_index` give NaN (the kernel cannot raise): validate token ids first."""
     _lib.require_gpu(logits, "logits")
     _lib.require_gpu(targets, "targets")
-    if logits.dim() < 1 or logits.dtype not in (torch.float16, torch.float32):
-        raise ValueError(f"logits must be (..., V) fp16 / fp32, got {tuple(logits.shape)} {logits.dtype}")
+    if logits.dim() < 1 or logits.dtype not in _lib.LOGITS_BITS:
+        raise ValueError(f"logits must be (..., V) fp16 / bf16 / fp32, got {tuple(logits.shape)} {logits.dtype}")
     lead, V = logits.shape[:-1], logits.shape[-1]
     if targets.dtype != torch.int64 or targets.shape != lead or targets.device != logits.device:
         raise ValueError(f"targets must be int64 of shape {tuple(lead)} on {logits.device}, got {tuple(targets.shape)} {targets.dtype}")
@@ -61,7 +61,7 @@ def token_logprobs(logits: torch.Tensor, targets: torch.Tensor, ignore_index: in
         if stride is None or stride < V:
             logits, stride = logits.contiguous(), V
         targets = targets.contiguous()
-        _lib.check(_lib.load().kivi_token_logprob(_lib.ptr(logits), 16 if logits.dtype == torch.float16 else 32, stride, N, V,
+        _lib.check(_lib.load().kivi_token_logprob(_lib.ptr(logits), _lib.LOGITS_BITS[logits.dtype], stride, N, V,
                                                   _lib.ptr(targets), 1, ignore_index, _lib.ptr(out),
                                                   None if lse is None else _lib.ptr(lse), None if rank is None else _lib.ptr(rank),
                                                   _lib.stream_ptr(logits)),
@@ -109,8 +109,8 @@ def top_logprobs(logits: torch.Tensor, k: int, targets: Optional[torch.Tensor] =
     _lib.require_gpu(logits, "logits")
     if targets is not None:
         _lib.require_gpu(targets, "targets")
-    if logits.dtype not in (torch.float16, torch.float32):
-        raise ValueError(f"logits must be (..., V) fp16 / fp32, got {tuple(logits.shape)} {logits.dtype}")
+    if logits.dtype not in _lib.LOGITS_BITS:
+        raise ValueError(f"logits must be (..., V) fp16 / bf16 / fp32, got {tuple(logits.shape)} {logits.dtype}")
     lead = logits.shape[:-1]
     if targets is not None and (targets.dtype != torch.int64 or targets.shape != lead or targets.device != logits.device):
         raise ValueError(f"targets must be int64 of shape {tuple(lead)} on {logits.device}, got {tuple(targets.shape)} {targets.dtype}")
@@ -130,7 +130,7 @@ def top_logprobs(logits: torch.Tensor, k: int, targets: Optional[torch.Tensor] =
         if targets is not None:
             targets = targets.contiguous()
         opt = lambda t: None if t is None else _lib.ptr(t)   # noqa: E731
-        _lib.check(_lib.load().kivi_token_top_logprobs(_lib.ptr(logits), 16 if logits.dtype == torch.float16 else 32, stride, N, V, k,
+        _lib.check(_lib.load().kivi_token_top_logprobs(_lib.ptr(logits), _lib.LOGITS_BITS[logits.dtype], stride, N, V, k,
                                                        opt(targets), 1, ignore_index, _lib.ptr(ids), _lib.ptr(top), k, opt(out),
                                                        opt(lse), opt(rank), _lib.stream_ptr(logits)),
                    "kivi_token_top_logprobs")
@@ -144,7 +144,7 @@ def score_into(logits: torch.Tensor, tokens: torch.Tensor, lp: torch.Tensor, top
     kivi_token_top_logprobs together with the lists -- the bits token_logprobs / top_logprobs give."""
     B, V = tokens.numel(), logits.shape[-1]
     assert logits.is_contiguous() and tokens.is_contiguous() and lp.is_contiguous() and logits.numel() == B * V
-    bits, lib = 16 if logits.dtype == torch.float16 else 32, _lib.load()
+    bits, lib = _lib.LOGITS_BITS[logits.dtype], _lib.load()
     if top_ids is None:
         _lib.check(lib.kivi_token_logprob(_lib.ptr(logits), bits, V, B, V, _lib.ptr(tokens), 1, -100, _lib.ptr(lp), None, None,
                                           _lib.stream_ptr(logits)), "kivi_token_logprob")
