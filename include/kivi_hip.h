@@ -1037,6 +1037,52 @@ int kivi_qkv_rope_bf16(const void* q_in, int64_t q_sb, int64_t q_st, int64_t q_s
                        int64_t k_sh, const void* v_in, int64_t v_sb, int64_t v_st, int64_t v_sh, const void* cos, const void* sin,
                        int64_t cs_sb, int64_t cs_st, const void* q_weight, const void* k_weight, float eps, void* q_out, void* k_out,
                        void* v_out, int B, int Q, int nh, int nh_kv, int Rp, int D, kivi_stream_t stream);
+/*
+ * The sparse mixture-of-experts feed-forward block (Mixtral, Qwen3-MoE).  Two entries, both launches only --
+ * no host read, no copy to the host -- so a stream capture may hold them.  N tokens, E experts, K = top_k experts per token; pair
+ * n * K + k is slot k of token n.  `dtype`: 16 (fp16) or KIVI_LOGITS_BF16 (bf16).
+ *
+ * kivi_moe_route
+ *   logits   (N, E) in the dtype, row n at logits + n * row_stride elements
+ *   flags    KIVI_MOE_NORM_TOPK: the K weights of a token are divided by their sum; KIVI_MOE_ROUND_WEIGHTS: see w
+ *   idx      (N, K) int32: the K largest LOGITS of the row, descending, equal logits (-0 equals +0) to the lower expert
+ *   w        (N, K) fp32: softmax over all E logits in fp32 (max subtracted, expf, one division by the sum) taken at idx; with
+ *            NORM_TOPK divided by the sum of the K, added in slot order; with ROUND_WEIGHTS rounded once to the dtype and stored as
+ *            that value's fp32 image (HF's Qwen3-MoE router casts the weights to the model dtype, Mixtral's does not)
+ *   counts   (E) int32 pairs per expert;  offsets (E + 1) their exclusive prefix sum
+ *   pairs    (N * K) int32 pair ids grouped by expert: expert e owns pairs[offsets[e] .. offsets[e + 1]), in no specified order
+ *   pos      (N, K) int32: pairs[pos[n, k]] == n * K + k
+ *   tiles    (kivi_moe_max_tiles(N, E, K), 3) int32 (expert, first row of `pairs`, rows <= KIVI_MOE_TOKEN_TILE): every expert's
+ *            segment cut into tiles, experts ascending; n_tiles: one int32, the number of entries written
+ * The host never learns the counts: kivi_moe_max_tiles = min(E, N * K) + N * K / KIVI_MOE_TOKEN_TILE bounds the tile count.
+ *
+ * kivi_moe_experts
+ *   x        (N, H) in the dtype, row stride x_stride elements (a multiple of 8), 16-byte aligned
+ *   w, pairs, pos, tiles, n_tiles   as kivi_moe_route left them for the same N, E, K
+ *   gate_up  (E, 2 I, H) contiguous, rows [0, I) of an expert its gate matrix, [I, 2 I) its up matrix;  down (E, H, I) contiguous
+ *   out      (N, H) in the dtype, row stride out_stride elements (a multiple of 4), 8-byte aligned; every element written once
+ *   workspace   kivi_moe_workspace_bytes(N, H, I, E, K) bytes, 16-byte aligned
+ * a = silu(x Wg^T) * (x Wu^T) per pair on the matrix pipe (fp32 accumulation), rounded once to the dtype; y = a Wd^T in fp32;
+ * out[n] = sum_k w[n, k] * y[pair n * K + k], fused multiply-adds in slot order k = 0 .. K - 1, rounded once.  No atomics on
+ * floating-point values.  The order in which a pair's sums are taken depends on H and I only: a token's output bits do not depend
+ * on N, on the other tokens or on where the plan put the pair.
+ *
+ * KIVI_EINVAL (nothing enqueued) for a dtype that is neither; N < 1; E outside [1, 256]; top_k outside [1, min(E, 16)];
+ * N * top_k >= 2^31; H or I not a positive multiple of 32 (or beyond 16 * 65535); unknown flags; a row stride smaller than the row;
+ * a null pointer; a workspace smaller than kivi_moe_workspace_bytes.  KIVI_EALIGN for a misaligned pointer or stride.
+ * kivi_moe_max_tiles / kivi_moe_workspace_bytes return KIVI_EINVAL (-1) for the same shapes.
+ */
+#define KIVI_MOE_TOKEN_TILE 16
+#define KIVI_MOE_NORM_TOPK 1
+#define KIVI_MOE_ROUND_WEIGHTS 2
+int kivi_moe_max_tiles(int N, int E, int top_k);
+int64_t kivi_moe_workspace_bytes(int N, int H, int I, int E, int top_k);
+int kivi_moe_route(const void* logits, int64_t row_stride, int dtype, int N, int E, int top_k, int flags, void* idx, void* w,
+                   void* counts, void* offsets, void* pairs, void* pos, void* tiles, void* n_tiles, kivi_stream_t stream);
+int kivi_moe_experts(const void* x, int64_t x_stride, int dtype, int N, int H, int I, int E, int top_k, const void* w,
+                     const void* pairs, const void* pos, const void* tiles, const void* n_tiles, const void* gate_up,
+                     const void* down, void* out, int64_t out_stride, void* workspace, int64_t workspace_bytes,
+                     kivi_stream_t stream);
 /* geometry class of a step (-1: bad arguments): the super-block counts of both stores and whether the step flushes a value; the
  * launch plan (one launch / S slices / two launches) is a function of the class and of constants of the call (shape, bits, flags) */
 int64_t kivi_mf_step_key(const kivi_mf_step* step, int B, int nh, int nh_kv, int residual_length, int flags);

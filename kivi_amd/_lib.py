@@ -125,6 +125,8 @@ SAMPLE_MAX_B = 65535      # include/kivi_hip.h: KIVI_SAMPLE_MAX_B, KIVI_SAMPLE_M
 SAMPLE_MAX_V = 1 << 20
 SAMPLE_MAX_LIST = 1024      # include/kivi_hip.h: KIVI_SAMPLE_MAX_LIST
 STOP_MAX_IDS, STOP_MAX_SEQS, STOP_MAX_LEN = 16, 8, 16    # include/kivi_hip.h: KIVI_STOP_MAX_*
+MOE_TOKEN_TILE, MOE_NORM_TOPK, MOE_ROUND_WEIGHTS = 16, 1, 2    # include/kivi_hip.h: KIVI_MOE_*
+MOE_MAX_E, MOE_MAX_K = 256, 16
 
 
 class ReorderSlab(ctypes.Structure):
@@ -214,6 +216,11 @@ SIGNATURES = {
                             _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "kivi_qkv_rope_bf16": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp,
                                   ctypes.c_float, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "kivi_moe_max_tiles": (_i32, [_i32, _i32, _i32]),
+    "kivi_moe_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "kivi_moe_route": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "kivi_moe_experts": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
+                                _vp]),
     "kivi_mf_step_key": (_i64, [ctypes.POINTER(MfStep), _i32, _i32, _i32, _i32, _i32]),
     "kivi_mf_step_advance": (_i32, [ctypes.POINTER(MfStep), _i32, _i64]),
     "kivi_mf_step_upload": (_i32, [ctypes.POINTER(MfStep), _vp, _vp]),

@@ -17,6 +17,7 @@ import glob
 import json
 import math
 import os
+import re
 from types import SimpleNamespace
 from typing import List, Optional
 
@@ -31,6 +32,7 @@ from .generation import (PADS_LEFT, DecodeLead, EagerStepper, _PaddedBatch, deco
                          padding_key_row, padding_position_ids, padding_prompt_mask, observe_prompts, bind_suppress,
                          resolve_sampler)
 from .graph import DecodeGraphs
+from .moe import SparseMoeBlock
 from .prefill import left_padded
 from .sampling import RowSampler
 from .scoring import check_top_k, check_top_logprobs, token_logprobs
@@ -38,15 +40,28 @@ from .scoring import top_logprobs as scoring_top_logprobs
 from .stopping import SYNC_EVERY, StopRows, check_sync_every, resolve_stopping
 
 
+_SHARED_EXPERT_FIELDS = ("shared_expert_intermediate_size", "n_shared_experts", "num_shared_experts")
+
+
 def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32, residual_length: int = 32,
                 max_cache_len: Optional[int] = None, prefill_kernel: bool = False, decode_lead: bool = False,
-                qk_kernel: bool = False) -> SimpleNamespace:
+                qk_kernel: bool = False, moe_kernel: bool = True, moe_kernel_max_tokens: Optional[int] = None) -> SimpleNamespace:
     """HF config.json fields (+ the four KIVI fields) -> the namespace the modules read.  `prefill_kernel`: the prompt pass's
     attention runs kivi_prefill_attention, and every attention class serves left-padded prompts.
     `decode_lead`: the decode steps of a padded batch hand the kernels every row's leading pads, and the row kernels skip the packed
     K and V under them.  `qk_kernel`: q and k are prepared by one kivi_qk_rope launch per layer, and a model
-    whose nh / nh_kv the matrix-pipe layout does not serve runs on it with padded query groups."""
+    whose nh / nh_kv the matrix-pipe layout does not serve runs on it with padded query groups.
+    A sparse mixture-of-experts config (Mixtral: `num_local_experts`; Qwen3-MoE: `num_experts`) also carries
+    num_experts, num_experts_per_tok, moe_intermediate_size (Mixtral's `intermediate_size`), norm_topk_prob (always true for
+    Mixtral), decoder_sparse_step and mlp_only_layers; `moe_kernel`: its routed blocks run kivi_moe_route / kivi_moe_experts, for at
+    most `moe_kernel_max_tokens` tokens outside a capture (None: kivi_amd.moe.KERNEL_MAX_TOKENS).  Shared experts are refused."""
     hidden, heads = d["hidden_size"], d["num_attention_heads"]
+    for field in _SHARED_EXPERT_FIELDS:
+        if d.get(field):
+            raise ValueError(f"config field `{field}` = {d[field]!r} asks for a shared expert, which the sparse block here does not "
+                             f"have (Qwen2-MoE, DeepSeek): only routed experts are served")
+    mixtral = "num_local_experts" in d or d.get("model_type") == "mixtral"
+    num_experts = int(d.get("num_local_experts", d.get("num_experts", 0)) or 0)
     return SimpleNamespace(
         hidden_size=hidden, num_attention_heads=heads, num_key_value_heads=d.get("num_key_value_heads", heads),
         num_hidden_layers=d["num_hidden_layers"], intermediate_size=d["intermediate_size"], vocab_size=d["vocab_size"],
@@ -58,7 +73,12 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
         residual_length=d.get("residual_length", residual_length),
         kivi_max_cache_len=max_cache_len,   # opt-in reservation; by default the cache starts prompt-sized and doubles
         kivi_prefill_kernel=bool(prefill_kernel), kivi_decode_lead=bool(decode_lead), kivi_qk_kernel=bool(qk_kernel),
-        model_type=d.get("model_type"), use_sliding_window=bool(d.get("use_sliding_window", False)))
+        model_type=d.get("model_type"), use_sliding_window=bool(d.get("use_sliding_window", False)),
+        num_experts=num_experts, num_experts_per_tok=int(d.get("num_experts_per_tok", 2 if mixtral else 8)),
+        moe_intermediate_size=d["intermediate_size"] if mixtral else d.get("moe_intermediate_size", d["intermediate_size"]),
+        norm_topk_prob=True if mixtral else bool(d.get("norm_topk_prob", False)),
+        decoder_sparse_step=int(d.get("decoder_sparse_step", 1) or 1), mlp_only_layers=list(d.get("mlp_only_layers") or []),
+        kivi_moe_kernel=bool(moe_kernel), kivi_moe_kernel_max_tokens=moe_kernel_max_tokens)
 
 
 class RMSNorm(nn.Module):
@@ -82,11 +102,28 @@ class MLP(nn.Module):
         return self.down_proj(F.silu(self.gate_proj(x)) * self.up_proj(x))
 
 
+def layer_is_sparse(cfg, layer_idx: int) -> bool:
+    """HF's rule (Qwen3MoeDecoderLayer): a layer carries the routed block when the config has experts, the layer is not in
+    `mlp_only_layers` and (layer_idx + 1) is a multiple of `decoder_sparse_step`; Mixtral has neither field: every layer is sparse."""
+    return (getattr(cfg, "num_experts", 0) > 0 and layer_idx not in getattr(cfg, "mlp_only_layers", ())
+            and (layer_idx + 1) % getattr(cfg, "decoder_sparse_step", 1) == 0)
+
+
+def make_mlp(cfg, layer_idx: int) -> nn.Module:
+    """The feed-forward block of a layer: the dense SwiGLU MLP, or the sparse block of kivi_amd/moe.py."""
+    if not layer_is_sparse(cfg, layer_idx):
+        return MLP(cfg)
+    return SparseMoeBlock(cfg.hidden_size, cfg.moe_intermediate_size, cfg.num_experts, cfg.num_experts_per_tok,
+                          norm_topk=cfg.norm_topk_prob, round_weights=getattr(cfg, "kivi_moe_round_weights", False),
+                          kernel=getattr(cfg, "kivi_moe_kernel", True),
+                          kernel_max_tokens=getattr(cfg, "kivi_moe_kernel_max_tokens", None))
+
+
 class DecoderLayer_KIVI(nn.Module):
     def __init__(self, cfg, layer_idx: int, attention_cls=LlamaAttention_KIVI):
         super().__init__()
         self.self_attn = attention_cls(cfg, layer_idx)
-        self.mlp = MLP(cfg)
+        self.mlp = make_mlp(cfg, layer_idx)     # the attribute stays `mlp` for either kind: DecodeGraphs calls layer.mlp
         self.input_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
         self.post_attention_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
 
@@ -740,12 +777,16 @@ class LlamaForCausalLM_KIVI(nn.Module):
     @classmethod
     def from_pretrained(cls, path: str, device="cuda", dtype=torch.float16, **kivi):
         """`path`: a local HF checkpoint directory (config.json + *.safetensors).  `kivi`: k_bits, v_bits, group_size,
-        residual_length, max_cache_len, prefill_kernel, decode_lead, qk_kernel (default: the class's, on for the Qwen classes).
-        Called on LlamaForCausalLM_KIVI, a config.json whose `model_type` is qwen2 / qwen3 builds that family's class."""
+        residual_length, max_cache_len, prefill_kernel, decode_lead, qk_kernel (default: the class's, on for the Qwen classes),
+        moe_kernel, moe_kernel_max_tokens.
+        Called on LlamaForCausalLM_KIVI, a config.json whose `model_type` is qwen2 / qwen3 / mixtral / qwen3_moe builds that
+        family's class.  The experts of a sparse checkpoint are taken under HF's per-expert names or the fused ones of
+        transformers 5 (take_expert_weights), file by file: each expert is copied into the stacked parameter in turn."""
         from safetensors.torch import load_file
         d = json.load(open(os.path.join(path, "config.json")))
         if cls is LlamaForCausalLM_KIVI:
-            cls = {"qwen2": Qwen2ForCausalLM_KIVI, "qwen3": Qwen3ForCausalLM_KIVI}.get(d.get("model_type"), cls)
+            cls = {"qwen2": Qwen2ForCausalLM_KIVI, "qwen3": Qwen3ForCausalLM_KIVI, "mixtral": MixtralForCausalLM_KIVI,
+                   "qwen3_moe": Qwen3MoeForCausalLM_KIVI}.get(d.get("model_type"), cls)
         kivi.setdefault("qk_kernel", cls._QK_KERNEL)
         cfg = make_config(d, **kivi)
         with torch.device(device):
@@ -755,11 +796,14 @@ class LlamaForCausalLM_KIVI(nn.Module):
                 model = cls(cfg)
             finally:
                 torch.set_default_dtype(prev)
-        state = {}
+        state, filled = {}, {}
         for f in sorted(glob.glob(os.path.join(path, "*.safetensors"))):
-            state.update(load_file(f, device=str(device)))
+            part = load_file(f, device=str(device))
+            take_expert_weights(model, part, filled)        # pops the expert tensors of this file: they die with `part`
+            state.update(part)
         missing, unexpected = model.load_state_dict(state, strict=False)
-        missing = [m for m in missing if "inv_freq" not in m and not (cfg.tie_word_embeddings and m == "lm_head.weight")]
+        missing = [m for m in missing if "inv_freq" not in m and not (cfg.tie_word_embeddings and m == "lm_head.weight")
+                   and not expert_weight_filled(model, m, filled)]
         if missing:
             raise KeyError(f"checkpoint lacks {missing[:5]}{' ...' if len(missing) > 5 else ''}")
         return model
@@ -773,6 +817,15 @@ class MistralForCausalLM_KIVI(LlamaForCausalLM_KIVI):
     def __init__(self, config, attention_cls=None):
         from .attention import MistralAttention_KIVI
         super().__init__(config, attention_cls or MistralAttention_KIVI)
+
+
+class MixtralForCausalLM_KIVI(MistralForCausalLM_KIVI):
+    """HF's MixtralForCausalLM: Mistral's attention block (32 / 8 heads) and, in every layer, the sparse block of kivi_amd/moe.py in
+    place of the MLP: `num_local_experts` experts of `intermediate_size`, `num_experts_per_tok` per token,
+    the weights of a token always normalised over its experts and kept in fp32."""
+
+    def __init__(self, config, attention_cls=None):
+        super().__init__(SimpleNamespace(**{**vars(config), "kivi_moe_round_weights": False, "norm_topk_prob": True}), attention_cls)
 
 
 class Qwen2ForCausalLM_KIVI(LlamaForCausalLM_KIVI):
@@ -797,3 +850,54 @@ class Qwen3ForCausalLM_KIVI(Qwen2ForCausalLM_KIVI):
     over head_dim on every head of q and k before RoPE (checkpoint names self_attn.q_norm.weight / self_attn.k_norm.weight)."""
 
     _HEAD_NORM = True
+
+
+class Qwen3MoeForCausalLM_KIVI(Qwen3ForCausalLM_KIVI):
+    """HF's Qwen3MoeForCausalLM: Qwen3's attention block (head norms, head_dim 128) and the sparse block of kivi_amd/moe.py in the
+    layers HF's rule names (layer_is_sparse), the dense MLP of `intermediate_size` in the others.  The
+    router's weights are rounded to the model dtype, as HF's Qwen3MoeTopKRouter casts them."""
+
+    def __init__(self, config, attention_cls=None):
+        super().__init__(SimpleNamespace(**{**vars(config), "kivi_moe_round_weights": True}), attention_cls)
+
+
+# ---------------------------------------------------------------------- expert weights of a checkpoint (DESIGN.md section 29)
+_EXPERT_NAME = re.compile(r"^(.*\.)(?:block_sparse_moe|mlp)\.experts\.(\d+)\.(w1|w2|w3|gate_proj|up_proj|down_proj)\.weight$")
+_EXPERT_PART = {"w1": "gate", "gate_proj": "gate", "w3": "up", "up_proj": "up", "w2": "down", "down_proj": "down"}
+
+
+def take_expert_weights(model: nn.Module, state: dict, filled: dict) -> dict:
+    """Move what `state` holds of the sparse blocks' weights into `model`, and out of `state` where that is a per-expert tensor.
+    Three spellings are taken: Mixtral's `block_sparse_moe.gate.weight` and `block_sparse_moe.experts.{e}.w1 / w3 / w2.weight`
+    (gate / up / down), Qwen3-MoE's `mlp.experts.{e}.gate_proj / up_proj / down_proj.weight`, and the fused names of transformers 5
+    (`mlp.experts.gate_up_proj` / `.down_proj`, also under `block_sparse_moe.`), which stay in `state` under the module's names for
+    load_state_dict.  A per-expert tensor is copied into its rows of the stacked parameter and popped: no second copy of the
+    experts is ever assembled.  `filled`: stacked parameter name -> number of pieces copied so far (updated and returned)."""
+    params = dict(model.named_parameters())
+    for name in list(state):
+        m = _EXPERT_NAME.match(name)
+        if m is None:
+            if ".block_sparse_moe." in name:
+                state[name.replace(".block_sparse_moe.", ".mlp.")] = state.pop(name)
+            continue
+        prefix, e, part = m.group(1), int(m.group(2)), _EXPERT_PART[m.group(3)]
+        target = f"{prefix}mlp.experts.{'down_proj' if part == 'down' else 'gate_up_proj'}"
+        if target not in params:
+            continue                                        # load_state_dict reports the name as unexpected
+        t, p = state.pop(name), params[target]
+        inter = p.shape[2] if part == "down" else p.shape[1] // 2
+        want = (p.shape[1], p.shape[2]) if part == "down" else (inter, p.shape[2])
+        if e >= p.shape[0] or tuple(t.shape) != want:
+            raise ValueError(f"{name}: shape {tuple(t.shape)} does not fit {target} {tuple(p.shape)}")
+        rows = p.data[e] if part == "down" else p.data[e, :inter] if part == "gate" else p.data[e, inter:]
+        rows.copy_(t)
+        filled[target] = filled.get(target, 0) + 1
+    return filled
+
+
+def expert_weight_filled(model: nn.Module, name: str, filled: dict) -> bool:
+    """True when every piece of the stacked expert parameter `name` has been copied by take_expert_weights."""
+    if name not in filled:
+        return False
+    p = dict(model.named_parameters())[name]
+    return filled[name] == p.shape[0] * (1 if name.endswith("down_proj") else 2)

@@ -1,0 +1,231 @@
+"""The sparse mixture-of-experts feed-forward block of Mixtral / Qwen3-MoE: a router over E experts, K of them
+per token, each a SwiGLU MLP.  `route` / `experts` are the two HIP entries kivi_moe_route / kivi_moe_experts
+(kivi_amd/csrc/kivi_moe.hip): launches only, nothing is read back, so a captured decode step may hold them.  `route_torch` /
+`experts_torch` state the same contract in torch -- the per-expert loop of the Hugging Face modules, whose `nonzero` / `where`
+synchronise with the host -- for tensors off the GPU, shapes the kernels refuse and passes of many tokens.  `SparseMoeBlock` is the
+module the decoder layers carry as `mlp`.
+
+The contract: token n's experts are the K largest router LOGITS, descending, equal logits to the lower expert (a choice that is
+decidable from the inputs; HF's top-k over the fp32 probabilities picks the same experts wherever two probabilities differ); its
+weights are the fp32 softmax over all E logits at those experts, divided by their sum with `norm_topk`, rounded once to the logits'
+dtype with `round_weights`; out[n] = sum_k w[n, k] * down_e(silu(gate_e(x[n])) * up_e(x[n])), e = idx[n, k]."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+
+TOKEN_TILE = _lib.MOE_TOKEN_TILE        # pairs per tile of the grouped plan: include/kivi_hip.h, KIVI_MOE_TOKEN_TILE
+MAX_EXPERTS, MAX_TOP_K = _lib.MOE_MAX_E, _lib.MOE_MAX_K
+# Eager calls of more tokens than this take the torch loop (its GEMMs run on rocBLAS; a prompt pass of thousands of tokens belongs
+# there).  The largest power of two at which tools/moe_time.py measured the kernels no slower than the loop at BOTH published
+# geometries (profiles/moe_time.log, MI355X): at N = 64 they are 1.6-1.85x (Mixtral-8x7B) and 58-61x (Qwen3-30B-A3B) ahead, at the
+# next measured size, 256, Mixtral's bf16 run is behind (0.84x; fp16 1.02x) while Qwen3's stay 38-44x ahead: a Qwen3-MoE user
+# may raise it.
+KERNEL_MAX_TOKENS = 64
+_DTYPES = {torch.float16: 16, torch.bfloat16: _lib.LOGITS_BF16}
+
+
+@dataclass
+class MoePlan:
+    """What route leaves on the device.  idx (N, K) int32, w (N, K) fp32; the grouped plan: counts (E), offsets (E + 1), pairs (N * K)
+    -- pair id n * K + k, grouped by expert, in no specified order inside an expert --, pos (N, K) with pairs[pos[n, k]] == n * K + k,
+    tiles (max_tiles, 3) rows (expert, first row of pairs, rows <= TOKEN_TILE) of which the first n_tiles[0] are written
+    (route_torch leaves tiles / n_tiles None)."""
+    idx: torch.Tensor
+    w: torch.Tensor
+    counts: torch.Tensor
+    offsets: torch.Tensor
+    pairs: torch.Tensor
+    pos: torch.Tensor
+    tiles: Optional[torch.Tensor]
+    n_tiles: Optional[torch.Tensor]
+    num_experts: int
+
+    @property
+    def top_k(self) -> int:
+        return self.idx.shape[1]
+
+
+def max_tiles(n_tokens: int, num_experts: int, top_k: int) -> int:
+    """The bound the expert launches are sized by: min(E, N * K) + N * K // TOKEN_TILE (kivi_amd/csrc/kivi_moe_plan.h)."""
+    return min(num_experts, n_tokens * top_k) + n_tokens * top_k // TOKEN_TILE
+
+
+def _check_route(logits: torch.Tensor, top_k: int, what: str):
+    if logits.dim() != 2 or logits.shape[0] < 1:
+        raise ValueError(f"{what}: logits must be (N >= 1, E), got {tuple(logits.shape)}")
+    E = logits.shape[1]
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= E:
+        raise ValueError(f"{what}: top_k has to be an integer in [1, E = {E}], got {top_k!r}")
+
+
+def usable(x: torch.Tensor, num_experts: int, top_k: int, hidden: int, intermediate: int) -> bool:
+    """True where the kernels serve: fp16 or bf16 on the GPU, E <= 256, K <= min(E, 16), H and I multiples of 32, N * K < 2^31."""
+    n = x.numel() // max(hidden, 1)
+    return (x.is_cuda and x.dtype in _DTYPES and 1 <= num_experts <= MAX_EXPERTS and 1 <= top_k <= min(num_experts, MAX_TOP_K)
+            and hidden >= 32 and hidden % 32 == 0 and intermediate >= 32 and intermediate % 32 == 0 and 1 <= n
+            and n * top_k < 2 ** 31 and hidden <= 16 * 65535 and intermediate <= 16 * 65535)
+
+
+def route_torch(logits: torch.Tensor, top_k: int, norm_topk: bool = True, round_weights: bool = False) -> MoePlan:
+    """The contract of kivi_moe_route in torch, any dtype and device: a stable descending sort of the logits, the fp32 softmax (fp64
+    for fp64 logits), the grouped plan by a stable sort of the pairs' experts (no tile list)."""
+    _check_route(logits, top_k, "route_torch")
+    N, E = logits.shape
+    wide = logits if logits.dtype == torch.float64 else logits.float()
+    idx = torch.sort(wide + 0.0, dim=-1, descending=True, stable=True).indices[:, :top_k]
+    w = torch.softmax(wide, dim=-1).gather(1, idx)
+    if norm_topk:
+        w = w / w.sum(-1, keepdim=True)
+    if round_weights:
+        w = w.to(logits.dtype).to(wide.dtype)
+    flat = idx.reshape(-1)
+    counts = torch.zeros(E, dtype=torch.int64, device=logits.device).scatter_add_(0, flat, torch.ones_like(flat))
+    offsets = torch.cat([counts.new_zeros(1), counts.cumsum(0)])
+    pairs = torch.sort(flat, stable=True).indices
+    pos = torch.empty_like(pairs).scatter_(0, pairs, torch.arange(N * top_k, device=logits.device))
+    return MoePlan(idx.int(), w, counts.int(), offsets.int(), pairs.int(), pos.view(N, top_k).int(), None, None, E)
+
+
+def experts_torch(x: torch.Tensor, plan: MoePlan, gate_up: torch.Tensor, down: torch.Tensor) -> torch.Tensor:
+    """The expert stage in torch, statement for statement the loop of HF's MixtralExperts / Qwen3MoeExperts: for every expert that
+    received a pair, its tokens through gate_up and down in x's dtype, times the weight, index_add_ into the result.  x (N, H),
+    gate_up (E, 2 I, H), down (E, H, I) -> (N, H).  Synchronises (nonzero / where)."""
+    E = gate_up.shape[0]
+    out = torch.zeros_like(x)
+    idx, w = plan.idx.long(), plan.w
+    mask = F.one_hot(idx, num_classes=E).permute(2, 1, 0)
+    hit = torch.greater(mask.sum(dim=(-1, -2)), 0).nonzero()
+    for e in hit:
+        e = e[0]
+        k_pos, tok = torch.where(mask[e])
+        g, u = F.linear(x[tok], gate_up[e]).chunk(2, dim=-1)
+        y = F.linear(F.silu(g) * u, down[e])
+        y = y * w[tok, k_pos, None]
+        out.index_add_(0, tok, y.to(out.dtype))
+    return out
+
+
+def route(logits: torch.Tensor, top_k: int, norm_topk: bool = True, round_weights: bool = False) -> MoePlan:
+    """One kivi_moe_route call (a memset and two launches on the current stream).  logits (N, E) fp16 or bf16 on the GPU with unit
+    expert stride (a view with a row stride is read as it is)."""
+    _check_route(logits, top_k, "kivi_moe_route")
+    _lib.require_gpu(logits, "logits")
+    if logits.dtype not in _DTYPES or logits.stride(1) != 1:
+        raise ValueError(f"kivi_moe_route: logits must be fp16 or bf16 with unit expert stride, got {logits.dtype}, strides "
+                         f"{logits.stride()}")
+    N, E = logits.shape
+    if E > MAX_EXPERTS or top_k > MAX_TOP_K or N * top_k >= 2 ** 31:
+        raise ValueError(f"kivi_moe_route: E = {E} (<= {MAX_EXPERTS}), top_k = {top_k} (<= {MAX_TOP_K}), N * top_k = {N * top_k} "
+                         f"(< 2^31)")
+    dev = logits.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    plan = MoePlan(torch.empty((N, top_k), **i32), torch.empty((N, top_k), dtype=torch.float32, device=dev), torch.empty(E, **i32),
+                   torch.empty(E + 1, **i32), torch.empty(N * top_k, **i32), torch.empty((N, top_k), **i32),
+                   torch.empty((max_tiles(N, E, top_k), 3), **i32), torch.empty(1, **i32), E)
+    flags = (_lib.MOE_NORM_TOPK if norm_topk else 0) | (_lib.MOE_ROUND_WEIGHTS if round_weights else 0)
+    rc = _lib.load().kivi_moe_route(
+        logits.data_ptr(), logits.stride(0), _DTYPES[logits.dtype], N, E, top_k, flags, plan.idx.data_ptr(), plan.w.data_ptr(),
+        plan.counts.data_ptr(), plan.offsets.data_ptr(), plan.pairs.data_ptr(), plan.pos.data_ptr(), plan.tiles.data_ptr(),
+        plan.n_tiles.data_ptr(), _lib.stream_ptr(logits))
+    _lib.check(rc, "kivi_moe_route")
+    return plan
+
+
+def experts(x: torch.Tensor, plan: MoePlan, gate_up: torch.Tensor, down: torch.Tensor, out: Optional[torch.Tensor] = None
+            ) -> torch.Tensor:
+    """One kivi_moe_experts call (three launches).  x (N, H) with unit channel stride, gate_up (E, 2 I, H) and down (E, H, I)
+    contiguous, all of one dtype (fp16 or bf16) on the GPU; `plan`: route's for the same N.  -> (N, H) in the dtype; `out`: a
+    contiguous buffer of that shape to write into.  The workspace (N * K rows of I activations and of H fp32 outputs) is allocated
+    per call: under capture it belongs to the graph's pool."""
+    for t, name in ((x, "x"), (gate_up, "gate_up"), (down, "down")):
+        _lib.require_gpu(t, name)
+    if x.dim() != 2 or gate_up.dim() != 3 or down.dim() != 3:
+        raise ValueError(f"kivi_moe_experts: x (N, H), gate_up (E, 2 I, H), down (E, H, I), got {tuple(x.shape)}, "
+                         f"{tuple(gate_up.shape)}, {tuple(down.shape)}")
+    N, H = x.shape
+    E, I = down.shape[0], down.shape[2]
+    if tuple(gate_up.shape) != (E, 2 * I, H) or tuple(down.shape) != (E, H, I) or E != plan.num_experts:
+        raise ValueError(f"kivi_moe_experts: x {tuple(x.shape)}, gate_up {tuple(gate_up.shape)}, down {tuple(down.shape)} and a plan "
+                         f"over {plan.num_experts} experts do not go together")
+    if x.dtype not in _DTYPES or gate_up.dtype != x.dtype or down.dtype != x.dtype:
+        raise ValueError(f"kivi_moe_experts: x, gate_up and down share one dtype, fp16 or bf16, got {x.dtype}, {gate_up.dtype}, "
+                         f"{down.dtype}")
+    if not gate_up.is_contiguous() or not down.is_contiguous() or x.stride(1) != 1:
+        raise ValueError("kivi_moe_experts: gate_up and down must be contiguous, x of unit channel stride")
+    if plan.tiles is None or tuple(plan.idx.shape) != (N, plan.top_k) or not plan.idx.is_cuda:
+        raise ValueError(f"kivi_moe_experts: the plan must be route()'s for these {N} tokens")
+    if x.stride(0) % 8 or x.data_ptr() % 16:
+        x = x.contiguous()
+    if out is None:
+        out = torch.empty((N, H), dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (N, H) or out.dtype != x.dtype or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"kivi_moe_experts: out must be contiguous {x.dtype} {(N, H)} on the GPU")
+    lib = _lib.load()
+    K = plan.top_k
+    nbytes = lib.kivi_moe_workspace_bytes(N, H, I, E, K)
+    if nbytes < 0:
+        _lib.check(-1, "kivi_moe_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    rc = lib.kivi_moe_experts(
+        x.data_ptr(), x.stride(0), _DTYPES[x.dtype], N, H, I, E, K, plan.w.data_ptr(), plan.pairs.data_ptr(), plan.pos.data_ptr(),
+        plan.tiles.data_ptr(), plan.n_tiles.data_ptr(), gate_up.data_ptr(), down.data_ptr(), out.data_ptr(), out.stride(0),
+        ws.data_ptr(), nbytes, _lib.stream_ptr(x))
+    _lib.check(rc, "kivi_moe_experts")
+    return out
+
+
+class _Router(nn.Module):
+    def __init__(self, num_experts: int, hidden: int):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(num_experts, hidden))
+
+
+class _Experts(nn.Module):
+    """The stacked expert weights under the names of transformers 5: gate_up_proj (E, 2 I, H), down_proj (E, H, I)."""
+
+    def __init__(self, num_experts: int, hidden: int, intermediate: int):
+        super().__init__()
+        self.gate_up_proj = nn.Parameter(torch.empty(num_experts, 2 * intermediate, hidden))
+        self.down_proj = nn.Parameter(torch.empty(num_experts, hidden, intermediate))
+
+
+class SparseMoeBlock(nn.Module):
+    """HF's MixtralSparseMoeBlock / Qwen3MoeSparseMoeBlock: gate.weight (E, H), experts.gate_up_proj, experts.down_proj.  The
+    router GEMM is F.linear.  `kernel`: route and experts run the HIP entries -- always under stream capture, where the torch loop
+    cannot run, and for at most `kernel_max_tokens` tokens otherwise; what the kernels do not serve (usable) takes the torch loop."""
+
+    def __init__(self, hidden: int, intermediate: int, num_experts: int, top_k: int, norm_topk: bool = True,
+                 round_weights: bool = False, kernel: bool = True, kernel_max_tokens: Optional[int] = None):
+        super().__init__()
+        if not 1 <= top_k <= num_experts:
+            raise ValueError(f"num_experts_per_tok = {top_k} outside [1, num_experts = {num_experts}]")
+        self.hidden, self.intermediate, self.num_experts, self.top_k = hidden, intermediate, num_experts, top_k
+        self.norm_topk, self.round_weights = bool(norm_topk), bool(round_weights)
+        self.kernel = bool(kernel)
+        self.kernel_max_tokens = KERNEL_MAX_TOKENS if kernel_max_tokens is None else int(kernel_max_tokens)
+        self.gate = _Router(num_experts, hidden)
+        self.experts = _Experts(num_experts, hidden, intermediate)
+        for p in self.parameters():
+            nn.init.normal_(p, 0.0, 0.02)
+
+    def uses_kernel(self, x2: torch.Tensor) -> bool:
+        if not self.kernel or not usable(x2, self.num_experts, self.top_k, self.hidden, self.intermediate):
+            return False
+        return torch.cuda.is_current_stream_capturing() or x2.shape[0] <= self.kernel_max_tokens
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        B, Q, H = x.shape
+        x2 = x.reshape(B * Q, H)
+        logits = F.linear(x2, self.gate.weight)
+        if self.uses_kernel(x2):
+            plan = route(logits, self.top_k, self.norm_topk, self.round_weights)
+            return experts(x2, plan, self.experts.gate_up_proj, self.experts.down_proj).view(B, Q, H)
+        plan = route_torch(logits, self.top_k, self.norm_topk, self.round_weights)
+        return experts_torch(x2, plan, self.experts.gate_up_proj, self.experts.down_proj).view(B, Q, H)
