@@ -1083,6 +1083,42 @@ int kivi_moe_experts(const void* x, int64_t x_stride, int dtype, int N, int H, i
                      const void* pairs, const void* pos, const void* tiles, const void* n_tiles, const void* gate_up,
                      const void* down, void* out, int64_t out_stride, void* workspace, int64_t workspace_bytes,
                      kivi_stream_t stream);
+/*
+ * Weight-only 4-bit dense layers.  A weight W (O, K) is quantised in groups of G in {64, 128} along K:
+ * codes, scale and mn are exactly what the reference's last-dim quantiser (quant/new_pack.py:217-252 at 4 bits; kivi_quant.h) gives
+ * for the FP16 IMAGE of W viewed as (1, 1, O, K) -- a bf16 weight is rounded once to fp16 first --, degenerate groups (constant,
+ * inf, NaN) resolving as kivi_quant.h documents; scale and mn are fp16 for fp16 and bf16 models alike.  The represented weight is the
+ * real number W~[o, k] = code * scale + mn.  `dtype`: 16 (fp16) or KIVI_LOGITS_BF16 (bf16).
+ *
+ * Layout "WT4" (kivi_amd/csrc/kivi_mfma_layout.h): tiles of 16 rows x 128 reduction elements, 256 int32 words each, the K / 128
+ * tiles of a 16-row stripe contiguous.  Element (o, k): tile (o / 16) * (K / 128) + k / 128, and with kk = k % 128 word
+ * ((o % 16) + 16 * ((kk >> 3) & 3)) * 4 + (kk >> 5) of the tile, bits 4 * ((k & 7) >> 1) + 16 * (k & 1).
+ *   qweight  O * K / 8 int32;   scales, mins  O * K / G halves each: (row o, group g) at ((o / 16) * (K / G) + g) * 16 + o % 16
+ *
+ * kivi_w4_pack      w (O, K) in the dtype, row stride w_stride elements -> qweight, scales, mins.  W is read once.
+ * kivi_w4_dequant   out[o, k] = round_to_dtype(fmaf(code, scale, mn)), the fused multiply-add in fp32; row stride out_stride
+ * kivi_w4_linear    y[n, o] = sum_k x[n, k] * W~[o, k] (+ bias[o]): accumulated in fp32, rounded once to the dtype.  x (N, K) by
+ *                   x_stride, y (N, O) by y_stride, bias (O) in the dtype or null.  Any N >= 1: tokens go through in chunks of 64
+ *                   (kivi_w4_gate_up: of 32), one pass over the stripe's codes per chunk.
+ * kivi_w4_gate_up   y[n, i] = silu(g) * u with g, u the two linears of the gate and the up matrix (I, K) in fp32, rounded once
+ * Launches only: a stream capture may hold them.  The order in which a token's sums are taken depends on K and G only, not on N, on
+ * the token's position or on the other tokens; no atomics.
+ *
+ * KIVI_EINVAL (nothing enqueued) for a dtype that is neither; O not a positive multiple of 16; K not a positive multiple of 128;
+ * group not 64 or 128; N < 1 or N * O >= 2^31; a row stride smaller than the row; a null pointer (bias may be null).  KIVI_EALIGN
+ * for x, w, out or qweight off 16 bytes, scales, mins or y off 8, a stride of x, w or out that is not a multiple of 8 elements,
+ * of y not of 4.  kivi_w4_bytes: the bytes of the three buffers together, O * K / 2 + 4 * O * K / G (KIVI_EINVAL for such a shape).
+ */
+int64_t kivi_w4_bytes(int O, int K, int group);
+int kivi_w4_pack(const void* w, int64_t w_stride, int dtype, int O, int K, int group, void* qweight, void* scales, void* mins,
+                 kivi_stream_t stream);
+int kivi_w4_dequant(const void* qweight, const void* scales, const void* mins, int O, int K, int group, int dtype, void* out,
+                    int64_t out_stride, kivi_stream_t stream);
+int kivi_w4_linear(const void* x, int64_t x_stride, int dtype, int N, int O, int K, int group, const void* qweight,
+                   const void* scales, const void* mins, const void* bias, void* y, int64_t y_stride, kivi_stream_t stream);
+int kivi_w4_gate_up(const void* x, int64_t x_stride, int dtype, int N, int I, int K, int group, const void* gate_qweight,
+                    const void* gate_scales, const void* gate_mins, const void* up_qweight, const void* up_scales,
+                    const void* up_mins, void* y, int64_t y_stride, kivi_stream_t stream);
 /* geometry class of a step (-1: bad arguments): the super-block counts of both stores and whether the step flushes a value; the
  * launch plan (one launch / S slices / two launches) is a function of the class and of constants of the call (shape, bits, flags) */
 int64_t kivi_mf_step_key(const kivi_mf_step* step, int B, int nh, int nh_kv, int residual_length, int flags);

@@ -24,6 +24,7 @@ from . import prefill as _prefill
 from . import qkrope as _qkrope
 from .cache import KiviCacheTuple, KiviConfig, KiviLayerCache, KiviPerformanceWarning  # noqa: F401
 from .cache_mf import KiviLayerCacheMF, make_layer_cache, padded_heads as _padded_heads, supported as _mf_supported
+from .wquant import make_linear
 
 __all__ = ["kivi_attention_decode", "kivi_attention_prefill", "LlamaAttention_KIVI", "LlamaFlashAttention_KIVI",
            "MistralAttention_KIVI", "MistralFlashAttention_KIVI", "QwenAttention_KIVI",
@@ -184,10 +185,11 @@ class LlamaAttention_KIVI(nn.Module):
         if self.head_dim * self.num_heads != self.hidden_size and getattr(config, "head_dim", None) is None:
             raise ValueError("hidden_size must be divisible by num_heads")
         bias = getattr(config, "attention_bias", False)
-        self.q_proj = nn.Linear(self.hidden_size, self.num_heads * self.head_dim, bias=bias)
-        self.k_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=bias)
-        self.v_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=bias)
-        self.o_proj = nn.Linear(self.num_heads * self.head_dim, self.hidden_size, bias=bias)
+        # nn.Linear, or with config.kivi_weight_bits == 4 the 4-bit QuantLinear
+        self.q_proj = make_linear(config, self.hidden_size, self.num_heads * self.head_dim, bias=bias)
+        self.k_proj = make_linear(config, self.hidden_size, self.num_key_value_heads * self.head_dim, bias=bias)
+        self.v_proj = make_linear(config, self.hidden_size, self.num_key_value_heads * self.head_dim, bias=bias)
+        self.o_proj = make_linear(config, self.num_heads * self.head_dim, self.hidden_size, bias=bias)
         self.register_buffer("inv_freq", _rope_inv_freq(config, self.head_dim, self.rope_theta), persistent=False)
         # config.kivi_qk_kernel (off by default): q / k are prepared by one kivi_qk_rope launch, and a query-group
         # ratio the matrix-pipe layout does not serve runs on it padded: `cache_heads` query heads, nh_kv * the padded ratio
@@ -415,7 +417,7 @@ class QwenAttention_KIVI(LlamaAttention_KIVI):
             raise ValueError("use_sliding_window=True: the quantised KV history has no sliding window; load the model with "
                              "use_sliding_window=false (full attention) or do not use this cache")
         super().__init__(config, layer_idx)
-        self.o_proj = nn.Linear(self.num_heads * self.head_dim, self.hidden_size, bias=False)
+        self.o_proj = make_linear(config, self.num_heads * self.head_dim, self.hidden_size, bias=False)
         if getattr(config, "kivi_head_norm", False):
             eps = getattr(config, "rms_norm_eps", 1e-6)
             self.q_norm, self.k_norm = HeadRMSNorm(self.head_dim, eps), HeadRMSNorm(self.head_dim, eps)

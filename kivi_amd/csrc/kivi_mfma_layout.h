@@ -90,6 +90,16 @@
 // B operand: register i = shift_i(w) & 0x03C003C0 with shift = << 6, << 2, >> 2, >> 6: every code on mantissa bits 9:6 of an fp16
 // subnormal = code * 2^-18, ONE exponent for the four registers: the A operand carries 2^6 throughout (aexp), a product is
 // a * code * 2^-12 as for 2 bits; the centre of a code is -7.5.
+//
+// ---- 4-bit WEIGHTS ("WT4"; kivi_w4.hip): the KT4 word for a dense weight W (O, K) quantised along K.  A tile is
+// 16 output rows x 128 reduction elements = 256 words = 1 KiB = one 16-byte load per lane; the K / 128 tiles of a 16-row stripe are
+// contiguous (a block streams K / 128 consecutive KiB).  Row o, element k, kk = k % 128, kb = (kk >> 3) & 3, j = kk >> 5, e = k & 7:
+//        tile (o / 16) * (K / 128) + k / 128, word ((o % 16) + 16 kb) * 4 + j, bits 4 (e >> 1) + 16 (e & 1)
+// i.e. lane r + 16 kb holds in word j the 8 elements 32 j + 8 kb + e of row r: word j IS the A operand of the tile's step j of
+// v_mfma_f32_16x16x32 after the KT4 views above (fp16: shift_i(w) & 0x03C003C0 = code * 2^-18; bf16: ((w >> 4 i) & 0x000F000F) |
+// 0x43004300 = 128 + code, exact).  scale / mn of (row o, group g of G in {64, 128} elements): half ((o / 16) * (K / G) + g) * 16 +
+// o % 16 of their buffers -- the lane holding result rows 4 q .. 4 q + 3 (q = lane >> 4) fetches their four values with one 8-byte
+// load per buffer and group.  The formulas as host code: kivi_w4_plan.h (kivi_w4_plan_word / _bit / _sm_half).
 #define KIVI_MF4_BLOCK_WORDS 512
 #define KIVI_MF4_SB_SCALE_WORD0 8192
 #define KIVI_MF4_SB_MN_WORD0 9216

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import admit
+from . import admit, wquant
 from .attention import KiviLayerCacheMF, LlamaAttention_KIVI
 from .beam import beam_search
 from .generation import (PADS_LEFT, DecodeLead, EagerStepper, _PaddedBatch, decode_loop, leading_pads, left_pad,  # noqa: F401
@@ -45,7 +45,9 @@ _SHARED_EXPERT_FIELDS = ("shared_expert_intermediate_size", "n_shared_experts", 
 
 def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32, residual_length: int = 32,
                 max_cache_len: Optional[int] = None, prefill_kernel: bool = False, decode_lead: bool = False,
-                qk_kernel: bool = False, moe_kernel: bool = True, moe_kernel_max_tokens: Optional[int] = None) -> SimpleNamespace:
+                qk_kernel: bool = False, moe_kernel: bool = True, moe_kernel_max_tokens: Optional[int] = None,
+                weight_bits: Optional[int] = None, weight_group: int = 128,
+                weight_kernel_max_tokens: Optional[int] = None) -> SimpleNamespace:
     """HF config.json fields (+ the four KIVI fields) -> the namespace the modules read.  `prefill_kernel`: the prompt pass's
     attention runs kivi_prefill_attention, and every attention class serves left-padded prompts.
     `decode_lead`: the decode steps of a padded batch hand the kernels every row's leading pads, and the row kernels skip the packed
@@ -54,7 +56,18 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
     A sparse mixture-of-experts config (Mixtral: `num_local_experts`; Qwen3-MoE: `num_experts`) also carries
     num_experts, num_experts_per_tok, moe_intermediate_size (Mixtral's `intermediate_size`), norm_topk_prob (always true for
     Mixtral), decoder_sparse_step and mlp_only_layers; `moe_kernel`: its routed blocks run kivi_moe_route / kivi_moe_experts, for at
-    most `moe_kernel_max_tokens` tokens outside a capture (None: kivi_amd.moe.KERNEL_MAX_TOKENS).  Shared experts are refused."""
+    most `moe_kernel_max_tokens` tokens outside a capture (None: kivi_amd.moe.KERNEL_MAX_TOKENS).  Shared experts are refused.
+    `weight_bits`: None, or 4 for 4-bit attention projections and dense MLPs in groups of `weight_group` (64 or 128) input channels
+    (kivi_amd/wquant.py): the kernel runs under capture and for at most `weight_kernel_max_tokens` tokens
+    otherwise (None: kivi_amd.wquant.KERNEL_MAX_TOKENS); embeddings, lm_head and the experts of a sparse block keep the model dtype."""
+    if weight_bits not in (None, 4):
+        raise ValueError(f"weight_bits has to be None or 4, got {weight_bits!r}")
+    if weight_bits is not None and weight_group not in wquant.GROUPS:
+        raise ValueError(f"weight_group has to be one of {wquant.GROUPS}, got {weight_group!r}")
+    extra = {}
+    if weight_bits is not None:             # (absent otherwise: the default namespace is what it was)
+        extra = dict(kivi_weight_bits=weight_bits, kivi_weight_group=weight_group,
+                     kivi_weight_kernel_max_tokens=weight_kernel_max_tokens, kivi_hf_config=dict(d))
     hidden, heads = d["hidden_size"], d["num_attention_heads"]
     for field in _SHARED_EXPERT_FIELDS:
         if d.get(field):
@@ -78,7 +91,7 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
         moe_intermediate_size=d["intermediate_size"] if mixtral else d.get("moe_intermediate_size", d["intermediate_size"]),
         norm_topk_prob=True if mixtral else bool(d.get("norm_topk_prob", False)),
         decoder_sparse_step=int(d.get("decoder_sparse_step", 1) or 1), mlp_only_layers=list(d.get("mlp_only_layers") or []),
-        kivi_moe_kernel=bool(moe_kernel), kivi_moe_kernel_max_tokens=moe_kernel_max_tokens)
+        kivi_moe_kernel=bool(moe_kernel), kivi_moe_kernel_max_tokens=moe_kernel_max_tokens, **extra)
 
 
 class RMSNorm(nn.Module):
@@ -112,7 +125,7 @@ def layer_is_sparse(cfg, layer_idx: int) -> bool:
 def make_mlp(cfg, layer_idx: int) -> nn.Module:
     """The feed-forward block of a layer: the dense SwiGLU MLP, or the sparse block of kivi_amd/moe.py."""
     if not layer_is_sparse(cfg, layer_idx):
-        return MLP(cfg)
+        return wquant.make_dense_mlp(cfg, MLP)  # MLP(cfg), or with cfg.kivi_weight_bits == 4 the 4-bit QuantMLP (section 30)
     return SparseMoeBlock(cfg.hidden_size, cfg.moe_intermediate_size, cfg.num_experts, cfg.num_experts_per_tok,
                           norm_topk=cfg.norm_topk_prob, round_weights=getattr(cfg, "kivi_moe_round_weights", False),
                           kernel=getattr(cfg, "kivi_moe_kernel", True),
@@ -778,12 +791,19 @@ class LlamaForCausalLM_KIVI(nn.Module):
     def from_pretrained(cls, path: str, device="cuda", dtype=torch.float16, **kivi):
         """`path`: a local HF checkpoint directory (config.json + *.safetensors).  `kivi`: k_bits, v_bits, group_size,
         residual_length, max_cache_len, prefill_kernel, decode_lead, qk_kernel (default: the class's, on for the Qwen classes),
-        moe_kernel, moe_kernel_max_tokens.
+        moe_kernel, moe_kernel_max_tokens, weight_bits, weight_group, weight_kernel_max_tokens.  With `weight_bits=4` the attention
+        projections and dense MLPs are built 4-bit up front and every `*_proj.weight` is quantised on the device as its file is read
+        (wquant.pack_checkpoint_weights); a directory written by save_quantized is recognised by its layout tag.
         Called on LlamaForCausalLM_KIVI, a config.json whose `model_type` is qwen2 / qwen3 / mixtral / qwen3_moe builds that
         family's class.  The experts of a sparse checkpoint are taken under HF's per-expert names or the fused ones of
         transformers 5 (take_expert_weights), file by file: each expert is copied into the stacked parameter in turn."""
         from safetensors.torch import load_file
         d = json.load(open(os.path.join(path, "config.json")))
+        if "kivi_weight_layout" in d:                       # a checkpoint of save_quantized: loaded as it is, nothing re-quantised
+            if d["kivi_weight_layout"] != wquant.LAYOUT:
+                raise ValueError(f"{path}: weight layout {d['kivi_weight_layout']!r} is not one this version reads ({wquant.LAYOUT!r})")
+            kivi["weight_bits"], kivi["weight_group"] = d["kivi_weight_bits"], d["kivi_weight_group"]
+            d = {k: v for k, v in d.items() if k not in ("kivi_weight_layout", "kivi_weight_bits", "kivi_weight_group")}
         if cls is LlamaForCausalLM_KIVI:
             cls = {"qwen2": Qwen2ForCausalLM_KIVI, "qwen3": Qwen3ForCausalLM_KIVI, "mixtral": MixtralForCausalLM_KIVI,
                    "qwen3_moe": Qwen3MoeForCausalLM_KIVI}.get(d.get("model_type"), cls)
@@ -796,17 +816,35 @@ class LlamaForCausalLM_KIVI(nn.Module):
                 model = cls(cfg)
             finally:
                 torch.set_default_dtype(prev)
-        state, filled = {}, {}
+        state, filled, packed = {}, {}, set()
         for f in sorted(glob.glob(os.path.join(path, "*.safetensors"))):
             part = load_file(f, device=str(device))
             take_expert_weights(model, part, filled)        # pops the expert tensors of this file: they die with `part`
+            wquant.pack_checkpoint_weights(model, part, packed, dtype)   # ... and quantises the dense weights of the 4-bit modules
             state.update(part)
         missing, unexpected = model.load_state_dict(state, strict=False)
         missing = [m for m in missing if "inv_freq" not in m and not (cfg.tie_word_embeddings and m == "lm_head.weight")
-                   and not expert_weight_filled(model, m, filled)]
+                   and not expert_weight_filled(model, m, filled) and m.rsplit(".", 1)[0] not in packed]
         if missing:
             raise KeyError(f"checkpoint lacks {missing[:5]}{' ...' if len(missing) > 5 else ''}")
         return model
+
+    def save_quantized(self, path: str) -> None:
+        """Write a model built with `weight_bits=4` to the directory `path`: config.json -- the fields it was loaded with plus
+        kivi_weight_bits, kivi_weight_group and the layout tag kivi_weight_layout -- and model.safetensors with the 4-bit modules'
+        `qweight` / `scales` / `mins` under their module names.  from_pretrained reads it back without quantising anything."""
+        from safetensors.torch import save_file
+        cfg = self.config
+        if getattr(cfg, "kivi_weight_bits", None) is None:
+            raise ValueError("save_quantized: the model was not built with weight_bits=4")
+        os.makedirs(path, exist_ok=True)
+        d = dict(cfg.kivi_hf_config, kivi_weight_bits=cfg.kivi_weight_bits, kivi_weight_group=cfg.kivi_weight_group,
+                 kivi_weight_layout=wquant.LAYOUT)
+        with open(os.path.join(path, "config.json"), "w") as fh:
+            json.dump(d, fh, indent=1)
+        state = {k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()
+                 if not (cfg.tie_word_embeddings and k == "lm_head.weight")}
+        save_file(state, os.path.join(path, "model.safetensors"))
 
 
 class MistralForCausalLM_KIVI(LlamaForCausalLM_KIVI):
