@@ -32,7 +32,7 @@ from .generation import (PADS_LEFT, DecodeLead, EagerStepper, _PaddedBatch, deco
                          padding_key_row, padding_position_ids, padding_prompt_mask, observe_prompts, bind_suppress,
                          resolve_sampler)
 from .graph import DecodeGraphs
-from .moe import SparseMoeBlock
+from .moe import QuantExperts, SparseMoeBlock
 from .prefill import left_padded
 from .sampling import RowSampler
 from .scoring import check_top_k, check_top_logprobs, token_logprobs
@@ -47,7 +47,8 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
                 max_cache_len: Optional[int] = None, prefill_kernel: bool = False, decode_lead: bool = False,
                 qk_kernel: bool = False, moe_kernel: bool = True, moe_kernel_max_tokens: Optional[int] = None,
                 weight_bits: Optional[int] = None, weight_group: int = 128,
-                weight_kernel_max_tokens: Optional[int] = None) -> SimpleNamespace:
+                weight_kernel_max_tokens: Optional[int] = None, expert_bits: Optional[int] = None,
+                expert_group: int = 128) -> SimpleNamespace:
     """HF config.json fields (+ the four KIVI fields) -> the namespace the modules read.  `prefill_kernel`: the prompt pass's
     attention runs kivi_prefill_attention, and every attention class serves left-padded prompts.
     `decode_lead`: the decode steps of a padded batch hand the kernels every row's leading pads, and the row kernels skip the packed
@@ -59,15 +60,27 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
     most `moe_kernel_max_tokens` tokens outside a capture (None: kivi_amd.moe.KERNEL_MAX_TOKENS).  Shared experts are refused.
     `weight_bits`: None, or 4 for 4-bit attention projections and dense MLPs in groups of `weight_group` (64 or 128) input channels
     (kivi_amd/wquant.py): the kernel runs under capture and for at most `weight_kernel_max_tokens` tokens
-    otherwise (None: kivi_amd.wquant.KERNEL_MAX_TOKENS); embeddings, lm_head and the experts of a sparse block keep the model dtype."""
+    otherwise (None: kivi_amd.wquant.KERNEL_MAX_TOKENS); embeddings, lm_head and the experts of a sparse block keep the model dtype.
+    `expert_bits`: None, or 4 for 4-bit experts in the sparse blocks, in groups of `expert_group` (64 or 128) along the reduction
+    axis (kivi_amd.moe.QuantExperts): the block dequantises each hit expert and runs the loop; it has no
+    capturable form, so the graphed decode paths raise on such a model.  Independent of `weight_bits`; a config without experts
+    refuses it."""
     if weight_bits not in (None, 4):
         raise ValueError(f"weight_bits has to be None or 4, got {weight_bits!r}")
     if weight_bits is not None and weight_group not in wquant.GROUPS:
         raise ValueError(f"weight_group has to be one of {wquant.GROUPS}, got {weight_group!r}")
+    if expert_bits not in (None, 4):
+        raise ValueError(f"expert_bits has to be None or 4, got {expert_bits!r}")
+    if expert_bits is not None and expert_group not in wquant.GROUPS:
+        raise ValueError(f"expert_group has to be one of {wquant.GROUPS}, got {expert_group!r}")
     extra = {}
     if weight_bits is not None:             # (absent otherwise: the default namespace is what it was)
         extra = dict(kivi_weight_bits=weight_bits, kivi_weight_group=weight_group,
                      kivi_weight_kernel_max_tokens=weight_kernel_max_tokens, kivi_hf_config=dict(d))
+    if expert_bits is not None:
+        if not int(d.get("num_local_experts", d.get("num_experts", 0)) or 0):
+            raise ValueError("expert_bits: the config has no experts (num_local_experts / num_experts)")
+        extra.update(kivi_expert_bits=expert_bits, kivi_expert_group=expert_group, kivi_hf_config=dict(d))
     hidden, heads = d["hidden_size"], d["num_attention_heads"]
     for field in _SHARED_EXPERT_FIELDS:
         if d.get(field):
@@ -129,7 +142,8 @@ def make_mlp(cfg, layer_idx: int) -> nn.Module:
     return SparseMoeBlock(cfg.hidden_size, cfg.moe_intermediate_size, cfg.num_experts, cfg.num_experts_per_tok,
                           norm_topk=cfg.norm_topk_prob, round_weights=getattr(cfg, "kivi_moe_round_weights", False),
                           kernel=getattr(cfg, "kivi_moe_kernel", True),
-                          kernel_max_tokens=getattr(cfg, "kivi_moe_kernel_max_tokens", None))
+                          kernel_max_tokens=getattr(cfg, "kivi_moe_kernel_max_tokens", None),
+                          expert_bits=getattr(cfg, "kivi_expert_bits", None), expert_group=getattr(cfg, "kivi_expert_group", 128))
 
 
 class DecoderLayer_KIVI(nn.Module):
@@ -172,6 +186,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
         self.lm_head = nn.Linear(config.hidden_size, config.vocab_size, bias=False)
         self.graphs = None          # kivi_amd.graph.DecodeGraphs of the last graphed decode (prepare_graphs / release_graphs)
         self._stoppers = {}         # (rows, device, pad) -> the StopRows that generate_graphed binds its keyword stops to
+        self._quant_experts = None  # whether a sparse block holds 4-bit experts (_refuse_capture)
         if getattr(config, "tie_word_embeddings", False):
             self.lm_head.weight = self.model.embed_tokens.weight
 
@@ -345,6 +360,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
         Per-request constraints (logit_bias, allowed_token_ids, min_new_tokens) come with `sampling`; `allowed_fn`: None, one callable
         or one per request, asked before every pick for the ids or the bitmask the request may emit next."""
         from .serving import generate_continuous
+        if graphed:
+            self._refuse_capture("generate_continuous(graphed=True)")
         return generate_continuous(self, prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, graphed, compact,
                                    short_admissions, return_logprobs, top_logprobs, stopping, return_finish, allowed_fn)
 
@@ -608,10 +625,20 @@ class LlamaForCausalLM_KIVI(nn.Module):
         return (seqs, logprobs) if return_logprobs else seqs
 
     # ------------------------------------------------------------------ hipGraph decode (kivi_amd/graph.py: DecodeGraphs)
+    def _refuse_capture(self, what: str) -> None:
+        """Raise, before anything runs, where the model holds a sparse block with 4-bit experts: that block's dequantising loop
+        synchronises, so no decode step of the model can be captured."""
+        if self._quant_experts is None:                         # (asked on every graphed step: walk the module tree once)
+            self._quant_experts = any(isinstance(m, QuantExperts) for m in self.modules())
+        if self._quant_experts:
+            raise ValueError(f"{what}: a model built with expert_bits=4 has no capturable decode step (its sparse blocks run the "
+                             f"dequantising loop, which synchronises); use the eager form")
+
     def prepare_graphs(self, batch: int, device, whole: bool = False, padded: bool = False, sampler=None,
                        logprobs: Optional[int] = None, stopper=None) -> None:
         """Capture the decode graphs for this batch size now (otherwise on the first graphed step).  `logprobs`, `stopper`: as
         decode_graphed."""
+        self._refuse_capture("prepare_graphs")
         key = None if sampler is None else sampler.key()
         lead = padded and bool(getattr(self.config, "kivi_decode_lead", False))
         if stopper is not None:
@@ -649,6 +676,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
         every s that is a multiple of `sync_every`, the host reads the stopper's `n_live` -- the only synchronisation -- and leaves
         when it is 0, so fewer than `steps` columns may come back and at most sync_every - 1 steps run after the last row has
         finished.  `sync_every=None`: never read, all `steps` run."""
+        self._refuse_capture("decode_graphed")
         if logprobs is not None and logprobs != 0:
             check_top_k(logprobs, self.config.vocab_size, "logprobs")
         if stopper is not None:
@@ -717,6 +745,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
         replays the graphs that exist; a StopRows passed as `stopping=` is used as it is and keys the graphs by its own buffers.
         `logit_bias` / `allowed_token_ids` / `min_new_tokens`: as in generate(); the constrained draw is
         inside the captured step, and so is the advance towards the end of the suppression."""
+        self._refuse_capture("generate_graphed")
         if sampling is None and num_beams != 1 and not do_sample:
             raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
         check_top_logprobs(top_logprobs, return_logprobs, num_beams, self.config.vocab_size)
@@ -791,7 +820,9 @@ class LlamaForCausalLM_KIVI(nn.Module):
     def from_pretrained(cls, path: str, device="cuda", dtype=torch.float16, **kivi):
         """`path`: a local HF checkpoint directory (config.json + *.safetensors).  `kivi`: k_bits, v_bits, group_size,
         residual_length, max_cache_len, prefill_kernel, decode_lead, qk_kernel (default: the class's, on for the Qwen classes),
-        moe_kernel, moe_kernel_max_tokens, weight_bits, weight_group, weight_kernel_max_tokens.  With `weight_bits=4` the attention
+        moe_kernel, moe_kernel_max_tokens, weight_bits, weight_group, weight_kernel_max_tokens, expert_bits, expert_group.
+        With `expert_bits=4` every expert matrix is quantised into its slab of the sparse block's
+        QuantExperts as its file is read (take_expert_weights): no dense expert stack ever exists.  With `weight_bits=4` the attention
         projections and dense MLPs are built 4-bit up front and every `*_proj.weight` is quantised on the device as its file is read
         (wquant.pack_checkpoint_weights); a directory written by save_quantized is recognised by its layout tag.
         Called on LlamaForCausalLM_KIVI, a config.json whose `model_type` is qwen2 / qwen3 / mixtral / qwen3_moe builds that
@@ -802,13 +833,19 @@ class LlamaForCausalLM_KIVI(nn.Module):
         if "kivi_weight_layout" in d:                       # a checkpoint of save_quantized: loaded as it is, nothing re-quantised
             if d["kivi_weight_layout"] != wquant.LAYOUT:
                 raise ValueError(f"{path}: weight layout {d['kivi_weight_layout']!r} is not one this version reads ({wquant.LAYOUT!r})")
-            kivi["weight_bits"], kivi["weight_group"] = d["kivi_weight_bits"], d["kivi_weight_group"]
-            d = {k: v for k, v in d.items() if k not in ("kivi_weight_layout", "kivi_weight_bits", "kivi_weight_group")}
+            if d.get("kivi_weight_bits") is not None:
+                kivi["weight_bits"], kivi["weight_group"] = d["kivi_weight_bits"], d["kivi_weight_group"]
+            if d.get("kivi_expert_bits") is not None:
+                kivi["expert_bits"], kivi["expert_group"] = d["kivi_expert_bits"], d["kivi_expert_group"]
+            d = {k: v for k, v in d.items() if k not in ("kivi_weight_layout", "kivi_weight_bits", "kivi_weight_group",
+                                                         "kivi_expert_bits", "kivi_expert_group")}
         if cls is LlamaForCausalLM_KIVI:
             cls = {"qwen2": Qwen2ForCausalLM_KIVI, "qwen3": Qwen3ForCausalLM_KIVI, "mixtral": MixtralForCausalLM_KIVI,
                    "qwen3_moe": Qwen3MoeForCausalLM_KIVI}.get(d.get("model_type"), cls)
         kivi.setdefault("qk_kernel", cls._QK_KERNEL)
         cfg = make_config(d, **kivi)
+        if getattr(cfg, "kivi_expert_bits", None) is not None and dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"from_pretrained(expert_bits=4) serves dtype torch.float16 or torch.bfloat16, got {dtype}")
         with torch.device(device):
             prev = torch.get_default_dtype()
             torch.set_default_dtype(dtype)
@@ -819,7 +856,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
         state, filled, packed = {}, {}, set()
         for f in sorted(glob.glob(os.path.join(path, "*.safetensors"))):
             part = load_file(f, device=str(device))
-            take_expert_weights(model, part, filled)        # pops the expert tensors of this file: they die with `part`
+            take_expert_weights(model, part, filled, dtype)     # pops the expert tensors of this file: they die with `part`
             wquant.pack_checkpoint_weights(model, part, packed, dtype)   # ... and quantises the dense weights of the 4-bit modules
             state.update(part)
         missing, unexpected = model.load_state_dict(state, strict=False)
@@ -830,16 +867,21 @@ class LlamaForCausalLM_KIVI(nn.Module):
         return model
 
     def save_quantized(self, path: str) -> None:
-        """Write a model built with `weight_bits=4` to the directory `path`: config.json -- the fields it was loaded with plus
-        kivi_weight_bits, kivi_weight_group and the layout tag kivi_weight_layout -- and model.safetensors with the 4-bit modules'
-        `qweight` / `scales` / `mins` under their module names.  from_pretrained reads it back without quantising anything."""
+        """Write a model built with `weight_bits=4` or `expert_bits=4` to the directory `path`: config.json -- the fields it was
+        loaded with plus kivi_weight_bits / kivi_weight_group, kivi_expert_bits / kivi_expert_group (those that are set) and the
+        layout tag kivi_weight_layout -- and model.safetensors with the 4-bit modules' `qweight` / `scales` / `mins` under their
+        module names.  from_pretrained reads it back without quantising anything."""
         from safetensors.torch import save_file
         cfg = self.config
-        if getattr(cfg, "kivi_weight_bits", None) is None:
-            raise ValueError("save_quantized: the model was not built with weight_bits=4")
+        wbits, ebits = getattr(cfg, "kivi_weight_bits", None), getattr(cfg, "kivi_expert_bits", None)
+        if wbits is None and ebits is None:
+            raise ValueError("save_quantized: the model was not built with weight_bits=4 or expert_bits=4")
         os.makedirs(path, exist_ok=True)
-        d = dict(cfg.kivi_hf_config, kivi_weight_bits=cfg.kivi_weight_bits, kivi_weight_group=cfg.kivi_weight_group,
-                 kivi_weight_layout=wquant.LAYOUT)
+        d = dict(cfg.kivi_hf_config, kivi_weight_layout=wquant.LAYOUT)
+        if wbits is not None:
+            d.update(kivi_weight_bits=wbits, kivi_weight_group=cfg.kivi_weight_group)
+        if ebits is not None:
+            d.update(kivi_expert_bits=ebits, kivi_expert_group=cfg.kivi_expert_group)
         with open(os.path.join(path, "config.json"), "w") as fh:
             json.dump(d, fh, indent=1)
         state = {k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()
@@ -904,22 +946,43 @@ _EXPERT_NAME = re.compile(r"^(.*\.)(?:block_sparse_moe|mlp)\.experts\.(\d+)\.(w1
 _EXPERT_PART = {"w1": "gate", "gate_proj": "gate", "w3": "up", "up_proj": "up", "w2": "down", "down_proj": "down"}
 
 
-def take_expert_weights(model: nn.Module, state: dict, filled: dict) -> dict:
+def take_expert_weights(model: nn.Module, state: dict, filled: dict, dtype=torch.float16) -> dict:
     """Move what `state` holds of the sparse blocks' weights into `model`, and out of `state` where that is a per-expert tensor.
     Three spellings are taken: Mixtral's `block_sparse_moe.gate.weight` and `block_sparse_moe.experts.{e}.w1 / w3 / w2.weight`
     (gate / up / down), Qwen3-MoE's `mlp.experts.{e}.gate_proj / up_proj / down_proj.weight`, and the fused names of transformers 5
     (`mlp.experts.gate_up_proj` / `.down_proj`, also under `block_sparse_moe.`), which stay in `state` under the module's names for
     load_state_dict.  A per-expert tensor is copied into its rows of the stacked parameter and popped: no second copy of the
-    experts is ever assembled.  `filled`: stacked parameter name -> number of pieces copied so far (updated and returned)."""
+    experts is ever assembled.  Where the block holds 4-bit experts (QuantExperts) a per-expert tensor is
+    quantised -- from its image in the model's `dtype` -- into the expert's slab, and a fused stack is quantised expert by expert
+    and popped.  `filled` (updated and returned): stacked parameter name -> number of pieces copied so far; for a 4-bit stack the
+    set of (expert, part) pieces packed so far, since its slabs start as zeros and nothing else could tell a missing one."""
     params = dict(model.named_parameters())
+    quant = {n: m for n, m in model.named_modules() if isinstance(m, QuantExperts)}
     for name in list(state):
         m = _EXPERT_NAME.match(name)
         if m is None:
-            if ".block_sparse_moe." in name:
-                state[name.replace(".block_sparse_moe.", ".mlp.")] = state.pop(name)
+            new = name.replace(".block_sparse_moe.", ".mlp.")
+            owner, _, leaf = new.rpartition(".")
+            if owner in quant and leaf in ("gate_up_proj", "down_proj"):    # a fused dense stack for a 4-bit block
+                q, t = quant[owner], state.pop(name)
+                part = "down" if leaf == "down_proj" else "gate_up"
+                if tuple(t.shape) != (q.num_experts, *q.shape_of(part)):
+                    raise ValueError(f"{name}: shape {tuple(t.shape)} does not fit {(q.num_experts, *q.shape_of(part))}")
+                for e in range(q.num_experts):
+                    q.pack_expert_(e, part, t[e].to(device=q.down_proj.qweight.device, dtype=dtype), f"{name}[{e}]")
+                    filled.setdefault(new, set()).update((e, p) for p in (("down",) if part == "down" else ("gate", "up")))
+            elif new != name:
+                state[new] = state.pop(name)
             continue
         prefix, e, part = m.group(1), int(m.group(2)), _EXPERT_PART[m.group(3)]
         target = f"{prefix}mlp.experts.{'down_proj' if part == 'down' else 'gate_up_proj'}"
+        if f"{prefix}mlp.experts" in quant:
+            q = quant[f"{prefix}mlp.experts"]
+            if e >= q.num_experts:
+                raise ValueError(f"{name}: expert {e} outside the block's {q.num_experts}")
+            q.pack_expert_(e, part, state.pop(name).to(device=q.down_proj.qweight.device, dtype=dtype), name)
+            filled.setdefault(target, set()).add((e, part))     # which pieces, not how many: a repeated tensor fills nothing twice
+            continue
         if target not in params:
             continue                                        # load_state_dict reports the name as unexpected
         t, p = state.pop(name), params[target]
@@ -934,7 +997,12 @@ def take_expert_weights(model: nn.Module, state: dict, filled: dict) -> dict:
 
 
 def expert_weight_filled(model: nn.Module, name: str, filled: dict) -> bool:
-    """True when every piece of the stacked expert parameter `name` has been copied by take_expert_weights."""
+    """True when every piece of the stacked expert parameter `name` -- or of the 4-bit stack that owns the buffer `name` (its
+    qweight, scales or mins) -- has been taken by take_expert_weights."""
+    stack, _, leaf = name.rpartition(".")
+    if leaf in ("qweight", "scales", "mins") and stack in filled:
+        owner = dict(model.named_modules()).get(stack.rpartition(".")[0])
+        return isinstance(owner, QuantExperts) and len(filled[stack]) == owner.num_experts * (1 if stack.endswith("down_proj") else 2)
     if name not in filled:
         return False
     p = dict(model.named_parameters())[name]

@@ -3,7 +3,8 @@ per token, each a SwiGLU MLP.  `route` / `experts` are the two HIP entries kivi_
 (kivi_amd/csrc/kivi_moe.hip): launches only, nothing is read back, so a captured decode step may hold them.  `route_torch` /
 `experts_torch` state the same contract in torch -- the per-expert loop of the Hugging Face modules, whose `nonzero` / `where`
 synchronise with the host -- for tensors off the GPU, shapes the kernels refuse and passes of many tokens.  `SparseMoeBlock` is the
-module the decoder layers carry as `mlp`.
+module the decoder layers carry as `mlp`; with `expert_bits=4` its experts are a `QuantExperts` -- the stacked matrices packed by
+kivi_w4_pack -- and every call takes `experts_w4_torch`, the loop with each hit expert dequantised first.
 
 The contract: token n's experts are the K largest router LOGITS, descending, equal logits to the lower expert (a choice that is
 decidable from the inputs; HF's top-k over the fp32 probabilities picks the same experts wherever two probabilities differ); its
@@ -18,7 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, wquant
 
 TOKEN_TILE = _lib.MOE_TOKEN_TILE        # pairs per tile of the grouped plan: include/kivi_hip.h, KIVI_MOE_TOKEN_TILE
 MAX_EXPERTS, MAX_TOP_K = _lib.MOE_MAX_E, _lib.MOE_MAX_K
@@ -181,6 +182,132 @@ def experts(x: torch.Tensor, plan: MoePlan, gate_up: torch.Tensor, down: torch.T
     return out
 
 
+class _QuantStack(nn.Module):
+    """The three buffers of E packed matrices (rows, cols) under QuantLinear's names: qweight (E, rows / 16, cols / 128, 256) int32,
+    scales and mins (E, rows / 16, cols / G, 16) int16 -- fp16 bit patterns, which .half() / .bfloat16() cannot re-round."""
+
+    def __init__(self, num_experts: int, rows: int, cols: int, group: int):
+        super().__init__()
+        qs, ss, ms = wquant.shapes(rows, cols, group)
+        self.register_buffer("qweight", torch.zeros((num_experts, *qs), dtype=torch.int32))
+        self.register_buffer("scales", torch.zeros((num_experts, *ss), dtype=torch.int16))
+        self.register_buffer("mins", torch.zeros((num_experts, *ms), dtype=torch.int16))
+
+    @property
+    def triple(self):
+        return self.qweight, self.scales, self.mins
+
+
+class QuantExperts(nn.Module):
+    """The stacked experts in 4 bits in `_Experts`' place: gate_up_proj and down_proj each hold qweight /
+    scales / mins, slab e of which is exactly wquant.pack of expert e's (2 I, H) gate_up and (H, I) down matrix (section 30's
+    quantiser and layout: I is a multiple of 16, so the gate stripes followed by the up stripes are the stripes of the (2 I, H)
+    matrix).  No dense expert parameter exists."""
+
+    def __init__(self, num_experts: int, hidden: int, intermediate: int, group: int = 128):
+        super().__init__()
+        if group not in wquant.GROUPS:
+            raise ValueError(f"expert_group has to be one of {wquant.GROUPS}, got {group!r}")
+        if hidden < wquant.K_TILE or hidden % wquant.K_TILE:
+            raise ValueError(f"4-bit experts need hidden_size to be a positive multiple of {wquant.K_TILE}, got {hidden}")
+        if intermediate < wquant.K_TILE or intermediate % wquant.K_TILE:
+            raise ValueError(f"4-bit experts need the experts' intermediate_size to be a positive multiple of {wquant.K_TILE}, got "
+                             f"{intermediate}")
+        self.num_experts, self.hidden, self.intermediate, self.group = num_experts, hidden, intermediate, group
+        self.gate_up_proj = _QuantStack(num_experts, 2 * intermediate, hidden, group)
+        self.down_proj = _QuantStack(num_experts, hidden, intermediate, group)
+
+    def extra_repr(self) -> str:
+        return f"num_experts={self.num_experts}, hidden={self.hidden}, intermediate={self.intermediate}, group={self.group}"
+
+    def slab(self, e: int, part: str):
+        """The views (qweight, scales, mins) that hold `part` (gate, up, gate_up or down) of expert e: contiguous."""
+        s = self.intermediate // wquant.ROW_TILE
+        if part not in ("gate", "up", "gate_up", "down"):
+            raise ValueError(f"part has to be gate, up, gate_up or down, got {part!r}")
+        if not 0 <= e < self.num_experts:
+            raise ValueError(f"expert {e} outside [0, {self.num_experts})")
+        if part == "down":
+            return tuple(t[e] for t in self.down_proj.triple)
+        a, b = {"gate": (0, s), "up": (s, 2 * s), "gate_up": (0, 2 * s)}[part]
+        return tuple(t[e, a:b] for t in self.gate_up_proj.triple)
+
+    def shape_of(self, part: str):
+        I, H = self.intermediate, self.hidden
+        return {"gate": (I, H), "up": (I, H), "gate_up": (2 * I, H), "down": (H, I)}[part]
+
+    def pack_expert_(self, e: int, part: str, weight: torch.Tensor, name: str = "weight") -> "QuantExperts":
+        """Quantise `weight` -- the gate, up (I, H), gate_up (2 I, H) or down (H, I) matrix of expert e, fp16 or bf16 on the module's
+        GPU -- straight into the expert's slab: one kivi_w4_pack launch."""
+        views = self.slab(e, part)
+        if weight.dtype not in _DTYPES:
+            raise ValueError(f"{name}: 4-bit experts are packed from torch.float16 or torch.bfloat16 weights, got {weight.dtype}")
+        if tuple(weight.shape) != self.shape_of(part):
+            raise ValueError(f"{name}: shape {tuple(weight.shape)} does not fit the {part} matrix {self.shape_of(part)}")
+        wquant.pack(weight, self.group, name, out=views)
+        return self
+
+    def load_ref_(self, e: int, part: str, code: torch.Tensor, scale: torch.Tensor, mn: torch.Tensor) -> "QuantExperts":
+        """Put the reference's triple of a matrix (wquant.quantize_ref) into the expert's slab, on any device."""
+        for view, t in zip(self.slab(e, part), wquant.from_ref(code, scale, mn, self.group)):
+            view.copy_(t)
+        return self
+
+    def dequant_expert(self, e: int, dtype=torch.float16, out=None):
+        """-> (gate_up (2 I, H), down (H, I)) of expert e in `dtype`: kivi_w4_dequant on the GPU, wquant.dequant_torch elsewhere.
+        `out`: a pair of contiguous buffers of those shapes to write into."""
+        res = []
+        for i, part in enumerate(("gate_up", "down")):
+            views = self.slab(e, part)
+            buf = None if out is None else out[i]
+            if views[0].is_cuda:
+                if dtype not in _DTYPES:
+                    raise ValueError(f"4-bit experts on the GPU serve torch.float16 and torch.bfloat16, got {dtype}")
+                res.append(wquant.dequant(*views, dtype=dtype, out=buf))
+            else:
+                t = wquant.dequant_torch(*views, dtype=dtype)
+                res.append(t if buf is None else buf.copy_(t))
+        return tuple(res)
+
+    @classmethod
+    def from_dense(cls, gate_up: torch.Tensor, down: torch.Tensor, group: int = 128) -> "QuantExperts":
+        """Quantise stacked dense experts gate_up (E, 2 I, H), down (E, H, I): on the GPU (fp16 or bf16) one kivi_w4_pack launch per
+        matrix, elsewhere wquant.quantize_ref."""
+        E, H, I = down.shape
+        if tuple(gate_up.shape) != (E, 2 * I, H):
+            raise ValueError(f"from_dense: gate_up {tuple(gate_up.shape)} and down {tuple(down.shape)} do not go together")
+        with torch.device(down.device):
+            m = cls(E, H, I, group)
+        for e in range(E):
+            for part, w in (("gate_up", gate_up[e]), ("down", down[e])):
+                if w.is_cuda:
+                    m.pack_expert_(e, part, w.detach(), f"experts.{part}[{e}]")
+                else:
+                    m.load_ref_(e, part, *wquant.quantize_ref(w.detach(), group))
+        return m
+
+
+def experts_w4_torch(x: torch.Tensor, plan: MoePlan, qexperts: QuantExperts) -> torch.Tensor:
+    """experts_torch over 4-bit experts, on any device: every expert that received a pair is dequantised to x's dtype into
+    wquant's shared scratch before its two F.linear's.  Synchronises."""
+    E, H, I = qexperts.num_experts, qexperts.hidden, qexperts.intermediate
+    out = torch.zeros_like(x)
+    idx, w = plan.idx.long(), plan.w
+    mask = F.one_hot(idx, num_classes=E).permute(2, 1, 0)
+    hit = torch.greater(mask.sum(dim=(-1, -2)), 0).nonzero()
+    buf = wquant._scratch(x.device, x.dtype, 3 * I, H)
+    bufs = (buf[: 2 * I], buf[2 * I:].view(H, I))
+    for e in hit:
+        e = e[0]
+        k_pos, tok = torch.where(mask[e])
+        gate_up, down = qexperts.dequant_expert(int(e), x.dtype, bufs)
+        g, u = F.linear(x[tok], gate_up).chunk(2, dim=-1)
+        y = F.linear(F.silu(g) * u, down)
+        y = y * w[tok, k_pos, None]
+        out.index_add_(0, tok, y.to(out.dtype))
+    return out
+
+
 class _Router(nn.Module):
     def __init__(self, num_experts: int, hidden: int):
         super().__init__()
@@ -199,24 +326,34 @@ class _Experts(nn.Module):
 class SparseMoeBlock(nn.Module):
     """HF's MixtralSparseMoeBlock / Qwen3MoeSparseMoeBlock: gate.weight (E, H), experts.gate_up_proj, experts.down_proj.  The
     router GEMM is F.linear.  `kernel`: route and experts run the HIP entries -- always under stream capture, where the torch loop
-    cannot run, and for at most `kernel_max_tokens` tokens otherwise; what the kernels do not serve (usable) takes the torch loop."""
+    cannot run, and for at most `kernel_max_tokens` tokens otherwise; what the kernels do not serve (usable) takes the torch loop.
+    `expert_bits=4`: the experts are a QuantExperts in groups of `expert_group` and every call takes the
+    loop, with each hit expert dequantised into wquant's shared scratch first.  That loop synchronises, and there is no expert
+    kernel over the packed buffers yet: under stream capture such a block raises."""
 
     def __init__(self, hidden: int, intermediate: int, num_experts: int, top_k: int, norm_topk: bool = True,
-                 round_weights: bool = False, kernel: bool = True, kernel_max_tokens: Optional[int] = None):
+                 round_weights: bool = False, kernel: bool = True, kernel_max_tokens: Optional[int] = None,
+                 expert_bits: Optional[int] = None, expert_group: int = 128):
         super().__init__()
         if not 1 <= top_k <= num_experts:
             raise ValueError(f"num_experts_per_tok = {top_k} outside [1, num_experts = {num_experts}]")
+        if expert_bits not in (None, 4):
+            raise ValueError(f"expert_bits has to be None or 4, got {expert_bits!r}")
         self.hidden, self.intermediate, self.num_experts, self.top_k = hidden, intermediate, num_experts, top_k
         self.norm_topk, self.round_weights = bool(norm_topk), bool(round_weights)
         self.kernel = bool(kernel)
+        self.expert_bits = expert_bits
         self.kernel_max_tokens = KERNEL_MAX_TOKENS if kernel_max_tokens is None else int(kernel_max_tokens)
         self.gate = _Router(num_experts, hidden)
-        self.experts = _Experts(num_experts, hidden, intermediate)
+        if expert_bits is None:
+            self.experts = _Experts(num_experts, hidden, intermediate)
+        else:
+            self.experts = QuantExperts(num_experts, hidden, intermediate, expert_group)
         for p in self.parameters():
             nn.init.normal_(p, 0.0, 0.02)
 
     def uses_kernel(self, x2: torch.Tensor) -> bool:
-        if not self.kernel or not usable(x2, self.num_experts, self.top_k, self.hidden, self.intermediate):
+        if self.expert_bits is not None or not self.kernel or not usable(x2, self.num_experts, self.top_k, self.hidden, self.intermediate):
             return False
         return torch.cuda.is_current_stream_capturing() or x2.shape[0] <= self.kernel_max_tokens
 
@@ -227,5 +364,10 @@ class SparseMoeBlock(nn.Module):
         if self.uses_kernel(x2):
             plan = route(logits, self.top_k, self.norm_topk, self.round_weights)
             return experts(x2, plan, self.experts.gate_up_proj, self.experts.down_proj).view(B, Q, H)
+        if self.expert_bits is not None and x2.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise _lib.KiviHipError("a sparse block with expert_bits=4 cannot run under stream capture: its experts go through the "
+                                    "dequantising loop, which synchronises, and no kernel over the packed experts exists")
         plan = route_torch(logits, self.top_k, self.norm_topk, self.round_weights)
+        if self.expert_bits is not None:
+            return experts_w4_torch(x2, plan, self.experts).view(B, Q, H)
         return experts_torch(x2, plan, self.experts.gate_up_proj, self.experts.down_proj).view(B, Q, H)

@@ -118,9 +118,10 @@ def _check_x(x: torch.Tensor, K: int, what: str) -> torch.Tensor:
     return x
 
 
-def pack(w: torch.Tensor, group: int = 128, name: str = "weight"):
+def pack(w: torch.Tensor, group: int = 128, name: str = "weight", out=None):
     """One kivi_w4_pack launch: w (O, K) fp16 or bf16 on the GPU -> (qweight, scales, mins).  A weight whose fp16 image holds an
-    infinity is refused, by `name`."""
+    infinity is refused, by `name`.  `out`: three contiguous buffers of those shapes and dtypes on w's device to write into (views
+    of a larger buffer: a stack of experts is packed slab by slab, kivi_amd/moe.py)."""
     _lib.require_gpu(w, name)
     if w.dim() != 2 or w.dtype not in _DTYPES:
         raise ValueError(f"{name}: a 2-D fp16 or bf16 weight is needed, got {tuple(w.shape)} {w.dtype}")
@@ -130,9 +131,15 @@ def pack(w: torch.Tensor, group: int = 128, name: str = "weight"):
         raise ValueError(f"{name}: the fp16 image of the weight holds an infinity; it cannot be quantised to 4 bits")
     if w.stride(1) != 1 or w.stride(0) % 8 or w.data_ptr() % 16:
         w = w.contiguous()
-    qweight = torch.empty(qs, dtype=torch.int32, device=w.device)
-    scales = torch.empty(ss, dtype=torch.int16, device=w.device)
-    mins = torch.empty(ms, dtype=torch.int16, device=w.device)
+    if out is None:
+        qweight = torch.empty(qs, dtype=torch.int32, device=w.device)
+        scales = torch.empty(ss, dtype=torch.int16, device=w.device)
+        mins = torch.empty(ms, dtype=torch.int16, device=w.device)
+    else:
+        qweight, scales, mins = out
+        for t, shape, dt in ((qweight, qs, torch.int32), (scales, ss, torch.int16), (mins, ms, torch.int16)):
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != w.device:
+                raise ValueError(f"{name}: out must be contiguous (qweight {qs} int32, scales {ss} int16, mins {ms} int16) on {w.device}")
     rc = _lib.load().kivi_w4_pack(w.data_ptr(), w.stride(0), _DTYPES[w.dtype], O, K, group, qweight.data_ptr(), scales.data_ptr(),
                                   mins.data_ptr(), _lib.stream_ptr(w))
     _lib.check(rc, "kivi_w4_pack")
