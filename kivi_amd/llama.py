@@ -4,20 +4,18 @@ Counterpart of the reference's LlamaForCausalLM_KIVI / MistralForCausalLM_KIVI w
 models/mistral_kivi.py:673-1100) reduced to what decoding needs: token embedding, pre-norm decoder blocks
 (RMSNorm, LlamaAttention_KIVI, SwiGLU MLP), final norm, lm_head, and the public methods of generation, scoring and checkpoints.
 Parameter names follow the Hugging Face checkpoints (model.embed_tokens, model.layers.N.self_attn.q_proj, ..., lm_head), so
-`load_state_dict` / `from_pretrained` take an unmodified Llama-2 / Llama-3 / Mistral checkpoint directory; everything outside the
-attention block is plain torch (rocBLAS / hipBLASLt GEMMs).  The reference patches k_bits / v_bits / group_size / residual_length
-onto the HF config (README.md:72-75); the same four fields are read here.
+`load_state_dict` / `from_pretrained` take an unmodified Llama-2 / Llama-3 / Mistral checkpoint directory -- what lies between
+such a directory and the filled model (config.json, the checkpoint's spellings, 4-bit packing, completeness) is
+kivi_amd/loading.py; here are the family table, make_config and the modules.  Everything outside the attention block is plain
+torch (rocBLAS / hipBLASLt GEMMs).  The reference patches k_bits / v_bits / group_size / residual_length onto the HF config
+(README.md:72-75); the same four fields are read here.
 What a generate call is made of -- left padding, the sampler of the call, the prompt pass and its fork, the eager step, the decode
 loop -- is kivi_amd/generation.py; beam search is kivi_amd/beam.py, the graphed decode step kivi_amd/graph.py (DecodeGraphs), the
 scheduler of continuous batching kivi_amd/serving.py (over admit_() here and kivi_amd/admit.py).
 """
 from __future__ import annotations
 
-import glob
-import json
 import math
-import os
-import re
 from types import SimpleNamespace
 from typing import List, Optional
 
@@ -25,7 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import admit, wquant
+from . import admit, loading, wquant
 from .attention import KiviLayerCacheMF, LlamaAttention_KIVI
 from .beam import beam_search
 from .generation import (PADS_LEFT, DecodeLead, EagerStepper, _PaddedBatch, decode_loop, leading_pads, left_pad,  # noqa: F401
@@ -821,24 +819,16 @@ class LlamaForCausalLM_KIVI(nn.Module):
         """`path`: a local HF checkpoint directory (config.json + *.safetensors).  `kivi`: k_bits, v_bits, group_size,
         residual_length, max_cache_len, prefill_kernel, decode_lead, qk_kernel (default: the class's, on for the Qwen classes),
         moe_kernel, moe_kernel_max_tokens, weight_bits, weight_group, weight_kernel_max_tokens, expert_bits, expert_group.
-        With `expert_bits=4` every expert matrix is quantised into its slab of the sparse block's
-        QuantExperts as its file is read (take_expert_weights): no dense expert stack ever exists.  With `weight_bits=4` the attention
-        projections and dense MLPs are built 4-bit up front and every `*_proj.weight` is quantised on the device as its file is read
-        (wquant.pack_checkpoint_weights); a directory written by save_quantized is recognised by its layout tag.
         Called on LlamaForCausalLM_KIVI, a config.json whose `model_type` is qwen2 / qwen3 / mixtral / qwen3_moe builds that
-        family's class.  The experts of a sparse checkpoint are taken under HF's per-expert names or the fused ones of
-        transformers 5 (take_expert_weights), file by file: each expert is copied into the stacked parameter in turn."""
-        from safetensors.torch import load_file
-        d = json.load(open(os.path.join(path, "config.json")))
-        if "kivi_weight_layout" in d:                       # a checkpoint of save_quantized: loaded as it is, nothing re-quantised
-            if d["kivi_weight_layout"] != wquant.LAYOUT:
-                raise ValueError(f"{path}: weight layout {d['kivi_weight_layout']!r} is not one this version reads ({wquant.LAYOUT!r})")
-            if d.get("kivi_weight_bits") is not None:
-                kivi["weight_bits"], kivi["weight_group"] = d["kivi_weight_bits"], d["kivi_weight_group"]
-            if d.get("kivi_expert_bits") is not None:
-                kivi["expert_bits"], kivi["expert_group"] = d["kivi_expert_bits"], d["kivi_expert_group"]
-            d = {k: v for k, v in d.items() if k not in ("kivi_weight_layout", "kivi_weight_bits", "kivi_weight_group",
-                                                         "kivi_expert_bits", "kivi_expert_group")}
+        family's class.  The class, the config and the empty model are made here; reading config.json and filling the model are
+        kivi_amd/loading.py: the files are read one at a time, and a checkpoint that leaves any tensor of
+        the model unfilled raises KeyError.  With `expert_bits=4` every expert matrix is quantised into its slab of the sparse
+        block's QuantExperts as its file is read: no dense expert stack ever exists.  With `weight_bits=4` the attention
+        projections and dense MLPs are built 4-bit up front and every `*_proj.weight` is quantised on the device as its file is
+        read; a directory written by save_quantized is recognised by its layout tag.  The experts of a sparse checkpoint are
+        taken under HF's per-expert names or the fused ones of transformers 5: each expert is copied into the stacked parameter in
+        turn."""
+        d = loading.read_config(path, kivi)     # (a directory of save_quantized: its tags become keywords of make_config)
         if cls is LlamaForCausalLM_KIVI:
             cls = {"qwen2": Qwen2ForCausalLM_KIVI, "qwen3": Qwen3ForCausalLM_KIVI, "mixtral": MixtralForCausalLM_KIVI,
                    "qwen3_moe": Qwen3MoeForCausalLM_KIVI}.get(d.get("model_type"), cls)
@@ -853,40 +843,14 @@ class LlamaForCausalLM_KIVI(nn.Module):
                 model = cls(cfg)
             finally:
                 torch.set_default_dtype(prev)
-        state, filled, packed = {}, {}, set()
-        for f in sorted(glob.glob(os.path.join(path, "*.safetensors"))):
-            part = load_file(f, device=str(device))
-            take_expert_weights(model, part, filled, dtype)     # pops the expert tensors of this file: they die with `part`
-            wquant.pack_checkpoint_weights(model, part, packed, dtype)   # ... and quantises the dense weights of the 4-bit modules
-            state.update(part)
-        missing, unexpected = model.load_state_dict(state, strict=False)
-        missing = [m for m in missing if "inv_freq" not in m and not (cfg.tie_word_embeddings and m == "lm_head.weight")
-                   and not expert_weight_filled(model, m, filled) and m.rsplit(".", 1)[0] not in packed]
-        if missing:
-            raise KeyError(f"checkpoint lacks {missing[:5]}{' ...' if len(missing) > 5 else ''}")
-        return model
+        return loading.load_weights(model, path, device, dtype)
 
     def save_quantized(self, path: str) -> None:
         """Write a model built with `weight_bits=4` or `expert_bits=4` to the directory `path`: config.json -- the fields it was
         loaded with plus kivi_weight_bits / kivi_weight_group, kivi_expert_bits / kivi_expert_group (those that are set) and the
         layout tag kivi_weight_layout -- and model.safetensors with the 4-bit modules' `qweight` / `scales` / `mins` under their
         module names.  from_pretrained reads it back without quantising anything."""
-        from safetensors.torch import save_file
-        cfg = self.config
-        wbits, ebits = getattr(cfg, "kivi_weight_bits", None), getattr(cfg, "kivi_expert_bits", None)
-        if wbits is None and ebits is None:
-            raise ValueError("save_quantized: the model was not built with weight_bits=4 or expert_bits=4")
-        os.makedirs(path, exist_ok=True)
-        d = dict(cfg.kivi_hf_config, kivi_weight_layout=wquant.LAYOUT)
-        if wbits is not None:
-            d.update(kivi_weight_bits=wbits, kivi_weight_group=cfg.kivi_weight_group)
-        if ebits is not None:
-            d.update(kivi_expert_bits=ebits, kivi_expert_group=cfg.kivi_expert_group)
-        with open(os.path.join(path, "config.json"), "w") as fh:
-            json.dump(d, fh, indent=1)
-        state = {k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()
-                 if not (cfg.tie_word_embeddings and k == "lm_head.weight")}
-        save_file(state, os.path.join(path, "model.safetensors"))
+        loading.save_quantized(self, path)
 
 
 class MistralForCausalLM_KIVI(LlamaForCausalLM_KIVI):
@@ -939,71 +903,3 @@ class Qwen3MoeForCausalLM_KIVI(Qwen3ForCausalLM_KIVI):
 
     def __init__(self, config, attention_cls=None):
         super().__init__(SimpleNamespace(**{**vars(config), "kivi_moe_round_weights": True}), attention_cls)
-
-
-# ---------------------------------------------------------------------- expert weights of a checkpoint
-_EXPERT_NAME = re.compile(r"^(.*\.)(?:block_sparse_moe|mlp)\.experts\.(\d+)\.(w1|w2|w3|gate_proj|up_proj|down_proj)\.weight$")
-_EXPERT_PART = {"w1": "gate", "gate_proj": "gate", "w3": "up", "up_proj": "up", "w2": "down", "down_proj": "down"}
-
-
-def take_expert_weights(model: nn.Module, state: dict, filled: dict, dtype=torch.float16) -> dict:
-    """Move what `state` holds of the sparse blocks' weights into `model`, and out of `state` where that is a per-expert tensor.
-    Three spellings are taken: Mixtral's `block_sparse_moe.gate.weight` and `block_sparse_moe.experts.{e}.w1 / w3 / w2.weight`
-    (gate / up / down), Qwen3-MoE's `mlp.experts.{e}.gate_proj / up_proj / down_proj.weight`, and the fused names of transformers 5
-    (`mlp.experts.gate_up_proj` / `.down_proj`, also under `block_sparse_moe.`), which stay in `state` under the module's names for
-    load_state_dict.  A per-expert tensor is copied into its rows of the stacked parameter and popped: no second copy of the
-    experts is ever assembled.  Where the block holds 4-bit experts (QuantExperts) a per-expert tensor is
-    quantised -- from its image in the model's `dtype` -- into the expert's slab, and a fused stack is quantised expert by expert
-    and popped.  `filled` (updated and returned): stacked parameter name -> number of pieces copied so far; for a 4-bit stack the
-    set of (expert, part) pieces packed so far, since its slabs start as zeros and nothing else could tell a missing one."""
-    params = dict(model.named_parameters())
-    quant = {n: m for n, m in model.named_modules() if isinstance(m, QuantExperts)}
-    for name in list(state):
-        m = _EXPERT_NAME.match(name)
-        if m is None:
-            new = name.replace(".block_sparse_moe.", ".mlp.")
-            owner, _, leaf = new.rpartition(".")
-            if owner in quant and leaf in ("gate_up_proj", "down_proj"):    # a fused dense stack for a 4-bit block
-                q, t = quant[owner], state.pop(name)
-                part = "down" if leaf == "down_proj" else "gate_up"
-                if tuple(t.shape) != (q.num_experts, *q.shape_of(part)):
-                    raise ValueError(f"{name}: shape {tuple(t.shape)} does not fit {(q.num_experts, *q.shape_of(part))}")
-                for e in range(q.num_experts):
-                    q.pack_expert_(e, part, t[e].to(device=q.down_proj.qweight.device, dtype=dtype), f"{name}[{e}]")
-                    filled.setdefault(new, set()).update((e, p) for p in (("down",) if part == "down" else ("gate", "up")))
-            elif new != name:
-                state[new] = state.pop(name)
-            continue
-        prefix, e, part = m.group(1), int(m.group(2)), _EXPERT_PART[m.group(3)]
-        target = f"{prefix}mlp.experts.{'down_proj' if part == 'down' else 'gate_up_proj'}"
-        if f"{prefix}mlp.experts" in quant:
-            q = quant[f"{prefix}mlp.experts"]
-            if e >= q.num_experts:
-                raise ValueError(f"{name}: expert {e} outside the block's {q.num_experts}")
-            q.pack_expert_(e, part, state.pop(name).to(device=q.down_proj.qweight.device, dtype=dtype), name)
-            filled.setdefault(target, set()).add((e, part))     # which pieces, not how many: a repeated tensor fills nothing twice
-            continue
-        if target not in params:
-            continue                                        # load_state_dict reports the name as unexpected
-        t, p = state.pop(name), params[target]
-        inter = p.shape[2] if part == "down" else p.shape[1] // 2
-        want = (p.shape[1], p.shape[2]) if part == "down" else (inter, p.shape[2])
-        if e >= p.shape[0] or tuple(t.shape) != want:
-            raise ValueError(f"{name}: shape {tuple(t.shape)} does not fit {target} {tuple(p.shape)}")
-        rows = p.data[e] if part == "down" else p.data[e, :inter] if part == "gate" else p.data[e, inter:]
-        rows.copy_(t)
-        filled[target] = filled.get(target, 0) + 1
-    return filled
-
-
-def expert_weight_filled(model: nn.Module, name: str, filled: dict) -> bool:
-    """True when every piece of the stacked expert parameter `name` -- or of the 4-bit stack that owns the buffer `name` (its
-    qweight, scales or mins) -- has been taken by take_expert_weights."""
-    stack, _, leaf = name.rpartition(".")
-    if leaf in ("qweight", "scales", "mins") and stack in filled:
-        owner = dict(model.named_modules()).get(stack.rpartition(".")[0])
-        return isinstance(owner, QuantExperts) and len(filled[stack]) == owner.num_experts * (1 if stack.endswith("down_proj") else 2)
-    if name not in filled:
-        return False
-    p = dict(model.named_parameters())[name]
-    return filled[name] == p.shape[0] * (1 if name.endswith("down_proj") else 2)

@@ -314,16 +314,3 @@ def make_dense_mlp(cfg, plain_cls) -> nn.Module:
                                            and usable(cfg.hidden_size, cfg.intermediate_size, group)):
         return plain_cls(cfg)
     return QuantMLP(cfg.hidden_size, cfg.intermediate_size, group, getattr(cfg, "kivi_weight_kernel_max_tokens", None))
-
-
-def pack_checkpoint_weights(model: nn.Module, state: dict, packed: set, dtype=torch.float16) -> set:
-    """Quantise what `state` (one file of a checkpoint, on the device) holds of the QuantLinear modules' `weight`s into their
-    buffers -- from the tensor in the model's `dtype`, as QuantLinear.from_linear on the loaded model would -- and pop it: the dense
-    tensor dies with the file's dict.  `packed`: the module names done so far (updated, returned)."""
-    mods = {n: m for n, m in model.named_modules() if isinstance(m, QuantLinear)}
-    for name in list(state):
-        if name.endswith(".weight") and name[:-7] in mods:
-            m = mods[name[:-7]]
-            m.pack_(state.pop(name).to(device=m.qweight.device, dtype=dtype), name)
-            packed.add(name[:-7])
-    return packed

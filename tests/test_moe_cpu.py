@@ -9,7 +9,7 @@
    reference's rms.  (The HF fp32 blocks themselves sit at 1.3-1.5e-6 of the fp64 restatement at E = 8 / K = 2 and E = 12 / K = 4,
    H = 64: the bar has about 7x room.)
 4. The layer-kind rule against HF's Qwen3MoeDecoderLayer for decoder_sparse_step 1 and 2 with mlp_only_layers; the translation of
-   checkpoint names for the three spellings; the refusal of shared experts."""
+   checkpoint names for the three spellings (kivi_amd/loading.py); the refusal of shared experts."""
 import os
 import shutil
 import subprocess
@@ -271,7 +271,8 @@ def _spell(state, spelling):
 
 @pytest.mark.parametrize("spelling", ["mixtral", "qwen3_moe", "fused"])
 def test_checkpoint_names_are_translated(spelling):
-    from kivi_amd.llama import MixtralForCausalLM_KIVI, expert_weight_filled, make_config, take_expert_weights
+    from kivi_amd.llama import MixtralForCausalLM_KIVI, make_config
+    from kivi_amd.loading import CheckpointLoader
     d = _cfg(model_type="mixtral", num_local_experts=4, num_experts_per_tok=2, num_hidden_layers=2, intermediate_size=32)
     torch.manual_seed(1)
     src = MixtralForCausalLM_KIVI(make_config(d))
@@ -282,24 +283,19 @@ def test_checkpoint_names_are_translated(spelling):
     dst = MixtralForCausalLM_KIVI(make_config(d))
     half = len(state) // 2                                      # two "files": the pieces of one parameter may come apart
     names = list(state)
-    filled = {}
-    rest = {}
+    loader = CheckpointLoader(dst, torch.float32)
     for part in ({k: state[k] for k in names[:half]}, {k: state[k] for k in names[half:]}):
-        take_expert_weights(dst, part, filled)
-        rest.update(part)
-    assert not any(".experts." in k and k[k.index(".experts.") + 9].isdigit() for k in rest)
-    assert not any("block_sparse_moe" in k for k in rest)
-    missing, unexpected = dst.load_state_dict(rest, strict=False)
-    missing = [m for m in missing if not expert_weight_filled(dst, m, filled)]
-    assert not missing and not unexpected, (missing, unexpected)
+        loader.take(part)
+    loader.finish()
+    assert not loader.unexpected, loader.unexpected
     for (k, a), (_, b) in zip(sorted(src.state_dict().items()), sorted(dst.state_dict().items())):
         assert torch.equal(a, b), k
     # a checkpoint that lacks one expert's piece is reported
     if spelling != "fused":
         torch.manual_seed(3)
-        short = MixtralForCausalLM_KIVI(make_config(d))
+        short = CheckpointLoader(MixtralForCausalLM_KIVI(make_config(d)), torch.float32)
         part = dict(state)
         part.pop(next(k for k in part if ".experts.3." in k))
-        filled = take_expert_weights(short, part, {})
-        missing, _ = short.load_state_dict(part, strict=False)
-        assert [m for m in missing if not expert_weight_filled(short, m, filled)]
+        short.take(part)
+        with pytest.raises(KeyError, match="experts.gate_up_proj"):
+            short.finish()
