@@ -257,9 +257,9 @@ def decode_loop(first_logits: torch.Tensor, step: Callable, pick: Callable, max_
     other, so a call whose rows all end by their limits does NOT run the pass after the last token."""
     if stopper is not None and eos_token_id is not None:
         raise ValueError("decode_loop takes either eos_token_id or a stopper (whose stop ids include it), not both")
-    if want_logprobs:
-        from .scoring import token_logprobs, top_logprobs
-    logits, out, lps, tids, tlps = first_logits, [], [], [], []
+    from .scoring import picked_scores                 # here, not at the top: scoring imports this module (this breaks the cycle)
+    k = (top_k or 0) if want_logprobs else None
+    logits, out, cols = first_logits, [], ([], [], [])  # cols: logprob, top ids, top log-probabilities of every token
     tok = pick(logits)
     B = tok.shape[0]
     live = None if eos_token_id is None else torch.ones((B, 1), dtype=torch.bool, device=tok.device)
@@ -269,15 +269,12 @@ def decode_loop(first_logits: torch.Tensor, step: Callable, pick: Callable, max_
             stopper(tok)
         elif live is not None:
             tok = torch.where(live, tok, torch.full_like(tok, pad_token_id))
-        if want_logprobs:                              # a finished row scores nothing: its target is the ignore_index
-            tgt = tok if live is None else torch.where(live, tok, torch.full_like(tok, -100))
-            if top_k:
-                res = top_logprobs(logits, top_k, tgt)
-                lps.append(res.target_logprob)
-                tids.append(res.ids if live is None else res.ids.masked_fill(~live.unsqueeze(-1), -1))
-                tlps.append(res.logprobs if live is None else res.logprobs.masked_fill(~live.unsqueeze(-1), 0.0))
-            else:
-                lps.append(token_logprobs(logits, tgt))
+        if k is not None:                              # a finished row scores nothing: its target is the ignore_index
+            sc = picked_scores(logits, tok if live is None else torch.where(live, tok, torch.full_like(tok, -100)), k)
+            if k and live is not None:                 # ... and its lists hold id -1, value 0
+                sc = (sc[0], sc[1].masked_fill(~live.unsqueeze(-1), -1), sc[2].masked_fill(~live.unsqueeze(-1), 0.0))
+            for col, v in zip(cols, sc):
+                col.append(v)
         if stopper is None and live is not None:
             live = live & (tok != eos_token_id)
         out.append(tok)
@@ -288,9 +285,19 @@ def decode_loop(first_logits: torch.Tensor, step: Callable, pick: Callable, max_
             break
         logits = step(tok)
         tok = pick(logits)
-    if want_logprobs:
-        lps = torch.cat(lps, dim=1) if lps else logits.new_empty((B, 0), dtype=torch.float32)
-        if top_k:
-            lps = (lps, torch.cat(tids, dim=1) if tids else tok.new_empty((B, 0, top_k)),
-                   torch.cat(tlps, dim=1) if tlps else logits.new_empty((B, 0, top_k), dtype=torch.float32))
-    return torch.cat(out, dim=1) if out else tok.new_empty((B, 0)), lps if want_logprobs else None
+    lps = None
+    if k is not None:
+        lps = torch.cat(cols[0], dim=1) if out else logits.new_empty((B, 0), dtype=torch.float32)
+        if k:
+            lps = (lps, torch.cat(cols[1], dim=1) if out else tok.new_empty((B, 0, k)),
+                   torch.cat(cols[2], dim=1) if out else logits.new_empty((B, 0, k), dtype=torch.float32))
+    return torch.cat(out, dim=1) if out else tok.new_empty((B, 0)), lps
+
+
+def pack_result(input_ids: torch.Tensor, new: torch.Tensor, scores=()):
+    """What a generate call returns: the prompts with the new tokens behind them, alone or as (sequences, logprobs[, top_ids,
+    top_logprobs]) -- `scores`: those of the new tokens as a tuple, or as decode_loop gives them (None, or the logprobs alone)."""
+    if not isinstance(scores, tuple):
+        scores = () if scores is None else (scores,)
+    seqs = torch.cat([input_ids, new], dim=1)
+    return (seqs,) + scores if scores else seqs

@@ -16,7 +16,8 @@ bound too, and the one-launch caps are whole super-blocks + a full residual, so 
 per row and the replayed one sliced the row are gone: tests/test_graph_gpu.py covers Tq just under 8192 / 9216).
 
 `DecodeGraphs` is what a model keeps for its graphed decode: the static buffers, the dense bodies, and either this whole-step graph
-or, for caches in the hook-state layout, per-layer graphs of the dense parts around an eager attention call.
+or, for caches in the hook-state layout, per-layer graphs of the dense parts around an eager attention call.  Beside it, as functions
+of the model, the calls that drive it (`prepare_graphs`, `decode_graphed`, `generate_graphed`): the model's methods delegate here.
 """
 from __future__ import annotations
 
@@ -31,9 +32,11 @@ import torch
 from . import _lib
 from .attention import _rotate_half, kivi_attention_decode, rope_cos_sin
 from .cache_mf import SB, KiviLayerCacheMF
-from .generation import _MIN16, leading_pads
+from .generation import _MIN16, bind_suppress, leading_pads, observe_prompts, pack_result, resolve_sampler
 from .qkrope import unpad
-from .scoring import score_into
+from .sampling import RowSampler
+from .scoring import check_top_k, check_top_logprobs, picked_scores, score_into
+from .stopping import StopRows, check_sync_every, resolve_stopping
 
 
 class MfStepDriver:
@@ -351,3 +354,114 @@ class DecodeGraphs:
     def end(self) -> None:
         """The caches of begin() die with their request: so does what was captured over them (buffers and per-layer graphs stay)."""
         self.driver = self.graphed = None
+
+
+# ------------------------------------------------------------------ the graphed calls of a model (its methods of the same names)
+def prepare_graphs(model, batch: int, device, whole, padded, sampler, logprobs, stopper) -> None:
+    """LlamaForCausalLM_KIVI.prepare_graphs: model.graphs serves this step, built anew only when one of the seven fields differs."""
+    model._refuse_capture("prepare_graphs")
+    key, stop_key = (None if x is None else x.key() for x in (sampler, stopper))
+    lead = padded and bool(getattr(model.config, "kivi_decode_lead", False))
+    if model.graphs is None or not model.graphs.matches(batch, whole, padded, key, lead, logprobs, stop_key):
+        model.graphs = DecodeGraphs(model, batch, device, whole, padded, sampler, lead, logprobs, stopper)
+
+
+@torch.no_grad()
+def decode_graphed(model, tok, past_key_values, position, steps, attention_mask, sampler, sampling, logprobs, stopper, sync_every):
+    """LlamaForCausalLM_KIVI.decode_graphed (its docstring is the reference): the checks, the graphs of the step, the step loop."""
+    model._refuse_capture("decode_graphed")
+    if logprobs is not None and logprobs != 0:
+        check_top_k(logprobs, model.config.vocab_size, "logprobs")
+    if stopper is not None:
+        if not isinstance(stopper, StopRows) or stopper.B != tok.shape[0]:
+            raise ValueError(f"decode_graphed(stopper=) takes a StopRows of {tok.shape[0]} rows")
+        check_sync_every(sync_every)
+    if sampling is not None:
+        if sampler is not None:
+            raise ValueError("pass either sampler= or sampling=, not both")
+        if not isinstance(sampling, RowSampler):
+            raise ValueError("decode_graphed(sampling=) takes a RowSampler")
+        if sampling.B != tok.shape[0]:
+            raise ValueError(f"the RowSampler holds {sampling.B} rows, the step has {tok.shape[0]}")
+        sampler = sampling
+    caches = [p.layer for p in past_key_values]
+    whole = all(isinstance(c, KiviLayerCacheMF) for c in caches)      # the whole step as one graph, else per-layer graphs
+    B, kv0 = tok.shape[0], caches[0].kv_seq_len
+    padded = attention_mask is not None and model._padded(attention_mask, B, kv0 + 1, kv0)
+    model.prepare_graphs(B, tok.device, whole, padded, sampler, logprobs, stopper)
+    g = model.graphs
+    g.begin(tok, caches, attention_mask)
+    # the static buffers the host clones: the token a step is fed, before the step; the scores of the token it produced, after it
+    bufs = (g.tok,) + (() if logprobs is None else (g.lp,) + ((g.top_ids, g.top_lp) if logprobs else ()))
+    cols = [[] for _ in bufs]
+    for s in range(steps):
+        if stopper is not None and sync_every is not None and s % sync_every == 0 and int(stopper.n_live) == 0:
+            break
+        cols[0].append(g.tok.clone())
+        g.step(position + s)
+        for col, buf in zip(cols[1:], bufs[1:]):
+            col.append(buf.clone())
+    res = tuple(torch.cat(col, dim=1) if col else buf.new_empty((B, 0) + buf.shape[2:]) for col, buf in zip(cols, bufs))
+    return res[0] if logprobs is None else res
+
+
+def kept_stopper(model, params, device, pad_token_id: int) -> StopRows:
+    """The model's own finish tracker for (rows, device, pad), its rows bound to `params`: the buffers stay from call to call, so
+    the graphs captured over them are replayed whatever the stops of the next call are."""
+    kept, key = model._stoppers, (len(params), str(device), pad_token_id)
+    if key in kept:
+        kept[key].rebind(params)
+    else:
+        kept[key] = StopRows(params, device, pad_token_id=pad_token_id)
+    return kept[key]
+
+
+@torch.no_grad()
+def generate_graphed(model, input_ids, max_new_tokens, attention_mask, num_beams, do_sample, temperature, top_k, top_p, min_p, seed,
+                     sampling, repetition_penalty, presence_penalty, frequency_penalty, return_logprobs, top_logprobs, eos_token_id,
+                     pad_token_id, stop_token_ids, stop_sequences, stopping, sync_every, logit_bias, allowed_token_ids, min_new_tokens):
+    """LlamaForCausalLM_KIVI.generate_graphed (its docstring is the reference).  One flow; finish conditions change, in explicit
+    branches, how many steps run and which tokens come back, and the cut to the tracker's lengths with the masking behind them."""
+    model._refuse_capture("generate_graphed")
+    if sampling is None and num_beams != 1 and not do_sample:
+        raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
+    vocab = model.config.vocab_size
+    check_top_logprobs(top_logprobs, return_logprobs, num_beams, vocab)
+    pick, _ = resolve_sampler(input_ids.device, input_ids.shape[0], 1, num_beams, do_sample, temperature, top_k, top_p, min_p,
+                              seed, sampling, repetition_penalty, presence_penalty, frequency_penalty, vocab, logit_bias,
+                              allowed_token_ids, min_new_tokens)
+    check_sync_every(sync_every)
+    stops = resolve_stopping(input_ids.shape[0], max_new_tokens, eos_token_id, pad_token_id, stop_token_ids, stop_sequences,
+                             stopping, 1, vocab, torch_eos=False)
+    bind_suppress(pick, sampling, stops, eos_token_id)
+    logits, pasts = model.forward(input_ids, padding_mask=attention_mask)
+    observe_prompts(pick, input_ids, attention_mask)
+    if attention_mask is not None:
+        attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, :1])], dim=1)
+    tok = logits.argmax(-1) if pick is None else pick(logits)
+    k = top_logprobs if return_logprobs else None
+    if stops is None or max_new_tokens <= 0:
+        # every step runs and the tokens FED come back: the caches end max_new_tokens tokens on, a sampler one draw more, as generate()
+        stopper, steps, how = None, max_new_tokens, {} if k is None else dict(logprobs=k)
+    else:
+        # the first token goes through the tracker eagerly, the steps may end early, and the last token is the one PRODUCED
+        stopper = stops if isinstance(stops, StopRows) else kept_stopper(model, stops, input_ids.device, pad_token_id)
+        before = stopper.length.clone()                 # (a caller's StopRows may have counted earlier tokens)
+        stopper(tok)
+        steps, how = max_new_tokens - 1, dict(logprobs=k, stopper=stopper, sync_every=sync_every)
+    firsts = picked_scores(logits, tok, k)
+    res = model.decode_graphed(tok, pasts, input_ids.shape[1], steps, attention_mask, pick, **how)
+    new, scores = (res, ()) if k is None else (res[0], res[1:])
+    if stopper is not None:
+        new = torch.cat([new, model.graphs.tok], dim=1)
+    model.graphs.end()                                  # the caches of this request die with it: so does the graph captured over them
+    n = new.shape[1]
+    if stopper is not None:                             # all finished: up to the longest row, as generate()
+        own, reason = torch.stack([stopper.length - before, stopper.reason]).tolist()
+        n = n if 0 in reason else max(max(own), 1)
+    # step s scores the token it produced, new[:, s + 1]: the first token's score in front, what lies past the width off
+    scores = tuple(torch.cat([f, sc], dim=1)[:, :n] for f, sc in zip(firsts, scores))
+    if stopper is not None and scores:                  # the scores of a finished row's pads: logprob 0, id -1, value 0
+        pads = torch.arange(n, device=new.device)[None, :] >= torch.tensor(own, device=new.device)[:, None]
+        scores = tuple(sc.masked_fill(pads if sc.dim() == 2 else pads.unsqueeze(-1), fill) for sc, fill in zip(scores, (0.0, -1, 0.0)))
+    return pack_result(input_ids, new[:, :n], scores)

@@ -9,9 +9,9 @@ such a directory and the filled model (config.json, the checkpoint's spellings, 
 kivi_amd/loading.py; here are the family table, make_config and the modules.  Everything outside the attention block is plain
 torch (rocBLAS / hipBLASLt GEMMs).  The reference patches k_bits / v_bits / group_size / residual_length onto the HF config
 (README.md:72-75); the same four fields are read here.
-What a generate call is made of -- left padding, the sampler of the call, the prompt pass and its fork, the eager step, the decode
-loop -- is kivi_amd/generation.py; beam search is kivi_amd/beam.py, the graphed decode step kivi_amd/graph.py (DecodeGraphs), the
-scheduler of continuous batching kivi_amd/serving.py (over admit_() here and kivi_amd/admit.py).
+The public methods carry the API documentation and delegate: what a generate call is made of (padding, sampler, prompt pass, eager
+step, decode loop) is kivi_amd/generation.py; beam search kivi_amd/beam.py; the graphed step and the calls over it kivi_amd/graph.py;
+score / perplexity kivi_amd/scoring.py; the scheduler kivi_amd/serving.py (over admit_() and kivi_amd/admit.py).  DESIGN.md section 33.
 """
 from __future__ import annotations
 
@@ -23,19 +23,15 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import admit, loading, wquant
-from .attention import KiviLayerCacheMF, LlamaAttention_KIVI
+from . import admit, graph, loading, scoring, serving, wquant
+from .attention import LlamaAttention_KIVI
 from .beam import beam_search
 from .generation import (PADS_LEFT, DecodeLead, EagerStepper, _PaddedBatch, decode_loop, leading_pads, left_pad,  # noqa: F401
                          padding_key_row, padding_position_ids, padding_prompt_mask, observe_prompts, bind_suppress,
-                         resolve_sampler)
-from .graph import DecodeGraphs
+                         pack_result, resolve_sampler)
 from .moe import QuantExperts, SparseMoeBlock
 from .prefill import left_padded
-from .sampling import RowSampler
-from .scoring import check_top_k, check_top_logprobs, token_logprobs
-from .scoring import top_logprobs as scoring_top_logprobs
-from .stopping import SYNC_EVERY, StopRows, check_sync_every, resolve_stopping
+from .stopping import SYNC_EVERY, StopRows, resolve_stopping
 
 
 _SHARED_EXPERT_FIELDS = ("shared_expert_intermediate_size", "n_shared_experts", "num_shared_experts")
@@ -357,11 +353,10 @@ class LlamaForCausalLM_KIVI(nn.Module):
         its own); `return_finish`: the result gains a list of (reason, index) per request.
         Per-request constraints (logit_bias, allowed_token_ids, min_new_tokens) come with `sampling`; `allowed_fn`: None, one callable
         or one per request, asked before every pick for the ids or the bitmask the request may emit next."""
-        from .serving import generate_continuous
         if graphed:
             self._refuse_capture("generate_continuous(graphed=True)")
-        return generate_continuous(self, prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, graphed, compact,
-                                   short_admissions, return_logprobs, top_logprobs, stopping, return_finish, allowed_fn)
+        return serving.generate_continuous(self, prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, graphed,
+                                           compact, short_admissions, return_logprobs, top_logprobs, stopping, return_finish, allowed_fn)
 
     # ------------------------------------------------------------------ rebase (DESIGN.md section 17)
     @classmethod
@@ -388,53 +383,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     # ------------------------------------------------------------------ scoring given tokens
     _HEAD_SLAB = 4096            # rows of hidden states per lm_head call of score(): logits exist for one slab at a time
+    _score_plan = staticmethod(scoring.score_plan)      # the name callers of the model know the plan by
 
-    def _score_plan(self, input_ids, first_chunk, chunk_size):
-        """The [a, b) token ranges of the passes of a score() call; ValueError for arguments that cannot be scored (no device work)."""
-        if input_ids.dim() != 2 or input_ids.shape[1] < 2:
-            raise ValueError(f"score needs input_ids (B, T) with T >= 2 (entry i scores token i + 1), got {tuple(input_ids.shape)}")
-        T = input_ids.shape[1]
-        first = T if first_chunk is None else first_chunk
-        if isinstance(first, bool) or not isinstance(first, int) or not 1 <= first <= T:
-            raise ValueError(f"first_chunk has to be an integer in [1, T = {T}], got {first_chunk!r}")
-        step = max(T - first, 1) if chunk_size is None else chunk_size
-        if isinstance(step, bool) or not isinstance(step, int) or step < 1:
-            raise ValueError(f"chunk_size has to be a positive integer, got {chunk_size!r}")
-        return [(0, first)] + [(a, min(a + step, T)) for a in range(first, T, step)]
-
-    def _head_logprobs(self, x, targets, return_rank, top_k: int = 0):
-        """token_logprobs of `targets` (B, q) under lm_head(norm(x)), x (B, q, H): the head runs on slabs of at most _HEAD_SLAB rows
-        (one slab: the very call forward() makes), so logits never exist for more rows than that.  -> (logprobs, ranks or None,
-        top ids or None, top log-probabilities or None); `top_k` > 0: one kivi_token_top_logprobs launch per slab in place of the
-        kivi_token_logprob launch, with the lists (B, q, top_k) of every row."""
-        from .scoring import token_logprobs, top_logprobs
-
-        def head(hs, ts):
-            if top_k:
-                r = top_logprobs(self.lm_head(hs), top_k, ts, return_rank=return_rank)
-                return r.target_logprob, r.rank, r.ids, r.logprobs
-            r = token_logprobs(self.lm_head(hs), ts, return_rank=return_rank)
-            return (r + (None, None)) if return_rank else (r, None, None, None)
-
-        h = self.model.norm(x)
-        B, q = targets.shape
-        if B * q <= self._HEAD_SLAB:
-            return head(h, targets)
-        h, t = h.reshape(B * q, -1), targets.reshape(-1)
-        lp = torch.empty(B * q, dtype=torch.float32, device=x.device)
-        rk = torch.empty(B * q, dtype=torch.int32, device=x.device) if return_rank else None
-        ti = torch.empty((B * q, top_k), dtype=torch.int64, device=x.device) if top_k else None
-        tl = torch.empty((B * q, top_k), dtype=torch.float32, device=x.device) if top_k else None
-        for s in range(0, B * q, self._HEAD_SLAB):
-            sl = slice(s, s + self._HEAD_SLAB)
-            res = head(h[sl], t[sl])
-            for dst, src in zip((lp, rk, ti, tl), res):
-                if dst is not None:
-                    dst[sl] = src
-        return (lp.view(B, q), rk.view(B, q) if return_rank else None, ti.view(B, q, top_k) if top_k else None,
-                tl.view(B, q, top_k) if top_k else None)
-
-    @torch.no_grad()
     def score(self, input_ids: torch.LongTensor, attention_mask: Optional[torch.Tensor] = None,
               past_key_values: Optional[List] = None, first_chunk: Optional[int] = None, chunk_size: Optional[int] = None,
               return_rank: bool = False, top_logprobs: int = 0):
@@ -458,58 +408,13 @@ class LlamaForCausalLM_KIVI(nn.Module):
         past + (tokens so far) columns (pads are on the left, so every such slice holds them).  Token ids are validated against
         vocab_size, and the mask is looked at, once: one synchronisation per call.  T < 2, a chunk size < 1 or first_chunk outside
         [1, T] raise ValueError before any device work."""
-        plan = self._score_plan(input_ids, first_chunk, chunk_size)
-        k = top_logprobs
-        if k != 0:
-            check_top_k(k, self.config.vocab_size, "top_logprobs")
-        B, T = input_ids.shape
-        facts = list(torch.aminmax(input_ids))
-        past_len = self._past_len(past_key_values)
-        if attention_mask is not None:
-            facts.append((attention_mask == 0).any().to(input_ids.device, torch.long))
-            if past_len == 0 and getattr(self.config, "kivi_prefill_kernel", False):
-                facts.append(left_padded(attention_mask).to(input_ids.device, torch.long))
-        lo, hi, *has_pad = (int(v) for v in torch.stack(facts).tolist())
-        if lo < 0 or hi >= self.config.vocab_size:
-            raise ValueError(f"input_ids hold token ids in [{lo}, {hi}], outside the vocabulary [0, {self.config.vocab_size})")
-        valid = torch.ones((B, T - 1), dtype=torch.bool, device=input_ids.device)
-        padded = attention_mask is not None and self._padded(attention_mask, B, past_len + T, past_len, bool(has_pad[0]),
-                                                             bool(has_pad[1]) if len(has_pad) > 1 else None)
-        if padded:
-            real = attention_mask[:, past_len:] != 0
-            valid = real[:, 1:] & real[:, :-1]
-        targets = torch.full((B, T), -100, dtype=torch.long, device=input_ids.device)     # the last token has nothing to predict
-        targets[:, :-1] = torch.where(valid, input_ids[:, 1:], targets[:, :-1])
-        logprobs = torch.empty((B, T), dtype=torch.float32, device=input_ids.device)
-        ranks = torch.empty((B, T), dtype=torch.int32, device=input_ids.device) if return_rank else None
-        top_ids = torch.empty((B, T, k), dtype=torch.int64, device=input_ids.device) if k else None
-        top_lps = torch.empty((B, T, k), dtype=torch.float32, device=input_ids.device) if k else None
-        pasts = past_key_values
-        for a, b in plan:
-            if padded:
-                pb = _PaddedBatch(attention_mask[:, : past_len + b], past_len + a, b - a, lead=padded == PADS_LEFT)
-                x, pasts = self._hidden(input_ids[:, a:b], pasts, pb.mask, pb.position_ids, True)
-            else:
-                x, pasts = self._hidden(input_ids[:, a:b], pasts, None, None, False)
-            lp, rk, ti, tl = self._head_logprobs(x, targets[:, a:b], return_rank, k)
-            logprobs[:, a:b] = lp
-            if return_rank:
-                ranks[:, a:b] = rk
-            if k:
-                top_ids[:, a:b], top_lps[:, a:b] = ti, tl
-        res = (logprobs[:, :-1], valid, pasts) + ((ranks[:, :-1],) if return_rank else ())
-        if k:
-            res += (top_ids[:, :-1].masked_fill(~valid.unsqueeze(-1), -1), top_lps[:, :-1].masked_fill(~valid.unsqueeze(-1), 0.0))
-        return res
+        return scoring.score(self, input_ids, attention_mask, past_key_values, first_chunk, chunk_size, return_rank, top_logprobs)
 
-    @torch.no_grad()
     def perplexity(self, input_ids: torch.LongTensor, attention_mask: Optional[torch.Tensor] = None,
                    past_key_values: Optional[List] = None, first_chunk: Optional[int] = None, chunk_size: Optional[int] = None):
         """exp(-sum of the valid log-probabilities / number of valid entries) of score() with the same arguments:
         (per row (B,), over all rows ()) float64 on the device, the sums taken in fp64.  A row without a valid entry gives NaN."""
-        lp, valid, _ = self.score(input_ids, attention_mask, past_key_values, first_chunk, chunk_size)
-        s, n = lp.double().sum(-1), valid.sum(-1).double()              # invalid entries are exactly 0
-        return torch.exp(-s / n), torch.exp(-s.sum() / n.sum())
+        return scoring.perplexity(self, input_ids, attention_mask, past_key_values, first_chunk, chunk_size)
 
     @torch.no_grad()
     def generate(self, input_ids: torch.LongTensor, max_new_tokens: int, past_key_values: Optional[List] = None,
@@ -588,7 +493,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
         if return_logprobs and num_beams > 1:
             raise ValueError("return_logprobs is for greedy decoding and sampling; beam search (num_beams > 1) returns its "
                              "sequences_scores with return_scores=True")
-        check_top_logprobs(top_logprobs, return_logprobs, num_beams, self.config.vocab_size)
+        scoring.check_top_logprobs(top_logprobs, return_logprobs, num_beams, self.config.vocab_size)
         pick, fan = resolve_sampler(input_ids.device, input_ids.shape[0], num_return_sequences, num_beams, do_sample, temperature,
                                     top_k, top_p, min_p, seed, sampling, repetition_penalty, presence_penalty, frequency_penalty,
                                     self.config.vocab_size, logit_bias, allowed_token_ids, min_new_tokens)
@@ -603,24 +508,17 @@ class LlamaForCausalLM_KIVI(nn.Module):
         bind_suppress(pick, sampling, stops, eos_token_id)
         stepper = EagerStepper(self, input_ids, past_key_values, attention_mask, max_new_tokens, max(num_beams, fan))
         observe_prompts(pick, input_ids, attention_mask, fan)
-        if stops is not None:
-            stopper = stops if isinstance(stops, StopRows) else StopRows(stops, input_ids.device, pad_token_id=pad_token_id)
-            new, logprobs = decode_loop(stepper.logits, stepper.step, pick or (lambda lg: lg.argmax(-1)), max_new_tokens,
-                                        want_logprobs=return_logprobs, top_k=top_logprobs, stopper=stopper)
-            seqs = torch.cat([stepper.input_ids, new], dim=1)
-            if top_logprobs:
-                return (seqs,) + logprobs
-            return (seqs, logprobs) if return_logprobs else seqs
-        if num_beams > 1:
+        if num_beams > 1:                       # (with beams resolve_stopping has answered None: one eos id, handled there)
             seqs, scores = beam_search(stepper.step, input_ids, stepper.logits, num_beams, max_new_tokens, eos_token_id,
                                        pad_token_id, length_penalty, early_stopping, num_return_sequences)
             return (seqs, scores) if return_scores else seqs
-        new, logprobs = decode_loop(stepper.logits, stepper.step, pick or (lambda lg: lg.argmax(-1)), max_new_tokens, eos_token_id,
-                                    pad_token_id, return_logprobs, top_logprobs)
-        seqs = torch.cat([stepper.input_ids, new], dim=1)
-        if top_logprobs:
-            return (seqs,) + logprobs
-        return (seqs, logprobs) if return_logprobs else seqs
+        if stops is None:                       # the loop's torch path: no finish condition, or one int eos id
+            finish = dict(eos_token_id=eos_token_id, pad_token_id=pad_token_id)
+        else:                                   # a tracker on the device: the caller's, or one for this call
+            finish = dict(stopper=stops if isinstance(stops, StopRows) else StopRows(stops, input_ids.device, pad_token_id=pad_token_id))
+        new, logprobs = decode_loop(stepper.logits, stepper.step, pick or (lambda lg: lg.argmax(-1)), max_new_tokens,
+                                    want_logprobs=return_logprobs, top_k=top_logprobs, **finish)
+        return pack_result(stepper.input_ids, new, logprobs)
 
     # ------------------------------------------------------------------ hipGraph decode (kivi_amd/graph.py: DecodeGraphs)
     def _refuse_capture(self, what: str) -> None:
@@ -636,24 +534,13 @@ class LlamaForCausalLM_KIVI(nn.Module):
                        logprobs: Optional[int] = None, stopper=None) -> None:
         """Capture the decode graphs for this batch size now (otherwise on the first graphed step).  `logprobs`, `stopper`: as
         decode_graphed."""
-        self._refuse_capture("prepare_graphs")
-        key = None if sampler is None else sampler.key()
-        lead = padded and bool(getattr(self.config, "kivi_decode_lead", False))
-        if stopper is not None:
-            if self.graphs is None or not self.graphs.matches(batch, whole, padded, key, lead, logprobs, stopper.key()):
-                self.graphs = DecodeGraphs(self, batch, device, whole, padded, sampler, lead, logprobs, stopper)
-        elif logprobs is None:                                  # (the call as it was before the option existed)
-            if self.graphs is None or not self.graphs.matches(batch, whole, padded, key, lead):
-                self.graphs = DecodeGraphs(self, batch, device, whole, padded, sampler, lead)
-        elif self.graphs is None or not self.graphs.matches(batch, whole, padded, key, lead, logprobs):
-            self.graphs = DecodeGraphs(self, batch, device, whole, padded, sampler, lead, logprobs)
+        graph.prepare_graphs(self, batch, device, whole, padded, sampler, logprobs, stopper)
 
     def release_graphs(self) -> None:
         """Drop the static buffers and everything captured; the next graphed decode builds them again."""
         self.graphs = None
         self._stoppers.clear()
 
-    @torch.no_grad()
     def decode_graphed(self, tok: torch.LongTensor, past_key_values: List, position: int, steps: int,
                        attention_mask: Optional[torch.Tensor] = None, sampler=None, sampling=None,
                        logprobs: Optional[int] = None, stopper=None, sync_every: int = SYNC_EVERY):
@@ -674,48 +561,9 @@ class LlamaForCausalLM_KIVI(nn.Module):
         every s that is a multiple of `sync_every`, the host reads the stopper's `n_live` -- the only synchronisation -- and leaves
         when it is 0, so fewer than `steps` columns may come back and at most sync_every - 1 steps run after the last row has
         finished.  `sync_every=None`: never read, all `steps` run."""
-        self._refuse_capture("decode_graphed")
-        if logprobs is not None and logprobs != 0:
-            check_top_k(logprobs, self.config.vocab_size, "logprobs")
-        if stopper is not None:
-            if not isinstance(stopper, StopRows) or stopper.B != tok.shape[0]:
-                raise ValueError(f"decode_graphed(stopper=) takes a StopRows of {tok.shape[0]} rows")
-            check_sync_every(sync_every)
-        if sampling is not None:
-            if sampler is not None:
-                raise ValueError("pass either sampler= or sampling=, not both")
-            if not isinstance(sampling, RowSampler):
-                raise ValueError("decode_graphed(sampling=) takes a RowSampler")
-            if sampling.B != tok.shape[0]:
-                raise ValueError(f"the RowSampler holds {sampling.B} rows, the step has {tok.shape[0]}")
-            sampler = sampling
-        caches = [p.layer for p in past_key_values]
-        whole = all(isinstance(c, KiviLayerCacheMF) for c in caches)      # the whole step as one graph, else per-layer graphs
-        B, kv0 = tok.shape[0], caches[0].kv_seq_len
-        padded = attention_mask is not None and self._padded(attention_mask, B, kv0 + 1, kv0)
-        self.prepare_graphs(B, tok.device, whole, padded, sampler, logprobs, stopper)
-        self.graphs.begin(tok, caches, attention_mask)
-        out, lps, tids, tlps = [], [], [], []
-        for s in range(steps):
-            if stopper is not None and sync_every is not None and s % sync_every == 0 and int(stopper.n_live) == 0:
-                break
-            out.append(self.graphs.tok.clone())
-            self.graphs.step(position + s)
-            if logprobs is not None:
-                lps.append(self.graphs.lp.clone())
-                if logprobs:
-                    tids.append(self.graphs.top_ids.clone())
-                    tlps.append(self.graphs.top_lp.clone())
-        toks = torch.cat(out, dim=1) if out else tok.new_empty((B, 0))
-        if logprobs is None:
-            return toks
-        res = (toks, torch.cat(lps, dim=1) if lps else self.graphs.lp.new_empty((B, 0)))
-        if logprobs:
-            res += (torch.cat(tids, dim=1) if tids else tok.new_empty((B, 0, logprobs)),
-                    torch.cat(tlps, dim=1) if tlps else self.graphs.lp.new_empty((B, 0, logprobs)))
-        return res
+        return graph.decode_graphed(self, tok, past_key_values, position, steps, attention_mask, sampler, sampling, logprobs, stopper,
+                                    sync_every)
 
-    @torch.no_grad()
     def generate_graphed(self, input_ids: torch.LongTensor, max_new_tokens: int,
                          attention_mask: Optional[torch.Tensor] = None, num_beams: int = 1, do_sample: bool = False,
                          temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
@@ -743,76 +591,10 @@ class LlamaForCausalLM_KIVI(nn.Module):
         replays the graphs that exist; a StopRows passed as `stopping=` is used as it is and keys the graphs by its own buffers.
         `logit_bias` / `allowed_token_ids` / `min_new_tokens`: as in generate(); the constrained draw is
         inside the captured step, and so is the advance towards the end of the suppression."""
-        self._refuse_capture("generate_graphed")
-        if sampling is None and num_beams != 1 and not do_sample:
-            raise ValueError(f"generate_graphed is greedy only (num_beams={num_beams}); use generate(num_beams=...)")
-        check_top_logprobs(top_logprobs, return_logprobs, num_beams, self.config.vocab_size)
-        pick, _ = resolve_sampler(input_ids.device, input_ids.shape[0], 1, num_beams, do_sample, temperature, top_k, top_p, min_p,
-                                  seed, sampling, repetition_penalty, presence_penalty, frequency_penalty, self.config.vocab_size,
-                                  logit_bias, allowed_token_ids, min_new_tokens)
-        check_sync_every(sync_every)
-        stops = resolve_stopping(input_ids.shape[0], max_new_tokens, eos_token_id, pad_token_id, stop_token_ids, stop_sequences,
-                                 stopping, 1, self.config.vocab_size, torch_eos=False)
-        bind_suppress(pick, sampling, stops, eos_token_id)
-        logits, pasts = self.forward(input_ids, padding_mask=attention_mask)
-        observe_prompts(pick, input_ids, attention_mask)
-        if attention_mask is not None:
-            attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, :1])], dim=1)
-        tok = logits.argmax(-1) if pick is None else pick(logits)
-        if stops is not None and max_new_tokens > 0:
-            return self._generate_graphed_stopping(input_ids, max_new_tokens, attention_mask, pick, logits, pasts, tok, stops,
-                                                   pad_token_id, sync_every, top_logprobs if return_logprobs else None)
-        if not return_logprobs:
-            new = self.decode_graphed(tok, pasts, input_ids.shape[1], max_new_tokens, attention_mask, pick)
-            self.graphs.end()           # the caches of this request die with it: so does the graph captured over them
-            return torch.cat([input_ids, new], dim=1)
-        k = top_logprobs
-        first = scoring_top_logprobs(logits, k, tok) if k else None
-        first_lp = first.target_logprob if k else token_logprobs(logits, tok)
-        new, *scores = self.decode_graphed(tok, pasts, input_ids.shape[1], max_new_tokens, attention_mask, pick, logprobs=k)
-        self.graphs.end()
-        n = new.shape[1]                # step s scores the token after new[:, s]: the first token's score in front, the last one off
-        firsts = (first_lp,) + ((first.ids, first.logprobs) if k else ())
-        return (torch.cat([input_ids, new], dim=1),) + tuple(torch.cat([f, sc], dim=1)[:, :n] for f, sc in zip(firsts, scores))
-
-    def _kept_stopper(self, params, device, pad_token_id: int) -> StopRows:
-        """The model's own finish tracker for (rows, device, pad), its rows bound to `params`: the buffers stay from call to call, so
-        the graphs captured over them are replayed whatever the stops of the next call are."""
-        kept = self._stoppers
-        key = (len(params), str(device), pad_token_id)
-        if key in kept:
-            kept[key].rebind(params)
-        else:
-            kept[key] = StopRows(params, device, pad_token_id=pad_token_id)
-        return kept[key]
-
-    def _generate_graphed_stopping(self, input_ids, max_new_tokens, attention_mask, pick, logits, pasts, tok, stops, pad_token_id,
-                                   sync_every, k):
-        """generate_graphed with finish conditions, from the first token `tok` picked of the prompt `logits` on; k: None, or the
-        top_logprobs of a return_logprobs call."""
-        stopper = stops if isinstance(stops, StopRows) else self._kept_stopper(stops, input_ids.device, pad_token_id)
-        before = stopper.length.clone()                 # (a caller's StopRows may have counted earlier tokens)
-        stopper(tok)                                    # the first token, eagerly
-        firsts = ()
-        if k is not None:
-            first = scoring_top_logprobs(logits, k, tok) if k else None
-            firsts = (first.target_logprob, first.ids, first.logprobs) if k else (token_logprobs(logits, tok),)
-        res = self.decode_graphed(tok, pasts, input_ids.shape[1], max_new_tokens - 1, attention_mask, pick, logprobs=k,
-                                  stopper=stopper, sync_every=sync_every)
-        fed, scores = (res, ()) if k is None else (res[0], res[1:])
-        new = torch.cat([fed, self.graphs.tok], dim=1)  # step s has produced new[:, s + 1] and its scores
-        self.graphs.end()
-        own, reason = torch.stack([stopper.length - before, stopper.reason]).tolist()
-        width = new.shape[1] if 0 in reason else max(max(own), 1)       # all finished: up to the longest row, as generate()
-        seqs = torch.cat([input_ids, new[:, :width]], dim=1)
-        if k is None:
-            return seqs
-        pads = torch.arange(width, device=new.device)[None, :] >= torch.tensor(own, device=new.device)[:, None]
-        lp, *tops = (torch.cat([f, sc], dim=1)[:, :width] for f, sc in zip(firsts, scores))
-        out = (seqs, lp.masked_fill(pads, 0.0))
-        if k:
-            out += (tops[0].masked_fill(pads.unsqueeze(-1), -1), tops[1].masked_fill(pads.unsqueeze(-1), 0.0))
-        return out
+        return graph.generate_graphed(self, input_ids, max_new_tokens, attention_mask, num_beams, do_sample, temperature, top_k, top_p,
+                                      min_p, seed, sampling, repetition_penalty, presence_penalty, frequency_penalty, return_logprobs,
+                                      top_logprobs, eos_token_id, pad_token_id, stop_token_ids, stop_sequences, stopping, sync_every,
+                                      logit_bias, allowed_token_ids, min_new_tokens)
 
     @classmethod
     def from_pretrained(cls, path: str, device="cuda", dtype=torch.float16, **kivi):

@@ -10,6 +10,11 @@ number of j with x_j > x_t, or x_j == x_t and j < t (0 exactly when argmax of th
 counts in, from one launch of kivi_token_top_logprobs; with targets its target_logprob / lse / rank hold the
 bits token_logprobs gives.
 
+`picked_scores(logits, tokens, k)` chooses between the two for the tokens a decode loop has just picked (generation.decode_loop,
+graph.generate_graphed, serving.generate_continuous); `score_into` is the same launch into the static buffers of a captured step.
+`score(model, ...)` / `perplexity(model, ...)`: teacher-forced scoring over a model, behind the model's
+methods of those names -- `score_plan` cuts the tokens into passes, `head_logprobs` runs the head on slabs of model._HEAD_SLAB rows.
+
 `reference_token_logprobs` / `reference_top_logprobs` restate the contracts in fp64 on the CPU for tests and tools; the product
 path never calls them.
 """
@@ -20,6 +25,8 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
+from .generation import PADS_LEFT, _PaddedBatch
+from .prefill import left_padded
 
 
 def _row_stride(logits: torch.Tensor):
@@ -156,6 +163,103 @@ def score_into(logits: torch.Tensor, tokens: torch.Tensor, lp: torch.Tensor, top
                    "kivi_token_top_logprobs")
 
 
+def picked_scores(logits: torch.Tensor, tokens: torch.Tensor, k: Optional[int]) -> tuple:
+    """The scores of the tokens just picked, `tokens` (B, 1), under the logits in hand (B, 1, V): () for k None (nothing is asked
+    for), (logprob (B, 1),) for k == 0 from one kivi_token_logprob launch, (logprob, top_ids (B, 1, k), top_logprobs (B, 1, k)) for
+    k > 0 from one kivi_token_top_logprobs launch.  A token of -100 (a row with nothing to score) gets logprob 0."""
+    if k is None:
+        return ()
+    if not k:
+        return (token_logprobs(logits, tokens),)
+    res = top_logprobs(logits, k, tokens)
+    return res.target_logprob, res.ids, res.logprobs
+
+
+# ------------------------------------------------------------------ scoring a model's given tokens (DESIGN.md section 14)
+def score_plan(input_ids: torch.Tensor, first_chunk: Optional[int], chunk_size: Optional[int]):
+    """The [a, b) token ranges of the passes of a score() call; ValueError for arguments that cannot be scored (no device work)."""
+    if input_ids.dim() != 2 or input_ids.shape[1] < 2:
+        raise ValueError(f"score needs input_ids (B, T) with T >= 2 (entry i scores token i + 1), got {tuple(input_ids.shape)}")
+    T = input_ids.shape[1]
+    first = T if first_chunk is None else first_chunk
+    if isinstance(first, bool) or not isinstance(first, int) or not 1 <= first <= T:
+        raise ValueError(f"first_chunk has to be an integer in [1, T = {T}], got {first_chunk!r}")
+    step = max(T - first, 1) if chunk_size is None else chunk_size
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError(f"chunk_size has to be a positive integer, got {chunk_size!r}")
+    return [(0, first)] + [(a, min(a + step, T)) for a in range(first, T, step)]
+
+
+def head_logprobs(model, x, targets, return_rank, top_k: int = 0):
+    """token_logprobs of `targets` (B, q) under lm_head(norm(x)), x (B, q, H): the head runs on slabs of at most model._HEAD_SLAB
+    rows (one slab: the very call forward() makes), so logits never exist for more rows than that.  -> (logprobs, ranks or None,
+    top ids or None, top log-probabilities or None); `top_k` > 0: one kivi_token_top_logprobs launch per slab in place of the
+    kivi_token_logprob launch, with the lists (B, q, top_k) of every row."""
+    def head(hs, ts):
+        if top_k:
+            r = top_logprobs(model.lm_head(hs), top_k, ts, return_rank=return_rank)
+            return r.target_logprob, r.rank, r.ids, r.logprobs
+        r = token_logprobs(model.lm_head(hs), ts, return_rank=return_rank)
+        return (r + (None, None)) if return_rank else (r, None, None, None)
+
+    h = model.model.norm(x)
+    B, q = targets.shape
+    slab = model._HEAD_SLAB
+    if B * q <= slab:
+        return head(h, targets)
+    h, t = h.reshape(B * q, -1), targets.reshape(-1)
+    slabs = [head(h[s:s + slab], t[s:s + slab]) for s in range(0, B * q, slab)]
+    return tuple(None if p[0] is None else torch.cat(p).view((B, q) + p[0].shape[1:]) for p in zip(*slabs))
+
+
+@torch.no_grad()
+def score(model, input_ids, attention_mask, past_key_values, first_chunk, chunk_size, return_rank, top_k):
+    """LlamaForCausalLM_KIVI.score (its docstring is the reference; `top_k` is its `top_logprobs`)."""
+    plan = score_plan(input_ids, first_chunk, chunk_size)
+    k, vocab = top_k, model.config.vocab_size
+    if k != 0:
+        check_top_k(k, vocab, "top_logprobs")
+    B, T = input_ids.shape
+    facts = list(torch.aminmax(input_ids))
+    past_len = model._past_len(past_key_values)
+    if attention_mask is not None:
+        facts.append((attention_mask == 0).any().to(input_ids.device, torch.long))
+        if past_len == 0 and getattr(model.config, "kivi_prefill_kernel", False):
+            facts.append(left_padded(attention_mask).to(input_ids.device, torch.long))
+    lo, hi, *has_pad = (int(v) for v in torch.stack(facts).tolist())        # the one synchronisation of the call
+    if lo < 0 or hi >= vocab:
+        raise ValueError(f"input_ids hold token ids in [{lo}, {hi}], outside the vocabulary [0, {vocab})")
+    valid = torch.ones((B, T - 1), dtype=torch.bool, device=input_ids.device)
+    padded = attention_mask is not None and model._padded(attention_mask, B, past_len + T, past_len, bool(has_pad[0]),
+                                                          bool(has_pad[1]) if len(has_pad) > 1 else None)
+    if padded:
+        real = attention_mask[:, past_len:] != 0
+        valid = real[:, 1:] & real[:, :-1]
+    targets = torch.full((B, T), -100, dtype=torch.long, device=input_ids.device)     # the last token has nothing to predict
+    targets[:, :-1] = torch.where(valid, input_ids[:, 1:], targets[:, :-1])
+    pasts, passes = past_key_values, []
+    for a, b in plan:
+        if padded:
+            pb = _PaddedBatch(attention_mask[:, : past_len + b], past_len + a, b - a, lead=padded == PADS_LEFT)
+            x, pasts = model._hidden(input_ids[:, a:b], pasts, pb.mask, pb.position_ids, True)
+        else:
+            x, pasts = model._hidden(input_ids[:, a:b], pasts, None, None, False)
+        passes.append(head_logprobs(model, x, targets[:, a:b], return_rank, k))
+    lp, rk, ti, tl = (None if p[0] is None else torch.cat(p, dim=1)[:, :-1] for p in zip(*passes))
+    res = (lp, valid, pasts) + ((rk,) if return_rank else ())
+    if k:
+        res += (ti.masked_fill(~valid.unsqueeze(-1), -1), tl.masked_fill(~valid.unsqueeze(-1), 0.0))
+    return res
+
+
+@torch.no_grad()
+def perplexity(model, input_ids, attention_mask, past_key_values, first_chunk, chunk_size):
+    """LlamaForCausalLM_KIVI.perplexity: exp(-mean valid log-probability) of model.score() with the same arguments, sums in fp64."""
+    lp, valid, _ = model.score(input_ids, attention_mask, past_key_values, first_chunk, chunk_size)
+    s, n = lp.double().sum(-1), valid.sum(-1).double()              # invalid entries are exactly 0
+    return torch.exp(-s / n), torch.exp(-s.sum() / n.sum())
+
+
 # ------------------------------------------------------------------ CPU restatement (tests, tools)
 def reference_top_logprobs(logits: torch.Tensor, k: int):
     """fp64 CPU restatement of the lists of kivi_token_top_logprobs: (ids int64 (..., k), logprobs float64 (..., k)).  A stable
@@ -163,7 +267,6 @@ def reference_top_logprobs(logits: torch.Tensor, k: int):
     x = logits.detach().cpu().double()
     order = torch.sort(x, dim=-1, descending=True, stable=True).indices[..., :k]
     return order, x.gather(-1, order) - torch.logsumexp(x, -1, keepdim=True)
-
 
 
 def reference_token_logprobs(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100):

@@ -59,8 +59,7 @@ import torch
 
 from .generation import decode_key_row, left_pad, padding_key_row
 from .sampling import RowSampler, SamplingParams
-from .scoring import check_top_logprobs, token_logprobs
-from .scoring import top_logprobs as score_top
+from .scoring import check_top_logprobs, picked_scores
 from .stopping import LIVE, StopParams, StopState, stop_ids
 
 
@@ -216,10 +215,7 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
         if skip:
             t = t.clone()
             t[list(skip)] = -100
-        if not k:
-            return (token_logprobs(lg, t),)
-        res = score_top(lg, k, t)
-        return res.target_logprob, res.ids, res.logprobs
+        return picked_scores(lg, t, k)
 
     out: List[List[int]] = [[] for _ in range(N)]
 
@@ -304,11 +300,9 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
             mask2d = torch.cat([mask2d, torch.ones_like(mask2d)], dim=1)
         m = mask2d[:, : L + 1]                                                 # the fed token is real in every row
         bind_masks(sampler, [(b, owner[b]) for b in range(B) if owner[b] is not None])
-        if graphed and return_logprobs:
-            _, *scores = model.decode_graphed(tok, pasts, L, 1, attention_mask=m, sampling=sampler, logprobs=k)
-            tok = model.graphs.tok.clone()
-        elif graphed:
-            model.decode_graphed(tok, pasts, L, 1, attention_mask=m, sampling=sampler)
+        if graphed:
+            res = model.decode_graphed(tok, pasts, L, 1, attention_mask=m, sampling=sampler, logprobs=k if return_logprobs else None)
+            scores = res[1:] if return_logprobs else None
             tok = model.graphs.tok.clone()
         else:
             # (config.kivi_decode_lead: the row travels with the leading zeros of the SAME mask -- what an admission rewrote and

@@ -358,6 +358,34 @@ def test_graph_owner_keys_on_the_lead_and_keeps_a_static_buffer(monkeypatch):
     assert g.lead.tolist() == [3, 5, 1] and g.lead.data_ptr() == ptr and _leading_masked(g.mask[..., :8]) == [3, 5, 1]
 
 
+def test_prepare_graphs_builds_anew_exactly_when_a_key_field_changes(monkeypatch):
+    model = _model(True, monkeypatch, [])
+
+    def prepared(batch=3, **kw):
+        model.prepare_graphs(batch, "cpu", whole=True, **kw)
+        return model.graphs
+
+    held = prepared()
+    assert prepared() is held and held.matches(3, True, False, None), "the same arguments keep the object; the 4-argument form finds it"
+    seen = [held]
+    for kw in (dict(batch=2), dict(), dict(padded=True), dict(), dict(logprobs=0), dict(logprobs=3), dict()):
+        new = prepared(**kw)
+        assert all(new is not g for g in seen) and prepared(**kw) is new, kw
+        assert (new.B, new.padded, new.logprobs) == (kw.get("batch", 3), kw.get("padded", False), kw.get("logprobs")) and new.whole
+        assert (new.lp is None) == (new.logprobs is None) and (new.top_ids is None) == (not new.logprobs)
+        seen.append(new)
+    assert model.graphs.matches(3, True, False, None)
+    # the lead is the model's decode_lead option, and only of a padded batch
+    assert prepared().lead is None
+    with_lead = prepared(padded=True)
+    assert with_lead.lead is not None and with_lead.matches(3, True, True, None, True) and prepared(padded=True) is with_lead
+    model.config.kivi_decode_lead = False
+    without = prepared(padded=True)
+    assert without is not with_lead and without.lead is None and without.matches(3, True, True, None) and prepared(padded=True) is without
+    model.release_graphs()
+    assert model.graphs is None
+
+
 def test_hook_state_cache_takes_a_lead_and_steps_as_before(monkeypatch):
     from kivi_amd.attention import kivi_attention_decode
     from kivi_amd.cache import KiviLayerCache

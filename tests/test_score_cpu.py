@@ -130,13 +130,14 @@ def test_score_and_generate_refuse_bad_arguments_before_device_work():
 
 
 def test_score_plan_covers_every_token_once():
-    m = _tiny()
+    from kivi_amd.scoring import score_plan
     ids = torch.zeros((1, 50), dtype=torch.long)
-    assert m._score_plan(ids, None, None) == [(0, 50)]
-    assert m._score_plan(ids, 50, 7) == [(0, 50)]
-    assert m._score_plan(ids, 40, None) == [(0, 40), (40, 50)]
-    assert m._score_plan(ids, 40, 7) == [(0, 40), (40, 47), (47, 50)]
-    assert m._score_plan(ids, 1, 1) == [(i, i + 1) for i in range(50)]
+    assert score_plan(ids, None, None) == [(0, 50)]
+    assert score_plan(ids, 50, 7) == [(0, 50)]
+    assert score_plan(ids, 40, None) == [(0, 40), (40, 50)]
+    assert score_plan(ids, 40, 7) == [(0, 40), (40, 47), (47, 50)]
+    assert score_plan(ids, 1, 1) == [(i, i + 1) for i in range(50)]
+    assert _tiny()._score_plan(ids, 40, 7) == score_plan(ids, 40, 7)           # the model still answers to the name it had
 
 
 def test_row_stride_collapse():

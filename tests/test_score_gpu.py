@@ -196,6 +196,7 @@ def _same_caches(pa, pb):
 @pytest.mark.parametrize("layout", ["mfma", "hook"])
 @pytest.mark.parametrize("nkv", [1, 4])
 def test_score_one_pass_and_chunked(nkv, layout, monkeypatch):
+    from kivi_amd.scoring import score_plan
     from kivi_amd.scoring import reference_token_logprobs
     _layouts(monkeypatch, layout)
     model = _model(nkv, 31)
@@ -210,7 +211,7 @@ def test_score_one_pass_and_chunked(nkv, layout, monkeypatch):
     bar = BAR * torch.maximum(torch.maximum(torch.ones_like(rlse), rlse.abs()), xt.abs())
     assert ((lp.cpu().double() - rlp).abs() <= bar).all() and torch.equal(rank.cpu().long(), rrank)
     for c in (1, 7, 33):
-        plan = model._score_plan(ids, 40, c)
+        plan = score_plan(ids, 40, c)
         assert len(plan) == 1 + -(-50 // c)
         got, v, pa = model.score(ids, first_chunk=40, chunk_size=c)
         ref, pb = _compose(model, ids, plan)
@@ -222,6 +223,7 @@ def test_score_one_pass_and_chunked(nkv, layout, monkeypatch):
 @pytest.mark.parametrize("layout", ["mfma", "hook"])
 @pytest.mark.parametrize("nkv", [1, 4])
 def test_score_left_padded_batch(nkv, layout, monkeypatch):
+    from kivi_amd.scoring import score_plan
     from kivi_amd.llama import left_pad
     _layouts(monkeypatch, layout)
     model = _model(nkv, 32)
@@ -229,7 +231,7 @@ def test_score_left_padded_batch(nkv, layout, monkeypatch):
     seqs = [torch.randint(1, 320, (n,), generator=g).tolist() for n in (50, 23, 41)]
     ids, mask = left_pad(seqs, pad_token_id=0, device="cuda")
     got, valid, pa = model.score(ids, attention_mask=mask, first_chunk=40, chunk_size=7)
-    ref, pb = _compose(model, ids, model._score_plan(ids, 40, 7), mask=mask)
+    ref, pb = _compose(model, ids, score_plan(ids, 40, 7), mask=mask)
     want = torch.zeros((3, 49), dtype=torch.bool)
     for r, n in enumerate((50, 23, 41)):
         want[r, 50 - n:] = True                        # context and target real: from the row's first real token on
@@ -251,6 +253,7 @@ def test_score_left_padded_batch(nkv, layout, monkeypatch):
 @pytest.mark.parametrize("layout", ["mfma", "hook"])
 @pytest.mark.parametrize("nkv", [1, 4])
 def test_score_second_turn_and_perplexity(nkv, layout, monkeypatch):
+    from kivi_amd.scoring import score_plan
     _layouts(monkeypatch, layout)
     model = _model(nkv, 33)
     gen = torch.Generator("cuda").manual_seed(5)
@@ -260,7 +263,7 @@ def test_score_second_turn_and_perplexity(nkv, layout, monkeypatch):
     got, valid, pa = model.score(ids2, past_key_values=past, first_chunk=9, chunk_size=5)
     assert getattr(pa[0].layer, "layout", "hook") == layout and pa[0][-1] == 68 and got.shape == (2, 22)
     _, past = model(ids1)
-    ref, pb = _compose(model, ids2, model._score_plan(ids2, 9, 5), past=past)
+    ref, pb = _compose(model, ids2, score_plan(ids2, 9, 5), past=past)
     assert torch.equal(got, ref)
     _same_caches(pa, pb)
     # perplexity: exp(-mean) of those entries in fp64, per row and over all rows

@@ -204,3 +204,25 @@ def test_generate_continuous_finishes_by_the_rule(layout, monkeypatch):
                                     return_finish=True)
     assert len(out) == 3 and [t.tolist() for t in out[0]] == runs[0][0] and out[2] == runs[0][1]
     assert all(lp.shape == t.shape for lp, t in zip(out[1], out[0]))
+
+
+@pytest.mark.parametrize("n", [1, 2])
+@pytest.mark.parametrize("layout", ["mfma", "hook"])
+def test_generate_graphed_equals_generate_at_the_edge_lengths(layout, n, monkeypatch):
+    """max_new_tokens 1 and 2 -- no graphed step and one with finish conditions, one and two without --, scores and lists with them;
+    with the conditions row 0 ends at its first token, so at n = 2 its second column is a pad with masked scores."""
+    _layouts(monkeypatch, layout)
+    model = _model(4, 76)
+    ids, mask = _batch(10)
+    T = ids.shape[1]
+    first = int(model.generate(ids, 1, attention_mask=mask)[0, T])
+    stops = [StopParams([first]), StopParams(), StopParams([NEVER])]
+    for how in (dict(), dict(stopping=stops, pad_token_id=PAD)):
+        args = dict(attention_mask=mask, return_logprobs=True, top_logprobs=3, **how)
+        eager, got = model.generate(ids, n, **args), model.generate_graphed(ids, n, **args)
+        assert eager[0].shape == (3, T + n) and eager[1].shape == (3, n) and eager[2].shape == eager[3].shape == (3, n, 3)
+        assert torch.equal(got[0], eager[0]) and _bits_equal(got[1], eager[1]), (layout, n, how)
+        assert torch.equal(got[2], eager[2]) and _bits_equal(got[3], eager[3]), (layout, n, how)
+        assert torch.equal(model.generate_graphed(ids, n, attention_mask=mask, **how), eager[0])
+        if how and n == 2:
+            assert eager[0][0, T:].tolist() == [first, PAD] and eager[1][0, 1] == 0 and eager[2][0, 1].tolist() == [-1] * 3

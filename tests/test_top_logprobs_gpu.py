@@ -238,6 +238,7 @@ def _compose_top(model, ids, plan, k, mask=None):
 @pytest.mark.parametrize("layout", ["mfma", "hook"])
 @pytest.mark.parametrize("nkv", [1, 4])
 def test_score_top_logprobs(nkv, layout, monkeypatch):
+    from kivi_amd.scoring import score_plan
     from kivi_amd.llama import left_pad
     from test_score_gpu import _layouts, _same_caches
     _layouts(monkeypatch, layout)
@@ -251,7 +252,7 @@ def test_score_top_logprobs(nkv, layout, monkeypatch):
         assert _bits_equal(lp, lp0) and torch.equal(valid, valid0), (layout, kw)
         _same_caches(past, past0)
         assert ti.shape == tl.shape == (2, T - 1, 5) and ti.dtype == torch.int64 and tl.dtype == torch.float32
-        ri, rl = _compose_top(model, ids, model._score_plan(ids, kw.get("first_chunk"), kw.get("chunk_size")), 5)
+        ri, rl = _compose_top(model, ids, score_plan(ids, kw.get("first_chunk"), kw.get("chunk_size")), 5)
         assert torch.equal(ti, ri) and _bits_equal(tl, rl), (layout, kw)
         # with the rank: the scored token sits at its rank with the bits of its log-probability
         res = model.score(ids, return_rank=True, top_logprobs=5, **kw)
@@ -268,7 +269,7 @@ def test_score_top_logprobs(nkv, layout, monkeypatch):
     lp, valid, _, ti, tl = model.score(pids, attention_mask=mask, first_chunk=40, chunk_size=7, top_logprobs=5)
     assert _bits_equal(lp, lp0) and torch.equal(valid, valid0) and not bool(valid.all())
     assert bool((ti[~valid] == -1).all()) and bool((tl[~valid] == 0).all()) and bool((ti[valid] >= 0).all())
-    ri, rl = _compose_top(model, pids, model._score_plan(pids, 40, 7), 5, mask=mask)
+    ri, rl = _compose_top(model, pids, score_plan(pids, 40, 7), 5, mask=mask)
     assert torch.equal(ti[valid], ri[valid]) and _bits_equal(tl[valid], rl[valid])
 
 
@@ -417,3 +418,27 @@ def test_generate_continuous_mixed_requests(kw, layout, monkeypatch):
             _check_lists(toks[r], lps[r], ti[r], tl[r], greedy=not params[r].do_sample)
     for a, b in zip(runs[0], runs[1]):                               # graphed equals eager bit for bit
         assert all(_bits_equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+def test_picked_scores_is_the_direct_launch_and_what_score_into_leaves(dtype):
+    """The one choice of the decode loops: nothing, kivi_token_logprob, or kivi_token_top_logprobs -- the bits of the direct calls
+    and of the captured step's buffers, a row with the ignore index among them."""
+    from kivi_amd.scoring import picked_scores, score_into, token_logprobs, top_logprobs
+    g = torch.Generator().manual_seed(23)
+    logits = (torch.randn((3, 1, 320), generator=g) * 4).to(dtype).cuda()
+    tokens = torch.tensor([[7], [-100], [319]], device="cuda")
+    assert picked_scores(logits, tokens, None) == ()
+    one = picked_scores(logits, tokens, 0)
+    assert len(one) == 1 and _bits_equal(one[0], token_logprobs(logits, tokens)) and one[0].shape == (3, 1)
+    assert one[0][:, 0].tolist()[1] == 0 and bool((one[0][[0, 2]] < 0).all())
+    lp, ids, top = picked_scores(logits, tokens, 3)
+    ref = top_logprobs(logits, 3, tokens)
+    assert _bits_equal(lp, ref.target_logprob) and torch.equal(ids, ref.ids) and _bits_equal(top, ref.logprobs)
+    assert _bits_equal(lp, one[0]) and ids.shape == top.shape == (3, 1, 3) and ids.dtype == torch.int64
+    buf = torch.full((3, 1), float("nan"), device="cuda")
+    score_into(logits, tokens, buf)
+    assert _bits_equal(buf, one[0])
+    buf, bi, bt = torch.full((3, 1), float("nan"), device="cuda"), torch.full((3, 1, 3), -7, device="cuda"), torch.full((3, 1, 3), 1.0, device="cuda")
+    score_into(logits, tokens, buf, bi, bt)
+    assert _bits_equal(buf, lp) and torch.equal(bi, ids) and _bits_equal(bt, top)
