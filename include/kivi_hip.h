@@ -1119,6 +1119,27 @@ int kivi_w4_linear(const void* x, int64_t x_stride, int dtype, int N, int O, int
 int kivi_w4_gate_up(const void* x, int64_t x_stride, int dtype, int N, int I, int K, int group, const void* gate_qweight,
                     const void* gate_scales, const void* gate_mins, const void* up_qweight, const void* up_scales,
                     const void* up_mins, void* y, int64_t y_stride, kivi_stream_t stream);
+/*
+ * Per-request LoRA adapters: the batched low-rank side path of a linear layer, two launches, nothing read
+ * back, so a stream capture may hold them.  S slots of table rank R in {8, 16, 32, 64}; A (S, R, K) and B (S, O, R) contiguous in
+ * the dtype -- 16 (fp16) or KIVI_LOGITS_BF16 (bf16) --, an adapter of rank r < R in rows / columns [0, r) of its slot and zeros
+ * behind them; scale (S) fp32; ranks (S) int32; slots (N / Q) int32, one per row of the pass: token n belongs to row n / Q.
+ *
+ * kivi_lora_shrink   t[n, j] = sum_k A[s, j, k] * x[n, k] for s = slots[n / Q] in [0, S): fp32, the order of the sum a function of
+ *                    K alone.  x (N, K) by x_stride elements (a multiple of 8), 16-byte aligned; t (N, R) fp32, contiguous.
+ * kivi_lora_expand   y[n, o] <- round_dtype(fmaf(scale[s], sum_j B[s, o, j] * t[n, j], y[n, o])), the sum in fp32 with j ascending,
+ *                    in place.  y (N, O) by y_stride elements (even), 4-byte aligned.
+ * Both walk ranks [0, ranks[s] rounded up to 8) only, and a row whose slot lies outside [0, S) -- -1 names the base model -- is
+ * neither read nor written: its bytes stay.  A token's bits depend on its x, its slot and that slot's tables alone.  No atomics.
+ *
+ * KIVI_EINVAL (nothing enqueued) for a dtype that is neither; N < 1, Q < 1 or N not a multiple of Q; K or O not a positive multiple of
+ * 8; R not one of the four; S < 1; a row stride smaller than the row; a null pointer.  KIVI_EALIGN for x, A or B off 16 bytes, an
+ * x_stride that is not a multiple of 8, y off 4 bytes or an odd y_stride, slots, ranks, scale or t off 4 bytes.
+ */
+int kivi_lora_shrink(const void* x, int64_t x_stride, int dtype, int64_t N, int64_t Q, int K, const void* slots, int S, int R,
+                     const void* ranks, const void* A, void* t, kivi_stream_t stream);
+int kivi_lora_expand(const void* t, const void* slots, int S, int R, const void* ranks, const void* scale, const void* B, void* y,
+                     int64_t y_stride, int dtype, int64_t N, int64_t Q, int O, kivi_stream_t stream);
 /* geometry class of a step (-1: bad arguments): the super-block counts of both stores and whether the step flushes a value; the
  * launch plan (one launch / S slices / two launches) is a function of the class and of constants of the call (shape, bits, flags) */
 int64_t kivi_mf_step_key(const kivi_mf_step* step, int B, int nh, int nh_kv, int residual_length, int flags);

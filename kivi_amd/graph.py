@@ -29,7 +29,7 @@ from typing import Callable, List, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, lora
 from .attention import _rotate_half, kivi_attention_decode, rope_cos_sin
 from .cache_mf import SB, KiviLayerCacheMF
 from .generation import _MIN16, bind_suppress, leading_pads, observe_prompts, pack_result, resolve_sampler
@@ -206,6 +206,7 @@ class DecodeGraphs:
         self.model, self.B, self.whole, self.padded, self.sampler = model, B, whole, padded, sampler
         self.sampler_key = None if sampler is None else sampler.key()
         self.stopper, self.stopper_key = stopper, None if stopper is None else stopper.key()
+        self.lora_key = lora.graph_key(model)       # the LoRA binding the captured steps read, or None
         self.tok = zeros(B, 1, dtype=torch.long)
         # a model that is not fp16: x stays in its dtype; q / k / v, the attention output and the mask are fp16 as
         # ever, cos / sin fp32, and pre() crosses with one kivi_qkv_rope_bf16 launch, post() back in the copy that feeds o_proj
@@ -228,9 +229,9 @@ class DecodeGraphs:
             self._capture_layers()
 
     def matches(self, B: int, whole: bool, padded: bool, sampler_key, lead: bool = False, logprobs: Optional[int] = None,
-                stopper_key=None) -> bool:
-        return ((self.B, self.whole, self.padded, self.sampler_key, self.lead is not None, self.logprobs, self.stopper_key) ==
-                (B, whole, padded, sampler_key, bool(lead), logprobs, stopper_key))
+                stopper_key=None, lora_key=None) -> bool:
+        return ((self.B, self.whole, self.padded, self.sampler_key, self.lead is not None, self.logprobs, self.stopper_key,
+                 self.lora_key) == (B, whole, padded, sampler_key, bool(lead), logprobs, stopper_key, lora_key))
 
     def pre(self, i: int) -> None:
         layer = self.model.model.layers[i]
@@ -362,7 +363,7 @@ def prepare_graphs(model, batch: int, device, whole, padded, sampler, logprobs, 
     model._refuse_capture("prepare_graphs")
     key, stop_key = (None if x is None else x.key() for x in (sampler, stopper))
     lead = padded and bool(getattr(model.config, "kivi_decode_lead", False))
-    if model.graphs is None or not model.graphs.matches(batch, whole, padded, key, lead, logprobs, stop_key):
+    if model.graphs is None or not model.graphs.matches(batch, whole, padded, key, lead, logprobs, stop_key, lora.graph_key(model)):
         model.graphs = DecodeGraphs(model, batch, device, whole, padded, sampler, lead, logprobs, stopper)
 
 

@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import admit, graph, loading, scoring, serving, wquant
+from . import admit, graph, loading, lora, scoring, serving, wquant
 from .attention import LlamaAttention_KIVI
 from .beam import beam_search
 from .generation import (PADS_LEFT, DecodeLead, EagerStepper, _PaddedBatch, decode_loop, leading_pads, left_pad,  # noqa: F401
@@ -181,16 +181,23 @@ class LlamaForCausalLM_KIVI(nn.Module):
         self.graphs = None          # kivi_amd.graph.DecodeGraphs of the last graphed decode (prepare_graphs / release_graphs)
         self._stoppers = {}         # (rows, device, pad) -> the StopRows that generate_graphed binds its keyword stops to
         self._quant_experts = None  # whether a sparse block holds 4-bit experts (_refuse_capture)
+        self.lora = None            # kivi_amd.lora.LoraSet of enable_lora() (a plain attribute: not a module, no state_dict entry)
+        self._lora_bindings = {}    # (rows, device) -> the RowBinding the graphed calls rebind (their captured steps hold its buffer)
         if getattr(config, "tie_word_embeddings", False):
             self.lm_head.weight = self.model.embed_tokens.weight
 
     @torch.no_grad()
     def forward(self, input_ids: torch.LongTensor, past_key_values: Optional[List] = None, attention_mask=None,
-                last_token_only: bool = True, padding_mask: Optional[torch.Tensor] = None):
+                last_token_only: bool = True, padding_mask: Optional[torch.Tensor] = None, adapters=None):
         """logits (B, 1 or T, vocab), new past_key_values.  `attention_mask`: the reference's additive (B, 1, 1, kv_len)
         fp16 mask for decode steps (llama_kivi.py:364-372); with it the prompt pass is causal over equal-length prompts.
         `padding_mask`: HF's 2D mask (B, past + T) of 0 / 1 (1 = real token) over the history and `input_ids` -- positions
-        and the additive masks of every pass are derived from it (not together with `attention_mask`)."""
+        and the additive masks of every pass are derived from it (not together with `attention_mask`).
+        `adapters`: the LoRA slot of every row (enable_lora) -- None: the base model, or the binding an outer
+        call has set; one slot for all rows; one int or None per row (None and -1: the base model); ValueError for anything else."""
+        if adapters is not None:
+            with lora.call_binding(self, adapters, input_ids.shape[0]):
+                return self.forward(input_ids, past_key_values, attention_mask, last_token_only, padding_mask)
         if padding_mask is None:
             return self._forward(input_ids, past_key_values, attention_mask, None, last_token_only, False)
         if attention_mask is not None:
@@ -300,7 +307,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     # ------------------------------------------------------------------ continuous batching
     @torch.no_grad()
-    def admit_(self, past_key_values, rows, input_ids: torch.LongTensor, attention_mask: torch.Tensor, offset: int = 0):
+    def admit_(self, past_key_values, rows, input_ids: torch.LongTensor, attention_mask: torch.Tensor, offset: int = 0,
+               adapters=None):
         """New requests take over rows of living caches: -> (prompt logits (n, 1, vocab), fresh tuples of the living caches).
         `past_key_values`: the tuples of forward() / generate() over caches of B rows at kv length L.  `input_ids` (n, L) and HF's 2D
         `attention_mask` (n, L): the n new prompts left-padded to exactly L (left_pad(..., length=L); a prompt of L tokens has no
@@ -314,7 +322,10 @@ class LlamaForCausalLM_KIVI(nn.Module):
         pass; the result lands in tokens [offset, L) of the rows, tokens [0, offset) become zero blocks.  The caller's 2D mask for
         the rows is cat(zeros(offset), attention_mask): the lead is masked like any pad.  `offset`: an int, a multiple of
         rebase_quantum(past_key_values), with L - offset >= residual_length; anything else is a ValueError before the forward pass.
-        The admitted rows are NOT bit-identical to an admission at offset 0 (serving.py has the reasons)."""
+        The admitted rows are NOT bit-identical to an admission at offset 0 (serving.py has the reasons).
+        `adapters`: the LoRA slots of the n admitted prompts, as forward() takes them: the prompt pass runs under a binding of the
+        admitted rows alone (the caller then set_row()s the living batch's binding)."""
+        bound = lora.call_binding(self, adapters, input_ids.shape[0] if input_ids.dim() == 2 else 1)
         caches = self._layer_caches(past_key_values, "admit_")
         L, B = caches[0].kv_seq_len, caches[0].B
         if offset != 0 or not isinstance(offset, int) or isinstance(offset, bool):
@@ -333,7 +344,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
         if not 1 <= n <= B:
             raise ValueError(f"admit_: {n} prompts for living caches of {B} rows")
         rows = admit.check_rows(rows, n, B, caches[0].k_res.device)
-        logits, fresh = self.forward(input_ids, padding_mask=attention_mask)
+        with bound:
+            logits, fresh = self.forward(input_ids, padding_mask=attention_mask)
         for c, t in zip(caches, fresh):
             c.admit_(rows, t.layer, check=False, offset=offset)
         return logits, [c.as_tuple() for c in caches]
@@ -341,7 +353,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
     def generate_continuous(self, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
                             pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False, compact: Optional[int] = None,
                             short_admissions: bool = False, return_logprobs: bool = False, top_logprobs: int = 0, stopping=None,
-                            return_finish: bool = False, allowed_fn=None):
+                            return_finish: bool = False, allowed_fn=None, adapters=None):
         """Continuous batching over a queue of requests (kivi_amd/serving.py: generate_continuous): a batch of `batch_size` rows whose
         finished rows are taken over by the waiting prompts.  -> the generated tokens of every request, in request order.
         `compact`: None, or the fewest leading tokens worth dropping from the living caches between two steps (rebase_).
@@ -352,11 +364,15 @@ class LlamaForCausalLM_KIVI(nn.Module):
         `eos_token_id`: an int or a list; `stopping`: None, one StopParams, or one per request (stop ids, stop sequences, a limit of
         its own); `return_finish`: the result gains a list of (reason, index) per request.
         Per-request constraints (logit_bias, allowed_token_ids, min_new_tokens) come with `sampling`; `allowed_fn`: None, one callable
-        or one per request, asked before every pick for the ids or the bitmask the request may emit next."""
+        or one per request, asked before every pick for the ids or the bitmask the request may emit next.
+        `adapters`: None, one LoRA slot for every request, or one int or None per request: an admission runs
+        its prompt pass under the admitted requests' slots, the batch's binding takes them by set_row -- the captured step is
+        replayed --, and a finished row goes back to -1."""
         if graphed:
             self._refuse_capture("generate_continuous(graphed=True)")
         return serving.generate_continuous(self, prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling, graphed,
-                                           compact, short_admissions, return_logprobs, top_logprobs, stopping, return_finish, allowed_fn)
+                                           compact, short_admissions, return_logprobs, top_logprobs, stopping, return_finish, allowed_fn,
+                                           adapters)
 
     # ------------------------------------------------------------------ rebase (DESIGN.md section 17)
     @classmethod
@@ -387,7 +403,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     def score(self, input_ids: torch.LongTensor, attention_mask: Optional[torch.Tensor] = None,
               past_key_values: Optional[List] = None, first_chunk: Optional[int] = None, chunk_size: Optional[int] = None,
-              return_rank: bool = False, top_logprobs: int = 0):
+              return_rank: bool = False, top_logprobs: int = 0, adapters=None):
         """Teacher-forced log-probabilities of given tokens: (logprobs (B, T - 1) fp32, valid (B, T - 1) bool, past_key_values)
         [, ranks (B, T - 1) int32 with `return_rank`: 0 where the token is the argmax of its distribution, -1 where not valid]
         [, top_ids (B, T - 1, k) int64, top_logprobs (B, T - 1, k) fp32 with `top_logprobs=k` in [1, min(vocab_size, 32)]: the k most
@@ -407,14 +423,17 @@ class LlamaForCausalLM_KIVI(nn.Module):
         token is a pad have valid == False and logprob 0.  Every piece runs the padded path of forward() on the mask's first
         past + (tokens so far) columns (pads are on the left, so every such slice holds them).  Token ids are validated against
         vocab_size, and the mask is looked at, once: one synchronisation per call.  T < 2, a chunk size < 1 or first_chunk outside
-        [1, T] raise ValueError before any device work."""
-        return scoring.score(self, input_ids, attention_mask, past_key_values, first_chunk, chunk_size, return_rank, top_logprobs)
+        [1, T] raise ValueError before any device work.  `adapters`: the LoRA slot of every row, as forward() takes them."""
+        with lora.call_binding(self, adapters, input_ids.shape[0]):
+            return scoring.score(self, input_ids, attention_mask, past_key_values, first_chunk, chunk_size, return_rank, top_logprobs)
 
     def perplexity(self, input_ids: torch.LongTensor, attention_mask: Optional[torch.Tensor] = None,
-                   past_key_values: Optional[List] = None, first_chunk: Optional[int] = None, chunk_size: Optional[int] = None):
+                   past_key_values: Optional[List] = None, first_chunk: Optional[int] = None, chunk_size: Optional[int] = None,
+                   adapters=None):
         """exp(-sum of the valid log-probabilities / number of valid entries) of score() with the same arguments:
         (per row (B,), over all rows ()) float64 on the device, the sums taken in fp64.  A row without a valid entry gives NaN."""
-        return scoring.perplexity(self, input_ids, attention_mask, past_key_values, first_chunk, chunk_size)
+        with lora.call_binding(self, adapters, input_ids.shape[0]):
+            return scoring.perplexity(self, input_ids, attention_mask, past_key_values, first_chunk, chunk_size)
 
     @torch.no_grad()
     def generate(self, input_ids: torch.LongTensor, max_new_tokens: int, past_key_values: Optional[List] = None,
@@ -424,7 +443,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
                  temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, min_p: Optional[float] = None,
                  seed: Optional[int] = None, return_logprobs: bool = False, sampling=None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, top_logprobs: int = 0, stop_token_ids=None,
-                 stop_sequences=None, stopping=None, logit_bias=None, allowed_token_ids=None, min_new_tokens: int = 0):
+                 stop_sequences=None, stopping=None, logit_bias=None, allowed_token_ids=None, min_new_tokens: int = 0,
+                 adapters=None):
         """Greedy decoding (the recipe of the reference's mem_spd_test.py / example.py), or sampling with `do_sample=True`.
         With `past_key_values` (the caches of an earlier turn) `input_ids` is the new turn: it is extended onto the caches in one
         pass (kivi_attention_extend) and decoding continues from there; the caches are advanced in place.  `attention_mask`:
@@ -489,7 +509,24 @@ class LlamaForCausalLM_KIVI(nn.Module):
         of identical rows; with `sampling=` they come from the SamplingParams (a list may constrain every request differently) and
         the three arguments stay neutral.  Not with beams.  `min_new_tokens` does not hold back stop SEQUENCES, which may still end
         a row early, and a caller's RowSampler is used as it is (bind its suppressed ids with `suppress=`).  `return_logprobs` /
-        `top_logprobs` stay under the RAW distribution: a token the constraints forbid can appear among the top ids."""
+        `top_logprobs` stay under the RAW distribution: a token the constraints forbid can appear among the top ids.
+
+        `adapters`: the LoRA slot of every request (enable_lora): None, one slot for all, or one int or None
+        per request (None and -1: the base model).  `num_beams` / `num_return_sequences` expand a request's slot over its rows, as
+        they expand its sampling parameters."""
+        fan = max(num_beams, num_return_sequences, 1) if isinstance(num_beams, int) and isinstance(num_return_sequences, int) else 1
+        with lora.call_binding(self, adapters, input_ids.shape[0], fan):
+            return self._generate(input_ids, max_new_tokens, past_key_values, attention_mask, eos_token_id, pad_token_id, num_beams,
+                                  length_penalty, early_stopping, num_return_sequences, return_scores, do_sample, temperature, top_k,
+                                  top_p, min_p, seed, return_logprobs, sampling, repetition_penalty, presence_penalty,
+                                  frequency_penalty, top_logprobs, stop_token_ids, stop_sequences, stopping, logit_bias,
+                                  allowed_token_ids, min_new_tokens)
+
+    def _generate(self, input_ids, max_new_tokens, past_key_values, attention_mask, eos_token_id, pad_token_id, num_beams, length_penalty,
+                  early_stopping, num_return_sequences, return_scores, do_sample, temperature, top_k, top_p, min_p, seed,
+                  return_logprobs, sampling, repetition_penalty, presence_penalty, frequency_penalty, top_logprobs, stop_token_ids,
+                  stop_sequences, stopping, logit_bias, allowed_token_ids, min_new_tokens):
+        """generate() under the call's LoRA binding, argument for argument."""
         if return_logprobs and num_beams > 1:
             raise ValueError("return_logprobs is for greedy decoding and sampling; beam search (num_beams > 1) returns its "
                              "sequences_scores with return_scores=True")
@@ -543,7 +580,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
 
     def decode_graphed(self, tok: torch.LongTensor, past_key_values: List, position: int, steps: int,
                        attention_mask: Optional[torch.Tensor] = None, sampler=None, sampling=None,
-                       logprobs: Optional[int] = None, stopper=None, sync_every: int = SYNC_EVERY):
+                       logprobs: Optional[int] = None, stopper=None, sync_every: int = SYNC_EVERY, adapters=None):
         """`steps` decode steps from token `tok` (B, 1) at position `position` with the dense part replayed from
         hipGraphs; the caches in `past_key_values` are advanced in place.  Returns the (B, steps) tokens fed to the model
         (tok first); the token following them is left in the graph's token buffer (`self.graphs.tok`).
@@ -560,9 +597,14 @@ class LlamaForCausalLM_KIVI(nn.Module):
         runs it on the token it produces (one kivi_stop_rows launch after the draw): finished rows feed its pad.  Before step s, for
         every s that is a multiple of `sync_every`, the host reads the stopper's `n_live` -- the only synchronisation -- and leaves
         when it is 0, so fewer than `steps` columns may come back and at most sync_every - 1 steps run after the last row has
-        finished.  `sync_every=None`: never read, all `steps` run."""
-        return graph.decode_graphed(self, tok, past_key_values, position, steps, attention_mask, sampler, sampling, logprobs, stopper,
-                                    sync_every)
+        finished.  `sync_every=None`: never read, all `steps` run.
+        `adapters`: the LoRA slots of the B rows -- a list as forward() takes it, which binds the model's own
+        binding for B rows in place, or a kivi_amd.lora.RowBinding of B rows, used as it is.  The captured step holds the two launches
+        per target linear and reads the binding's buffer: its key() joins what the graphs are matched by, and another request mix
+        (bind, set_row) replays the graphs that exist."""
+        with lora.call_binding(self, adapters, tok.shape[0], kept=True):
+            return graph.decode_graphed(self, tok, past_key_values, position, steps, attention_mask, sampler, sampling, logprobs,
+                                        stopper, sync_every)
 
     def generate_graphed(self, input_ids: torch.LongTensor, max_new_tokens: int,
                          attention_mask: Optional[torch.Tensor] = None, num_beams: int = 1, do_sample: bool = False,
@@ -571,7 +613,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
                          presence_penalty: float = 0.0, frequency_penalty: float = 0.0, return_logprobs: bool = False,
                          top_logprobs: int = 0, eos_token_id=None, pad_token_id: Optional[int] = None, stop_token_ids=None,
                          stop_sequences=None, stopping=None, sync_every: Optional[int] = SYNC_EVERY, logit_bias=None,
-                         allowed_token_ids=None, min_new_tokens: int = 0):
+                         allowed_token_ids=None, min_new_tokens: int = 0, adapters=None):
         """generate() with the dense part of every decode step replayed from hipGraphs (kivi_amd.graph.DecodeGraphs).
         `attention_mask`: HF's 2D (B, T) mask of left-padded prompts (1 = real token).  Greedy, or sampling with `do_sample=True`
         and the parameters of generate() (the draw inside the graph; the same tokens as generate() with the same seed).  Beams
@@ -590,11 +632,36 @@ class LlamaForCausalLM_KIVI(nn.Module):
         keyword forms the model keeps one tracker per (B, device, pad) and rebinds its rows, so another call with other stops
         replays the graphs that exist; a StopRows passed as `stopping=` is used as it is and keys the graphs by its own buffers.
         `logit_bias` / `allowed_token_ids` / `min_new_tokens`: as in generate(); the constrained draw is
-        inside the captured step, and so is the advance towards the end of the suppression."""
-        return graph.generate_graphed(self, input_ids, max_new_tokens, attention_mask, num_beams, do_sample, temperature, top_k, top_p,
-                                      min_p, seed, sampling, repetition_penalty, presence_penalty, frequency_penalty, return_logprobs,
-                                      top_logprobs, eos_token_id, pad_token_id, stop_token_ids, stop_sequences, stopping, sync_every,
-                                      logit_bias, allowed_token_ids, min_new_tokens)
+        inside the captured step, and so is the advance towards the end of the suppression.
+        `adapters`: as in generate(); the prompt pass and the captured steps run under the model's own binding
+        for B rows, rebound in place, so another request mix replays the graphs that exist."""
+        with lora.call_binding(self, adapters, input_ids.shape[0], kept=True):
+            return graph.generate_graphed(self, input_ids, max_new_tokens, attention_mask, num_beams, do_sample, temperature, top_k,
+                                          top_p, min_p, seed, sampling, repetition_penalty, presence_penalty, frequency_penalty,
+                                          return_logprobs, top_logprobs, eos_token_id, pad_token_id, stop_token_ids, stop_sequences,
+                                          stopping, sync_every, logit_bias, allowed_token_ids, min_new_tokens)
+
+    # ------------------------------------------------------------------ per-request LoRA adapters (DESIGN.md section 34)
+    def enable_lora(self, max_adapters: int, max_rank: int, target_modules=("q_proj", "v_proj")) -> "lora.LoraSet":
+        """Attach adapter tables of `max_adapters` slots and table rank `max_rank` (8, 16, 32 or 64) to the linears named
+        `target_modules`, a subset of q_proj, k_proj, v_proj, o_proj, gate_proj, up_proj, down_proj -> the kivi_amd.lora.LoraSet
+        (load / unload adapters there; `adapters=` of the entry points binds rows to its slots).  On Mixtral and Qwen3-MoE the
+        attention projections and the dense MLP layers are served; a sparse block is never a target.  Forward hooks on the target
+        linears do the work: the module tree, the parameter and buffer names, state_dict() and what save_quantized writes stay.
+        Captured graphs are released."""
+        if self.lora is not None:
+            self.disable_lora()
+        self.lora = lora.LoraSet(self, max_adapters, max_rank, target_modules).attach()
+        self.release_graphs()
+        return self.lora
+
+    def disable_lora(self) -> None:
+        """Undo enable_lora: the hooks and the tables go, captured graphs are released."""
+        if self.lora is not None:
+            self.lora.detach()
+        self.lora = None
+        self._lora_bindings.clear()
+        self.release_graphs()
 
     @classmethod
     def from_pretrained(cls, path: str, device="cuda", dtype=torch.float16, **kivi):

@@ -53,10 +53,12 @@ The policy is fixed (tests restate it):
 """
 from __future__ import annotations
 
+import contextlib
 from typing import List, Optional
 
 import torch
 
+from . import lora
 from .generation import decode_key_row, left_pad, padding_key_row
 from .sampling import RowSampler, SamplingParams
 from .scoring import check_top_logprobs, picked_scores
@@ -162,7 +164,7 @@ def admission_offset(L: int, longest_prompt: int, R: int, quantum: int) -> int:
 def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_token_id: Optional[int] = None,
                         pad_token_id: Optional[int] = 0, sampling=None, graphed: bool = False,
                         compact: Optional[int] = None, short_admissions: bool = False, return_logprobs: bool = False,
-                        top_logprobs: int = 0, stopping=None, return_finish: bool = False, allowed_fn=None):
+                        top_logprobs: int = 0, stopping=None, return_finish: bool = False, allowed_fn=None, adapters=None):
     """`prompts`: a list of token id sequences, possibly more than `batch_size`; `max_new_tokens`: an int or one per request;
     `sampling`: None (greedy), one SamplingParams, or one per request.  -> the generated tokens of every request as 1-D int64
     tensors, in request order, ending with `eos_token_id` where it was produced.  The policy: the module docstring.
@@ -184,7 +186,10 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
     Constraints come with `sampling`: a request's logit_bias, allowed_token_ids and min_new_tokens, which
     holds back the request's eos and stop token ids (not its stop sequences).  `allowed_fn`: None, one callable, or one callable or
     None per request -- before every pick it is called with the list of the request's generated ids and answers token ids, an int32
-    bitmask (RowSampler.set_allowed) or None (the request's own allowed_token_ids, or no mask): the mask of that one pick."""
+    bitmask (RowSampler.set_allowed) or None (the request's own allowed_token_ids, or no mask): the mask of that one pick.
+    `adapters`: None, one LoRA slot for every request, or one int or None per request.  The batch owns one
+    RowBinding: the first prompt pass and every step run under it; an admission runs its prompt pass under a binding of the admitted
+    rows alone (admit_(adapters=)) and then set_row()s the batch's, so the captured step is replayed; a finished row goes back to -1."""
     prompts, limits, params = check_arguments(prompts, max_new_tokens, batch_size, eos_token_id, pad_token_id, sampling,
                                               model.config.vocab_size, compact, short_admissions, allowed_fn)
     stops = check_stopping(limits, eos_token_id, pad_token_id, stopping, model.config.vocab_size)
@@ -198,6 +203,21 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
     B = min(batch_size, N)
     L = max(p.numel() for p in prompts)
 
+    lset = getattr(model, "lora", None)
+    slot_of = lora.resolve_adapters(adapters, N, None if lset is None else lset.S)
+    if isinstance(slot_of, lora.RowBinding):
+        raise ValueError("generate_continuous(adapters=) takes slots per request, not a RowBinding: the batch owns its binding")
+    binding = None if slot_of is None else lora.RowBinding(B, device, slot_of[:B])
+    bound = contextlib.nullcontext() if binding is None else lset.bound(binding)
+    with bound:
+        return _continuous(model, prompts, params, stops, finish, fns, k, pad, use_lead, N, device, B, L,
+                           graphed, compact, short_admissions, return_logprobs, return_finish, slot_of, binding)
+
+
+def _continuous(model, prompts, params, stops, finish, fns, k, pad, use_lead, N, device, B, L, graphed, compact,
+                short_admissions, return_logprobs, return_finish, slot_of, binding):
+    """The scheduler of generate_continuous behind its checks; `binding`: the batch's LoRA binding (active for the whole call) or
+    None, `slot_of`: the slot of every request."""
     ids, mask = left_pad(prompts[:B], pad, device, length=L)
     logits, pasts = model.forward(ids, padding_mask=mask)
     con = params is not None and (fns is not None or any(p.constrained for p in params))
@@ -245,6 +265,8 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
                 dst[r].append(v[i])
         if finish[r].push(t) != LIVE:              # the rule of kivi_amd/stopping.py on the request's own tokens
             owner[b] = None
+            if binding is not None and binding.host[b] != -1:
+                binding.set_row(b, -1)                 # an idle row runs the base model
 
     while True:
         toks = tok.view(-1).tolist()                                           # the one synchronisation of a step
@@ -270,7 +292,8 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
                 off = admission_offset(L, max(prompts[r].numel() for r in reqs), pasts[0].layer.cfg.residual_length,
                                        model.rebase_quantum(pasts))
             new_ids, new_mask = left_pad([prompts[r] for r in reqs], pad, device, length=L - off)
-            lg, pasts = model.admit_(pasts, rows, new_ids, new_mask, offset=off)
+            own = {} if binding is None else dict(adapters=[slot_of[r] for r in reqs])     # the admitted rows' slots alone
+            lg, pasts = model.admit_(pasts, rows, new_ids, new_mask, offset=off, **own)
             if off:
                 mask2d[rows, :off] = 0                                             # the zeroed lead is masked like any pad
             mask2d[rows, off:L] = new_mask
@@ -287,6 +310,8 @@ def generate_continuous(model, prompts, max_new_tokens, batch_size: int, eos_tok
             for i, (b, r, t) in enumerate(zip(rows, reqs, firsts)):
                 owner[b] = r
                 lead[b] = L - prompts[r].numel()
+                if binding is not None:
+                    binding.set_row(b, slot_of[r])
                 if sampler is not None:
                     sampler.set_row(b, params[r], draw_index=1, prompt=prompts[r], generated=[t],
                                     suppress=stops[r].stop_token_ids if con else None)

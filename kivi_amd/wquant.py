@@ -18,6 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .lora import active_binding
 
 LAYOUT = "WT4"                  # the tag save_quantized writes and from_pretrained recognises
 GROUPS = (64, 128)
@@ -288,6 +289,16 @@ class QuantMLP(nn.Module):
         if not self.down_proj.uses_kernel(x2.shape[0]):
             return self.down_proj(F.silu(self.gate_proj(x)) * self.up_proj(x))
         a = gate_up(x2, self.gate_proj.triple, self.up_proj.triple)
+        bound = active_binding(self.gate_proj, self.up_proj)
+        if bound is not None and x.dim() == 3:
+            # A LoRA adapter on gate or up needs the two linears apart: the three-linear route, each linear
+            # kivi_w4_linear and its hook.  The fused launch rounds silu(g) * u once, that route three times, so the rows of the base
+            # model (slot -1) keep the fused value: their bytes stay those of a pass without adapters.
+            adapted = (F.silu(self.gate_proj(x)) * self.up_proj(x)).view_as(a)
+            rows = (bound.for_rows(x.shape[0]).slots >= 0).repeat_interleave(x.shape[1])
+            a = torch.where(rows[:, None], adapted, a)
+        if active_binding(self.down_proj) is not None and x.dim() == 3:
+            return self.down_proj(a.view(*x.shape[:-1], -1))        # the same kivi_w4_linear launch, then the module's hook
         return linear(a, *self.down_proj.triple).view(x.shape)
 
 
