@@ -1120,6 +1120,33 @@ int kivi_w4_gate_up(const void* x, int64_t x_stride, int dtype, int N, int I, in
                     const void* gate_scales, const void* gate_mins, const void* up_qweight, const void* up_scales,
                     const void* up_mins, void* y, int64_t y_stride, kivi_stream_t stream);
 /*
+ * FP8 weights under 16-bit activations, W8A16.  The two buffers of a weight (O, K) are those of a fine-grained
+ * FP8 checkpoint, as they are on disk: `weight` (O, K) row-major, one OCP e4m3fn byte per element, no NaN byte (0x7F, 0xFF);
+ * `scale_inv` (ceil(O / 128), K / 128) fp32 row-major, the factor one MULTIPLIES by.  The represented weight is the real number
+ * W~[o, k] = e4m3(weight[o, k]) * scale_inv[o / 128, k / 128].  `dtype`: 16 (fp16) or KIVI_LOGITS_BF16 (bf16).
+ *
+ * kivi_w8_dequant   out[o, k] = round_to_dtype(fp32(e4m3) * scale), the product rounded to fp32 first; row stride out_stride
+ * kivi_w8_linear    y[n, o] = sum_k x[n, k] * W~[o, k] (+ bias[o]): x is not quantised; accumulated in fp32, rounded once to the
+ *                   dtype.  x (N, K) by x_stride, y (N, O) by y_stride, bias (O) in the dtype or null.  Any N >= 1: tokens go
+ *                   through in chunks of 64 (kivi_w8_gate_up: of 32), one pass over the stripe's bytes per chunk.
+ * kivi_w8_gate_up   y[n, i] = silu(g) * u with g, u the two linears of the gate and the up matrix (I, K) in fp32, rounded once
+ * Launches only: a stream capture may hold them.  The order in which a token's sums are taken depends on K only, not on N, on the
+ * token's position or on the other tokens; no atomics.
+ *
+ * KIVI_EINVAL (nothing enqueued) for a dtype that is neither; O not a positive multiple of 16; K not a positive multiple of 128;
+ * N < 1 or N * O >= 2^31; a row stride smaller than the row; a null pointer (bias may be null).  KIVI_EALIGN for x, out or weight
+ * off 16 bytes, scale_inv off 4, y off 8, a stride of x or out that is not a multiple of 8 elements, of y not of 4.
+ * kivi_w8_bytes: the bytes of the two buffers together, O * K + 4 * ceil(O / 128) * (K / 128) (KIVI_EINVAL for such a shape).
+ */
+int64_t kivi_w8_bytes(int O, int K);
+int kivi_w8_dequant(const void* weight, const void* scale_inv, int O, int K, int dtype, void* out, int64_t out_stride,
+                    kivi_stream_t stream);
+int kivi_w8_linear(const void* x, int64_t x_stride, int dtype, int N, int O, int K, const void* weight, const void* scale_inv,
+                   const void* bias, void* y, int64_t y_stride, kivi_stream_t stream);
+int kivi_w8_gate_up(const void* x, int64_t x_stride, int dtype, int N, int I, int K, const void* gate_weight,
+                    const void* gate_scale_inv, const void* up_weight, const void* up_scale_inv, void* y, int64_t y_stride,
+                    kivi_stream_t stream);
+/*
  * Per-request LoRA adapters: the batched low-rank side path of a linear layer, two launches, nothing read
  * back, so a stream capture may hold them.  S slots of table rank R in {8, 16, 32, 64}; A (S, R, K) and B (S, O, R) contiguous in
  * the dtype -- 16 (fp16) or KIVI_LOGITS_BF16 (bf16) --, an adapter of rank r < R in rows / columns [0, r) of its slot and zeros

@@ -226,6 +226,10 @@ SIGNATURES = {
     "kivi_w4_dequant": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "kivi_w4_linear": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "kivi_w4_gate_up": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "kivi_w8_bytes": (_i64, [_i32, _i32]),
+    "kivi_w8_dequant": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "kivi_w8_linear": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "kivi_w8_gate_up": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "kivi_lora_shrink": (_i32, [_vp, _i64, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "kivi_lora_expand": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _i32, _vp]),
     "kivi_mf_step_key": (_i64, [ctypes.POINTER(MfStep), _i32, _i32, _i32, _i32, _i32]),

@@ -185,11 +185,14 @@ class LlamaAttention_KIVI(nn.Module):
         if self.head_dim * self.num_heads != self.hidden_size and getattr(config, "head_dim", None) is None:
             raise ValueError("hidden_size must be divisible by num_heads")
         bias = getattr(config, "attention_bias", False)
-        # nn.Linear, or with config.kivi_weight_bits == 4 the 4-bit QuantLinear
-        self.q_proj = make_linear(config, self.hidden_size, self.num_heads * self.head_dim, bias=bias)
-        self.k_proj = make_linear(config, self.hidden_size, self.num_key_value_heads * self.head_dim, bias=bias)
-        self.v_proj = make_linear(config, self.hidden_size, self.num_key_value_heads * self.head_dim, bias=bias)
-        self.o_proj = make_linear(config, self.num_heads * self.head_dim, self.hidden_size, bias=bias)
+        # nn.Linear, with config.kivi_weight_bits == 4 the 4-bit QuantLinear, with config.kivi_fp8_weights the
+        # Fp8Linear (section 35), which a checkpoint's `modules_to_not_convert` may keep dense by the module's dotted name
+        self.q_proj = make_linear(config, self.hidden_size, self.num_heads * self.head_dim, bias=bias, name=self._proj_name("q_proj"))
+        self.k_proj = make_linear(config, self.hidden_size, self.num_key_value_heads * self.head_dim, bias=bias,
+                                  name=self._proj_name("k_proj"))
+        self.v_proj = make_linear(config, self.hidden_size, self.num_key_value_heads * self.head_dim, bias=bias,
+                                  name=self._proj_name("v_proj"))
+        self.o_proj = make_linear(config, self.num_heads * self.head_dim, self.hidden_size, bias=bias, name=self._proj_name("o_proj"))
         self.register_buffer("inv_freq", _rope_inv_freq(config, self.head_dim, self.rope_theta), persistent=False)
         # config.kivi_qk_kernel (off by default): q / k are prepared by one kivi_qk_rope launch, and a query-group
         # ratio the matrix-pipe layout does not serve runs on it padded: `cache_heads` query heads, nh_kv * the padded ratio
@@ -198,6 +201,10 @@ class LlamaAttention_KIVI(nn.Module):
         if self.qk_kernel:
             self.cache_heads = _padded_heads(self.kivi, self.head_dim, self.num_heads, self.num_key_value_heads) or self.num_heads
         self.q_norm = self.k_norm = None            # the per-head RMSNorm of q and k before RoPE (QwenAttention_KIVI)
+
+    def _proj_name(self, leaf: str) -> Optional[str]:
+        """The projection's dotted name in the model (a checkpoint's names), or None for a block built outside a model."""
+        return None if self.layer_idx is None else f"model.layers.{self.layer_idx}.self_attn.{leaf}"
 
     def _rope(self, q, k, position_ids):
         cos, sin = (x[:, None] for x in rope_cos_sin(self.inv_freq, position_ids, q.dtype))   # (B, 1, T, D)
@@ -417,7 +424,7 @@ class QwenAttention_KIVI(LlamaAttention_KIVI):
             raise ValueError("use_sliding_window=True: the quantised KV history has no sliding window; load the model with "
                              "use_sliding_window=false (full attention) or do not use this cache")
         super().__init__(config, layer_idx)
-        self.o_proj = make_linear(config, self.num_heads * self.head_dim, self.hidden_size, bias=False)
+        self.o_proj = make_linear(config, self.num_heads * self.head_dim, self.hidden_size, bias=False, name=self._proj_name("o_proj"))
         if getattr(config, "kivi_head_norm", False):
             eps = getattr(config, "rms_norm_eps", 1e-6)
             self.q_norm, self.k_norm = HeadRMSNorm(self.head_dim, eps), HeadRMSNorm(self.head_dim, eps)

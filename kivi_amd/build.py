@@ -20,7 +20,7 @@ SOURCES = ["kivi_abi.hip", "kivi_pack.hip", "kivi_gemv_k.hip", "kivi_gemv_v.hip"
            "kivi_softmax.hip", "kivi_layer.hip", "kivi_gqa.hip", "kivi_mf.hip", "kivi_extend.hip",
            "kivi_reorder.hip", "kivi_sample.hip", "kivi_rowcopy.hip", "kivi_score.hip", "kivi_shift.hip",
            "kivi_admit_shift.hip", "kivi_prefill.hip", "kivi_stop.hip", "kivi_qkrope.hip", "kivi_moe.hip",
-           "kivi_w4.hip", "kivi_lora.hip"]
+           "kivi_w4.hip", "kivi_lora.hip", "kivi_w8.hip"]
 import glob
 
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(os.path.dirname(HERE), "include", "kivi_hip.h")]

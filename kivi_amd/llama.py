@@ -42,7 +42,7 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
                 qk_kernel: bool = False, moe_kernel: bool = True, moe_kernel_max_tokens: Optional[int] = None,
                 weight_bits: Optional[int] = None, weight_group: int = 128,
                 weight_kernel_max_tokens: Optional[int] = None, expert_bits: Optional[int] = None,
-                expert_group: int = 128) -> SimpleNamespace:
+                expert_group: int = 128, fp8_weights: bool = False, fp8_skip_modules=None) -> SimpleNamespace:
     """HF config.json fields (+ the four KIVI fields) -> the namespace the modules read.  `prefill_kernel`: the prompt pass's
     attention runs kivi_prefill_attention, and every attention class serves left-padded prompts.
     `decode_lead`: the decode steps of a padded batch hand the kernels every row's leading pads, and the row kernels skip the packed
@@ -58,7 +58,13 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
     `expert_bits`: None, or 4 for 4-bit experts in the sparse blocks, in groups of `expert_group` (64 or 128) along the reduction
     axis (kivi_amd.moe.QuantExperts): the block dequantises each hit expert and runs the loop; it has no
     capturable form, so the graphed decode paths raise on such a model.  Independent of `weight_bits`; a config without experts
-    refuses it."""
+    refuses it.
+    `fp8_weights`: the attention projections and dense MLPs hold FP8 weights in the form of transformers' fine-grained FP8
+    checkpoints -- e4m3fn bytes and one fp32 `weight_scale_inv` per [128, 128] block -- under 16-bit activations (kivi_amd/wfp8.py,
+    DESIGN.md section 35); `weight_kernel_max_tokens` bounds its kernel as it does the 4-bit one (None:
+    kivi_amd.wfp8.KERNEL_MAX_TOKENS).  `fp8_skip_modules`: a checkpoint's `modules_to_not_convert`, patterns of module names that
+    stay dense.  Embeddings, lm_head and the experts of a sparse block keep the model dtype.  Together with `weight_bits=4` it
+    raises: the two are formats of the same weights; together with `expert_bits=4` it raises as well."""
     if weight_bits not in (None, 4):
         raise ValueError(f"weight_bits has to be None or 4, got {weight_bits!r}")
     if weight_bits is not None and weight_group not in wquant.GROUPS:
@@ -67,7 +73,14 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
         raise ValueError(f"expert_bits has to be None or 4, got {expert_bits!r}")
     if expert_bits is not None and expert_group not in wquant.GROUPS:
         raise ValueError(f"expert_group has to be one of {wquant.GROUPS}, got {expert_group!r}")
+    if fp8_weights and weight_bits is not None:
+        raise ValueError("fp8_weights and weight_bits=4 are two formats of the same weights: choose one")
+    if fp8_weights and expert_bits is not None:
+        raise ValueError("fp8_weights together with expert_bits=4 is not served: save_quantized has no format that holds both")
     extra = {}
+    if fp8_weights:                         # (absent otherwise: the default namespace is what it was)
+        extra = dict(kivi_fp8_weights=True, kivi_fp8_skip=None if fp8_skip_modules is None else list(fp8_skip_modules),
+                     kivi_weight_kernel_max_tokens=weight_kernel_max_tokens, kivi_hf_config=dict(d))
     if weight_bits is not None:             # (absent otherwise: the default namespace is what it was)
         extra = dict(kivi_weight_bits=weight_bits, kivi_weight_group=weight_group,
                      kivi_weight_kernel_max_tokens=weight_kernel_max_tokens, kivi_hf_config=dict(d))
@@ -132,7 +145,8 @@ def layer_is_sparse(cfg, layer_idx: int) -> bool:
 def make_mlp(cfg, layer_idx: int) -> nn.Module:
     """The feed-forward block of a layer: the dense SwiGLU MLP, or the sparse block of kivi_amd/moe.py."""
     if not layer_is_sparse(cfg, layer_idx):
-        return wquant.make_dense_mlp(cfg, MLP)  # MLP(cfg), or with cfg.kivi_weight_bits == 4 the 4-bit QuantMLP (section 30)
+        # MLP(cfg), with cfg.kivi_weight_bits == 4 the 4-bit QuantMLP (section 30), with cfg.kivi_fp8_weights the Fp8MLP (section 35)
+        return wquant.make_dense_mlp(cfg, MLP, name=f"model.layers.{layer_idx}.mlp")
     return SparseMoeBlock(cfg.hidden_size, cfg.moe_intermediate_size, cfg.num_experts, cfg.num_experts_per_tok,
                           norm_topk=cfg.norm_topk_prob, round_weights=getattr(cfg, "kivi_moe_round_weights", False),
                           kernel=getattr(cfg, "kivi_moe_kernel", True),
@@ -667,7 +681,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
     def from_pretrained(cls, path: str, device="cuda", dtype=torch.float16, **kivi):
         """`path`: a local HF checkpoint directory (config.json + *.safetensors).  `kivi`: k_bits, v_bits, group_size,
         residual_length, max_cache_len, prefill_kernel, decode_lead, qk_kernel (default: the class's, on for the Qwen classes),
-        moe_kernel, moe_kernel_max_tokens, weight_bits, weight_group, weight_kernel_max_tokens, expert_bits, expert_group.
+        moe_kernel, moe_kernel_max_tokens, weight_bits, weight_group, weight_kernel_max_tokens, expert_bits, expert_group,
+        fp8_weights, fp8_skip_modules (an FP8 checkpoint's `modules_to_not_convert` is added to a list given here).
         Called on LlamaForCausalLM_KIVI, a config.json whose `model_type` is qwen2 / qwen3 / mixtral / qwen3_moe builds that
         family's class.  The class, the config and the empty model are made here; reading config.json and filling the model are
         kivi_amd/loading.py: the files are read one at a time, and a checkpoint that leaves any tensor of
@@ -676,7 +691,13 @@ class LlamaForCausalLM_KIVI(nn.Module):
         projections and dense MLPs are built 4-bit up front and every `*_proj.weight` is quantised on the device as its file is
         read; a directory written by save_quantized is recognised by its layout tag.  The experts of a sparse checkpoint are
         taken under HF's per-expert names or the fused ones of transformers 5: each expert is copied into the stacked parameter in
-        turn."""
+        turn.
+        A fine-grained FP8 checkpoint (config.json: `quantization_config.quant_method == "fp8"`, e4m3, weight_block_size [128, 128]
+        or null, float scales) is served as it lies on disk: its `weight` bytes and `weight_scale_inv` go into
+        Fp8Linear modules unchanged, `modules_to_not_convert` stay dense, and an FP8 weight whose module the kernels do not serve is
+        dequantised in torch.  `activation_scheme: "dynamic"` is accepted and NOT applied: activations stay 16-bit, the more exact
+        arithmetic.  "static", `input_scale` / `activation_scale` tensors, ue8m0 scales, another block size and FP8 experts raise.
+        With `fp8_weights=True` a 16-bit checkpoint is quantised to that format on the device as its files are read."""
         d = loading.read_config(path, kivi)     # (a directory of save_quantized: its tags become keywords of make_config)
         if cls is LlamaForCausalLM_KIVI:
             cls = {"qwen2": Qwen2ForCausalLM_KIVI, "qwen3": Qwen3ForCausalLM_KIVI, "mixtral": MixtralForCausalLM_KIVI,
@@ -698,7 +719,10 @@ class LlamaForCausalLM_KIVI(nn.Module):
         """Write a model built with `weight_bits=4` or `expert_bits=4` to the directory `path`: config.json -- the fields it was
         loaded with plus kivi_weight_bits / kivi_weight_group, kivi_expert_bits / kivi_expert_group (those that are set) and the
         layout tag kivi_weight_layout -- and model.safetensors with the 4-bit modules' `qweight` / `scales` / `mins` under their
-        module names.  from_pretrained reads it back without quantising anything."""
+        module names.  A model built with `fp8_weights` is written in transformers' format instead: `weight` as float8_e4m3fn and
+        `weight_scale_inv` as float32 under the module names, and a `quantization_config` block (fp8, e4m3, dynamic, [128, 128],
+        float scales, `modules_to_not_convert`: the linears that stayed dense) in place of the tags.  from_pretrained reads either
+        back without quantising anything."""
         loading.save_quantized(self, path)
 
 

@@ -16,7 +16,7 @@ import re
 import torch
 import torch.nn as nn
 
-from . import wquant
+from . import wfp8, wquant
 from .moe import QuantExperts, SparseMoeBlock
 
 _TAGS = ("kivi_weight_layout", "kivi_weight_bits", "kivi_weight_group", "kivi_expert_bits", "kivi_expert_group")
@@ -24,12 +24,40 @@ _EXPERT_NAME = re.compile(r"^(.*\.)(?:block_sparse_moe|mlp)\.experts\.(\d+)\.(w1
 _EXPERT_PART = {"w1": "gate", "gate_proj": "gate", "w3": "up", "up_proj": "up", "w2": "down", "down_proj": "down"}
 _STACK_PARTS = {"gate_up_proj": ("gate", "up"), "down_proj": ("down",)}
 _TRIPLE = ("qweight", "scales", "mins")
+_FP8_PAIR = ("weight", "weight_scale_inv")
+_FP8_ACTIVATION = ("input_scale", "activation_scale")      # tensors of a static activation scheme: never served
+
+
+def _fp8_config(path: str, q: dict, kivi: dict) -> None:
+    """A checkpoint's `quantization_config` block with quant_method "fp8" (transformers' FineGrainedFP8Config) -> fp8_weights and the
+    skip list among the keywords of make_config.  What the kernels do not serve is refused by name."""
+    fmt = q.get("fmt", "e4m3")
+    if fmt != "e4m3":
+        raise ValueError(f"{path}: quantization_config.fmt {fmt!r}: only e4m3 FP8 weights are served")
+    if q.get("scale_fmt") not in (None, "float"):
+        raise ValueError(f"{path}: quantization_config.scale_fmt {q['scale_fmt']!r}: only float (fp32) scales are served, not ue8m0")
+    block = q.get("weight_block_size")
+    if block is not None and list(block) != [wfp8.BLOCK, wfp8.BLOCK]:
+        raise ValueError(f"{path}: quantization_config.weight_block_size {block!r}: only [128, 128] blocks and per-tensor scales "
+                         f"(null) are served")
+    scheme = q.get("activation_scheme", "dynamic")
+    if scheme != "dynamic":     # "dynamic" is accepted and not applied: activations stay 16-bit (DESIGN.md section 35)
+        raise ValueError(f"{path}: quantization_config.activation_scheme {scheme!r}: static activation scales are not served")
+    kivi["fp8_weights"] = True
+    if q.get("modules_to_not_convert"):     # added to a list the caller gave: a module either names stays dense
+        kivi["fp8_skip_modules"] = list(kivi.get("fp8_skip_modules") or []) + list(q["modules_to_not_convert"])
 
 
 def read_config(path: str, kivi: dict) -> dict:
     """config.json of the directory `path` without the tags of save_quantized.  Where the layout tag is there, the bits and groups
-    it was written with go into `kivi` (the keywords of make_config); another layout than this version's raises."""
+    it was written with go into `kivi` (the keywords of make_config); another layout than this version's raises.  A
+    `quantization_config` block of quant_method "fp8"  is validated, becomes fp8_weights=True plus the skip list
+    in `kivi`, and is stripped as well."""
     d = json.load(open(os.path.join(path, "config.json")))
+    q = d.get("quantization_config")
+    if isinstance(q, dict) and q.get("quant_method") == "fp8":
+        _fp8_config(path, q, kivi)
+        d = {k: v for k, v in d.items() if k != "quantization_config"}
     if "kivi_weight_layout" in d:                           # a checkpoint of save_quantized: loaded as it is, nothing re-quantised
         if d["kivi_weight_layout"] != wquant.LAYOUT:
             raise ValueError(f"{path}: weight layout {d['kivi_weight_layout']!r} is not one this version reads ({wquant.LAYOUT!r})")
@@ -48,18 +76,27 @@ class CheckpointLoader:
       a fused expert stack  quantised expert by expert where the block holds a QuantExperts (a dense block takes it as any tensor);
       a QuantLinear weight  cast to `dtype` on the module's device and packed into its buffers (section 30), as
                             QuantLinear.from_linear on the loaded model would;
+      an Fp8Linear's pair   (section 35) a float8_e4m3fn `weight` is checked for NaN bytes and copied as bytes, a `weight_scale_inv`
+                            copied as bits (a per-tensor scalar expanded), each filling its own key, in any order and from any
+                            file; a 16-bit `weight` is quantised on the module's device and fills both;
+      an FP8 pair of a dense linear   (a shape the kernels do not serve, a module of `modules_to_not_convert`) the one case that
+                            holds a tensor across files: the first of `weight` / `weight_scale_inv` waits in `pending` for the
+                            other, then the pair is dequantised in torch into the parameter; until then its key stays owed;
       any other             `block_sparse_moe.` spelled `mlp.`, then model.load_state_dict(strict=False) over the file's remainder:
                             a shape that does not fit raises there, a name nothing takes ends in `unexpected`, a tensor that comes
                             again is written again.
     The ledger `owed`: state_dict key -> the slots nothing has filled yet.  A key is one slot; the key of an expert stack -- the
     dense parameter, or each of a 4-bit stack's three buffers -- is one slot per (expert, part), part in gate / up / down, since
-    only a set can tell a repeated piece from a missing one.  The tied lm_head.weight owes nothing.  Nothing here keeps a tensor
-    of a file: it dies with the caller's dict."""
+    only a set can tell a repeated piece from a missing one.  The tied lm_head.weight owes nothing.  But for that
+    waiting half of an FP8 pair nothing here keeps a tensor of a file: it dies with the caller's dict."""
 
     def __init__(self, model: nn.Module, dtype=torch.float16):
         self.model, self.dtype = model, dtype
         self.unexpected = []
         self.linears = {n: m for n, m in model.named_modules() if isinstance(m, wquant.QuantLinear)}
+        self.fp8 = {n: m for n, m in model.named_modules() if isinstance(m, wfp8.Fp8Linear)}
+        self.dense = {n: m for n, m in model.named_modules() if isinstance(m, nn.Linear)}
+        self.pending = {}           # dense linear -> {"weight" / "weight_scale_inv": tensor}: an FP8 pair waiting for its other half
         blocks = {f"{n}.experts": m for n, m in model.named_modules() if isinstance(m, SparseMoeBlock)}
         self.experts = {owner: m.experts for owner, m in blocks.items()}
         tied = getattr(model.config, "tie_word_embeddings", False)
@@ -83,6 +120,7 @@ class CheckpointLoader:
     def take(self, tensors: dict) -> None:
         rest = {}
         for name, t in tensors.items():
+            self._refuse_unserved_fp8(name, t)
             m = _EXPERT_NAME.match(name)
             if m is not None:
                 owner = f"{m.group(1)}mlp.experts"
@@ -93,6 +131,8 @@ class CheckpointLoader:
                 continue
             new = name.replace(".block_sparse_moe.", ".mlp.")
             owner, _, leaf = new.rpartition(".")
+            if self._take_fp8(new, owner, leaf, t):
+                continue
             if leaf in _STACK_PARTS and isinstance(self.experts.get(owner), QuantExperts):
                 self._take_fused(name, owner, leaf, t)
             elif leaf == "weight" and owner in self.linears:
@@ -105,6 +145,50 @@ class CheckpointLoader:
             _, unexpected = self.model.load_state_dict(rest, strict=False)
             self.unexpected += unexpected
             self._fill(rest.keys() - set(unexpected))
+
+    @staticmethod
+    def _refuse_unserved_fp8(name: str, t: torch.Tensor) -> None:
+        """ValueError, by name, for what of the FP8 format nothing here serves: experts, static activation scales, e5m2."""
+        leaf = name.rpartition(".")[2]
+        if ".experts." in name and (t.dtype in (torch.float8_e4m3fn, torch.float8_e5m2) or leaf.endswith("_scale_inv")):
+            raise ValueError(f"{name}: FP8 experts are not served (the attention projections and the dense MLP layers are)")
+        if leaf in _FP8_ACTIVATION or leaf.endswith(tuple("_" + a for a in _FP8_ACTIVATION)):
+            raise ValueError(f"{name}: a static activation scale (input_scale / activation_scale); activations are not quantised "
+                             f"here and the tensor is not served")
+        if t.dtype == torch.float8_e5m2:
+            raise ValueError(f"{name}: {t.dtype}: only e4m3 FP8 weights are served")
+
+    def _take_fp8(self, name: str, owner: str, leaf: str, t: torch.Tensor) -> bool:
+        """The tensors of the FP8 format -> True when `name` was one and has been dealt with."""
+        fp8_dtype = t.dtype == torch.float8_e4m3fn
+        lin = self.fp8.get(owner)
+        if lin is not None and leaf in _FP8_PAIR:
+            t = t.to(lin.weight.device)
+            if leaf == "weight" and not fp8_dtype:          # a 16-bit weight: quantised here, as from_pretrained(fp8_weights=True) asks
+                lin.quantize_(t, name)
+                self._fill(f"{owner}.{b}" for b in _FP8_PAIR)
+            else:
+                lin.load_(**{"weight_fp8" if leaf == "weight" else "scale": t}, name=name)
+                self._fill([name])
+            return True
+        dense = self.dense.get(owner)
+        if dense is not None and leaf == "weight" and t.dtype == torch.uint8:
+            raise ValueError(f"{name}: a uint8 weight for a linear; FP8 bytes have to come as float8_e4m3fn with their weight_scale_inv")
+        if not (fp8_dtype or leaf == "weight_scale_inv"):
+            return False
+        if dense is None or not (leaf == "weight_scale_inv" or (fp8_dtype and leaf == "weight")):
+            raise ValueError(f"{name}: an FP8 tensor whose owner is neither an FP8 linear nor a dense linear of this model")
+        have = self.pending.setdefault(owner, {})
+        have[leaf] = t
+        if len(have) == 2:
+            w, O, K = have["weight"].to(dense.weight.device), dense.out_features, dense.in_features
+            if tuple(w.shape) != (O, K):
+                raise ValueError(f"{owner}.weight: shape {tuple(w.shape)} does not fit ({O}, {K})")
+            scale = wfp8.as_scale(have["weight_scale_inv"].to(w.device), O, K, f"{owner}.weight_scale_inv")
+            dense.weight.data.copy_(wfp8.dequant_torch(wfp8.as_bytes(w, f"{owner}.weight"), scale, dense.weight.dtype))
+            del self.pending[owner]
+            self._fill([f"{owner}.weight"])
+        return True
 
     def _take_piece(self, name: str, owner: str, e: int, part: str, t: torch.Tensor) -> None:
         ex, stack = self.experts[owner], "down_proj" if part == "down" else "gate_up_proj"
@@ -131,10 +215,14 @@ class CheckpointLoader:
         self._fill(self._keys(owner, stack))
 
     def finish(self) -> None:
-        """KeyError over the state_dict keys that still owe a slot."""
+        """KeyError over the state_dict keys that still owe a slot; ValueError over a half of an FP8 pair left waiting."""
         missing = [k for k, slots in self.owed.items() if slots]
         if missing:
             raise KeyError(f"checkpoint lacks {missing[:5]}{' ...' if len(missing) > 5 else ''}")
+        if self.pending:            # (its key is filled: the weight came as 16-bit, and this half belongs to nothing)
+            stray = [f"{owner}.{leaf}" for owner, have in self.pending.items() for leaf in have]
+            raise ValueError(f"{stray[:5]}{' ...' if len(stray) > 5 else ''}: half of an FP8 pair whose other half never came, beside a "
+                             f"weight that is not FP8")
 
 
 def load_weights(model: nn.Module, path: str, device, dtype) -> nn.Module:
@@ -152,6 +240,8 @@ def save_quantized(model: nn.Module, path: str) -> None:
     """The body of the models' save_quantized: config.json with the tags read_config strips, and model.safetensors."""
     from safetensors.torch import save_file
     cfg = model.config
+    if getattr(cfg, "kivi_fp8_weights", False):
+        return _save_fp8(model, path)
     wbits, ebits = getattr(cfg, "kivi_weight_bits", None), getattr(cfg, "kivi_expert_bits", None)
     if wbits is None and ebits is None:
         raise ValueError("save_quantized: the model was not built with weight_bits=4 or expert_bits=4")
@@ -165,4 +255,30 @@ def save_quantized(model: nn.Module, path: str) -> None:
         json.dump(d, fh, indent=1)
     state = {k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()
              if not (cfg.tie_word_embeddings and k == "lm_head.weight")}
+    save_file(state, os.path.join(path, "model.safetensors"))
+
+
+def _save_fp8(model: nn.Module, path: str) -> None:
+    """save_quantized of a model built with fp8_weights: transformers' fine-grained FP8 format -- `weight` as
+    float8_e4m3fn and `weight_scale_inv` as float32 under the module names, and the `quantization_config` block read_config reads;
+    `modules_to_not_convert` lists the linears that stayed dense, lm_head among them.  No tag of this project's."""
+    from safetensors.torch import save_file
+    cfg = model.config
+    os.makedirs(path, exist_ok=True)
+    fp8 = {n for n, m in model.named_modules() if isinstance(m, wfp8.Fp8Linear)}
+    dense = [n for n, m in model.named_modules() if isinstance(m, nn.Linear)]
+    d = dict(cfg.kivi_hf_config, quantization_config=dict(
+        quant_method="fp8", fmt="e4m3", activation_scheme="dynamic", weight_block_size=[wfp8.BLOCK, wfp8.BLOCK], scale_fmt="float",
+        modules_to_not_convert=dense))
+    with open(os.path.join(path, "config.json"), "w") as fh:
+        json.dump(d, fh, indent=1)
+    state = {}
+    for k, v in model.state_dict().items():
+        if cfg.tie_word_embeddings and k == "lm_head.weight":
+            continue
+        owner, _, leaf = k.rpartition(".")
+        v = v.detach().cpu().contiguous()
+        if owner in fp8 and leaf in _FP8_PAIR:
+            v = v.view(torch.float8_e4m3fn if leaf == "weight" else torch.float32)
+        state[k] = v
     save_file(state, os.path.join(path, "model.safetensors"))

@@ -285,6 +285,7 @@ class LoraSet:
     for the length of a call (`bound`)."""
 
     def __init__(self, model: nn.Module, max_adapters: int, max_rank: int, target_modules: Sequence[str] = ("q_proj", "v_proj")):
+        from .wfp8 import Fp8Linear
         from .wquant import QuantLinear
         if isinstance(max_adapters, bool) or not isinstance(max_adapters, int) or max_adapters < 1:
             raise ValueError(f"max_adapters has to be a positive integer, got {max_adapters!r}")
@@ -306,7 +307,7 @@ class LoraSet:
         self.B: Dict[str, torch.Tensor] = {}
         for name, m in model.named_modules():
             leaf = name.rsplit(".", 1)[-1]
-            if leaf not in target_modules or not isinstance(m, (nn.Linear, QuantLinear)) or ".experts." in name:
+            if leaf not in target_modules or not isinstance(m, (nn.Linear, QuantLinear, Fp8Linear)) or ".experts." in name:
                 continue
             K, O = m.in_features, m.out_features
             if K % 8 or O % 8:

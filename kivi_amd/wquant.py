@@ -273,6 +273,28 @@ class QuantLinear(nn.Module):
         return y.view(*x.shape[:-1], self.out_features)
 
 
+def swiglu_forward(mlp: nn.Module, x: torch.Tensor, fused_gate_up, down_linear) -> torch.Tensor:
+    """The forward pass of a SwiGLU MLP over quantised linears `mlp.gate_proj / up_proj / down_proj` -- the one statement of the
+    policy, whatever the weight format (QuantMLP here, Fp8MLP of kivi_amd/wfp8.py).  `fused_gate_up(x2)`: the format's gate_up launch
+    over (N, K) rows; `down_linear(a)`: its linear launch over the down matrix, without the module's hooks."""
+    _lib.require_gpu(x, "x")
+    x2 = x.reshape(-1, x.shape[-1])
+    if not mlp.down_proj.uses_kernel(x2.shape[0]):
+        return mlp.down_proj(F.silu(mlp.gate_proj(x)) * mlp.up_proj(x))
+    a = fused_gate_up(x2)
+    bound = active_binding(mlp.gate_proj, mlp.up_proj)
+    if bound is not None and x.dim() == 3:
+        # A LoRA adapter on gate or up (DESIGN.md section 34) needs the two linears apart: the three-linear route, each linear
+        # the format's linear launch and its hook.  The fused launch rounds silu(g) * u once, that route three times, so the rows of
+        # the base model (slot -1) keep the fused value: their bytes stay those of a pass without adapters.
+        adapted = (F.silu(mlp.gate_proj(x)) * mlp.up_proj(x)).view_as(a)
+        rows = (bound.for_rows(x.shape[0]).slots >= 0).repeat_interleave(x.shape[1])
+        a = torch.where(rows[:, None], adapted, a)
+    if active_binding(mlp.down_proj) is not None and x.dim() == 3:
+        return mlp.down_proj(a.view(*x.shape[:-1], -1))         # the same linear launch, then the module's hook
+    return down_linear(a).view(x.shape)
+
+
 class QuantMLP(nn.Module):
     """The dense SwiGLU MLP over 4-bit weights under the checkpoint's names gate_proj / up_proj / down_proj: one kivi_w4_gate_up
     launch and one kivi_w4_linear launch; above `kernel_max_tokens` outside a capture the three linears through the scratch."""
@@ -284,22 +306,8 @@ class QuantMLP(nn.Module):
         self.down_proj = QuantLinear(intermediate, hidden, False, group, kernel_max_tokens)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        _lib.require_gpu(x, "x")
-        x2 = x.reshape(-1, x.shape[-1])
-        if not self.down_proj.uses_kernel(x2.shape[0]):
-            return self.down_proj(F.silu(self.gate_proj(x)) * self.up_proj(x))
-        a = gate_up(x2, self.gate_proj.triple, self.up_proj.triple)
-        bound = active_binding(self.gate_proj, self.up_proj)
-        if bound is not None and x.dim() == 3:
-            # A LoRA adapter on gate or up needs the two linears apart: the three-linear route, each linear
-            # kivi_w4_linear and its hook.  The fused launch rounds silu(g) * u once, that route three times, so the rows of the base
-            # model (slot -1) keep the fused value: their bytes stay those of a pass without adapters.
-            adapted = (F.silu(self.gate_proj(x)) * self.up_proj(x)).view_as(a)
-            rows = (bound.for_rows(x.shape[0]).slots >= 0).repeat_interleave(x.shape[1])
-            a = torch.where(rows[:, None], adapted, a)
-        if active_binding(self.down_proj) is not None and x.dim() == 3:
-            return self.down_proj(a.view(*x.shape[:-1], -1))        # the same kivi_w4_linear launch, then the module's hook
-        return linear(a, *self.down_proj.triple).view(x.shape)
+        return swiglu_forward(self, x, lambda x2: gate_up(x2, self.gate_proj.triple, self.up_proj.triple),
+                              lambda a: linear(a, *self.down_proj.triple))
 
 
 # ------------------------------------------------------------------------------------------------ the factory the models use
@@ -310,18 +318,47 @@ def weight_bits_of(cfg) -> Optional[int]:
     return bits
 
 
-def make_linear(cfg, in_features: int, out_features: int, bias: bool = False) -> nn.Module:
-    """nn.Linear, or with `cfg.kivi_weight_bits == 4` and a shape the kernels serve a QuantLinear."""
+def fp8_weights_of(cfg) -> bool:
+    fp8 = bool(getattr(cfg, "kivi_fp8_weights", False))
+    if fp8 and weight_bits_of(cfg) is not None:
+        raise ValueError("fp8_weights and weight_bits=4 are two formats of the same weights: choose one")
+    return fp8
+
+
+def _fp8_converts(cfg, *names) -> bool:
+    """Whether the checkpoint's `modules_to_not_convert` (cfg.kivi_fp8_skip) leaves all of the dotted module names to FP8."""
+    from .wfp8 import should_convert
+    return all(should_convert(n, getattr(cfg, "kivi_fp8_skip", None)) for n in names)
+
+
+def make_linear(cfg, in_features: int, out_features: int, bias: bool = False, name: Optional[str] = None) -> nn.Module:
+    """nn.Linear; with `cfg.kivi_weight_bits == 4` and a shape the kernels serve a QuantLinear; with `cfg.kivi_fp8_weights`, a shape
+    the FP8 kernels serve and a dotted module `name` the checkpoint's `modules_to_not_convert` does not hold, an Fp8Linear
+    (kivi_amd/wfp8.py)."""
+    max_tokens = getattr(cfg, "kivi_weight_kernel_max_tokens", None)
+    if fp8_weights_of(cfg):
+        from .wfp8 import Fp8Linear, usable as fp8_usable
+        if fp8_usable(out_features, in_features) and _fp8_converts(cfg, name):
+            return Fp8Linear(in_features, out_features, bias, max_tokens)
+        return nn.Linear(in_features, out_features, bias=bias)
     group = getattr(cfg, "kivi_weight_group", 128)
     if weight_bits_of(cfg) is None or not usable(out_features, in_features, group):
         return nn.Linear(in_features, out_features, bias=bias)
-    return QuantLinear(in_features, out_features, bias, group, getattr(cfg, "kivi_weight_kernel_max_tokens", None))
+    return QuantLinear(in_features, out_features, bias, group, max_tokens)
 
 
-def make_dense_mlp(cfg, plain_cls) -> nn.Module:
-    """`plain_cls(cfg)`, or with `cfg.kivi_weight_bits == 4` and sizes the kernels serve a QuantMLP."""
-    group = getattr(cfg, "kivi_weight_group", 128)
-    if weight_bits_of(cfg) is None or not (usable(cfg.intermediate_size, cfg.hidden_size, group)
-                                           and usable(cfg.hidden_size, cfg.intermediate_size, group)):
+def make_dense_mlp(cfg, plain_cls, name: Optional[str] = None) -> nn.Module:
+    """`plain_cls(cfg)`; with `cfg.kivi_weight_bits == 4` and sizes the kernels serve a QuantMLP; with `cfg.kivi_fp8_weights`, sizes
+    the FP8 kernels serve and none of the three projections under the dotted module `name` in `modules_to_not_convert`, an Fp8MLP."""
+    hidden, inter = cfg.hidden_size, cfg.intermediate_size
+    max_tokens = getattr(cfg, "kivi_weight_kernel_max_tokens", None)
+    if fp8_weights_of(cfg):
+        from .wfp8 import Fp8MLP, usable as fp8_usable
+        names = [None if name is None else f"{name}.{p}_proj" for p in ("gate", "up", "down")]
+        if fp8_usable(inter, hidden) and fp8_usable(hidden, inter) and _fp8_converts(cfg, *names):
+            return Fp8MLP(hidden, inter, max_tokens)
         return plain_cls(cfg)
-    return QuantMLP(cfg.hidden_size, cfg.intermediate_size, group, getattr(cfg, "kivi_weight_kernel_max_tokens", None))
+    group = getattr(cfg, "kivi_weight_group", 128)
+    if weight_bits_of(cfg) is None or not (usable(inter, hidden, group) and usable(hidden, inter, group)):
+        return plain_cls(cfg)
+    return QuantMLP(hidden, inter, group, max_tokens)
