@@ -1084,6 +1084,24 @@ int kivi_moe_experts(const void* x, int64_t x_stride, int dtype, int N, int H, i
                      const void* down, void* out, int64_t out_stride, void* workspace, int64_t workspace_bytes,
                      kivi_stream_t stream);
 /*
+ * kivi_moe_experts_w8: kivi_moe_experts over experts held in the fine-grained FP8 format of section 35, as a
+ * checkpoint stacks them.  Three launches (gate/up, down, combine), nothing read back.
+ *   gate_up        (E, 2 I, H) row-major, one OCP e4m3fn byte per element, no NaN byte; gate rows [0, I), up rows [I, 2 I)
+ *   gate_up_scale  (E, 2 I / 128, H / 128) fp32, the factor one MULTIPLIES by (`gate_up_proj_scale_inv`)
+ *   down           (E, H, I) bytes;   down_scale  (E, H / 128, I / 128) fp32
+ *   every other argument as kivi_moe_experts; the plan is kivi_moe_route's, the workspace kivi_moe_workspace_bytes's.
+ * The represented weight is the real number e4m3(byte) * scale[row / 128, col / 128]; the result is kivi_moe_experts' contract over
+ * those weights: x stays 16-bit, fp32 accumulation (per 128-element stretch on the matrix pipe, then one fused multiply-add by the
+ * block's scale), silu(g) * u rounded once to the dtype, the pair outputs combined in slot order and rounded once.  A token's bits
+ * depend on H and I only.  No atomics.
+ * KIVI_EINVAL / KIVI_EALIGN as kivi_moe_experts, and KIVI_EINVAL for H or I not a positive multiple of 128 or a null scale pointer,
+ * KIVI_EALIGN for a scale pointer off 4 bytes.
+ */
+int kivi_moe_experts_w8(const void* x, int64_t x_stride, int dtype, int N, int H, int I, int E, int top_k, const void* w,
+                        const void* pairs, const void* pos, const void* tiles, const void* n_tiles, const void* gate_up,
+                        const void* gate_up_scale, const void* down, const void* down_scale, void* out, int64_t out_stride,
+                        void* workspace, int64_t workspace_bytes, kivi_stream_t stream);
+/*
  * Weight-only 4-bit dense layers.  A weight W (O, K) is quantised in groups of G in {64, 128} along K:
  * codes, scale and mn are exactly what the reference's last-dim quantiser (quant/new_pack.py:217-252 at 4 bits; kivi_quant.h) gives
  * for the FP16 IMAGE of W viewed as (1, 1, O, K) -- a bf16 weight is rounded once to fp16 first --, degenerate groups (constant,

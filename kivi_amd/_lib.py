@@ -221,6 +221,8 @@ SIGNATURES = {
     "kivi_moe_route": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kivi_moe_experts": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
                                 _vp]),
+    "kivi_moe_experts_w8": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                   _vp, _i64, _vp]),
     "kivi_w4_bytes": (_i64, [_i32, _i32, _i32]),
     "kivi_w4_pack": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "kivi_w4_dequant": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),

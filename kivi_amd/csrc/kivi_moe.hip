@@ -1,5 +1,6 @@
 // kivi_moe_route / kivi_moe_experts (include/kivi_hip.h): the sparse mixture-of-experts feed-forward block of
 // Mixtral / Qwen3-MoE as launches that never report to the host, so that a decode step holding one can be captured.
+// kivi_moe_experts_w8 (section 36): the same three launches over experts held as block-scaled e4m3fn bytes (moe_gemm_w8_kernel).
 //
 //   route     one wave per token: the K largest logits (ties to the lower expert), their softmax weights, a count per expert;
 //             then one block: the prefix sums, the tile list and the grouping of the pairs by expert
@@ -23,6 +24,8 @@
 
 #include "kivi_common.h"
 #include "kivi_moe_plan.h"
+#include "kivi_moe_w8_plan.h"
+#include "kivi_w8_operand.h"
 
 namespace {
 
@@ -256,6 +259,122 @@ __global__ __launch_bounds__(kThreads) void moe_gemm_kernel(const uint16_t* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------------------- experts, FP8 weights
+// moe_gemm_kernel over e4m3fn bytes with one fp32 scale per 128 x 128 block.  The block, the guards, the
+// split of the reduction axis, the tree and the epilogues are moe_gemm_kernel's; inside a 128-element stretch the operands are
+// formed as kivi_w8.hip forms them (kivi_w8_operand.h, kivi_w8_plan_step_k): lane (r, kb) reads, for half h, the 16 bytes of its
+// row at k = 128 stretch + 64 h + 16 kb -- the low 8 its A fragment of one step against x[k .. k + 8), the high 8 that of the
+// next against x[k + 8 .. k + 16).  The stretch's four MFMAs go into a zeroed tile, then yacc = fma(tile, s, yacc) with the ONE
+// scale of (stripe, stretch).  Every address is kivi_moe_w8_plan.h's.
+//   What one wave needs of one stretch: per matrix 2 x 16 bytes of its lane's row and the scale, and 16 bytes per step of its token row.
+template <int NM>
+struct MoeW8Stage {
+    u32x4 w[NM][2];
+    float s[NM];
+    u32x4 x[4];
+    __device__ __forceinline__ void load(bool in, int64_t st, const uint8_t* const* wr, const float* const* sp, const uint16_t* xr,
+                                         int kb, bool live) {
+        if (!in) return;                                    // wave-uniform: past the wave's last stretch
+#pragma unroll
+        for (int m = 0; m < NM; m++) {
+            w[m][0] = *reinterpret_cast<const u32x4*>(wr[m] + kivi_moe_w8_plan_weight_byte(0, 0, 0, 0, st, 0, 0));
+            w[m][1] = *reinterpret_cast<const u32x4*>(wr[m] + kivi_moe_w8_plan_weight_byte(0, 0, 0, 0, st, 1, 0));
+            s[m] = sp[m][st];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) x[j] = live ? ld16(xr + kivi_moe_w8_plan_src_elem(0, 0, st, j, kb)) : u32x4{0u, 0u, 0u, 0u};
+    }
+};
+
+//   src     GATEUP: x (N, H) by src_stride, the row of a pair found through `pairs`; else act (NK, I), row = position in `pairs`
+//   wmat / scale   GATEUP: gate_up (E, 2 I, H) bytes and (E, 2 I / 128, H / 128) fp32; else down (E, H, I) and (E, H / 128, I / 128)
+//   R       rows of the matrix this launch walks (I / H), C its columns = the reduction length (H / I): multiples of 128
+template <bool BF, bool GATEUP>
+__global__ __launch_bounds__(kThreads) void moe_gemm_w8_kernel(const uint16_t* __restrict__ src, int64_t src_stride,
+                                                               const uint8_t* __restrict__ wmat, const float* __restrict__ scale,
+                                                               const int* __restrict__ pairs, const int* __restrict__ tiles,
+                                                               const int* __restrict__ n_tiles, int max_tiles, void* __restrict__ dst,
+                                                               int NK, int R, int C, int E, int K) {
+    constexpr int NM = GATEUP ? 2 : 1;
+    __shared__ f32x4 red[kWaves - 1][NM][KIVI_WAVE];
+    const int tile = blockIdx.x;
+    const int live_tiles = *n_tiles;
+    if (tile >= live_tiles || tile >= max_tiles) return;    // block-uniform: the grid is the host's bound
+    const int* tl = tiles + (int64_t)tile * KIVI_MOE_TILE_WORDS;
+    const int e = tl[0], first = tl[1], rows = tl[2];
+    if ((unsigned)e >= (unsigned)E || rows < 1 || rows > kTile || first < 0 || first > NK - rows) return;   // not a plan of route's
+    const int lane = threadIdx.x & (KIVI_WAVE - 1), wave = threadIdx.x / KIVI_WAVE;
+    const int r = lane & 15, kb = lane >> 4;
+    const int r0 = blockIdx.y * KIVI_MOE_ROW_TILE;
+    const int64_t slab = (int64_t)NM * R;                   // rows of an expert's matrix: 2 I (gate rows, then up rows) or H
+    const uint8_t* wr[NM];
+    const float* sp[NM];
+    wr[0] = wmat + kivi_moe_w8_plan_weight_byte(e, slab, r0 + r, C, 0, 0, kb);
+    sp[0] = scale + kivi_moe_w8_plan_scale_word(e, slab, r0, C, 0);
+    if constexpr (GATEUP) {
+        wr[1] = wmat + kivi_moe_w8_plan_weight_byte(e, slab, (int64_t)R + r0 + r, C, 0, 0, kb);
+        sp[1] = scale + kivi_moe_w8_plan_scale_word(e, slab, (int64_t)R + r0, C, 0);
+    }
+    bool live = r < rows;
+    const uint16_t* xr = src;
+    if (live) {
+        if constexpr (GATEUP) {
+            const int pair = pairs[first + r];
+            live = (unsigned)pair < (unsigned)NK;
+            xr = src + kivi_moe_w8_plan_src_elem(live ? pair / K : 0, src_stride, 0, 0, 0);
+        } else {
+            xr = src + kivi_moe_w8_plan_src_elem(first + r, src_stride, 0, 0, 0);
+        }
+    }
+    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 yacc[NM];
+#pragma unroll
+    for (int m = 0; m < NM; m++) yacc[m] = zero;
+    const int64_t stretches = kivi_moe_w8_plan_stretches(C);
+    // a stretch's bytes, scales and token row are requested one stretch of the wave ahead of their use
+    MoeW8Stage<NM> cur, nxt;
+    cur.load(wave < stretches, wave, wr, sp, xr, kb, live);
+    for (int64_t st = wave; st < stretches; st += kWaves) { // wave-uniform
+        nxt.load(st + kWaves < stretches, st + kWaves, wr, sp, xr, kb, live);
+        f32x4 acc[NM];
+#pragma unroll
+        for (int m = 0; m < NM; m++) acc[m] = zero;
+#pragma unroll
+        for (int j = 0; j < 4; j++)                         // four steps of 32 reduction elements
+#pragma unroll
+            for (int m = 0; m < NM; m++)
+                acc[m] = mfma<BF>(w8_operand<BF>(cur.w[m][j >> 1][2 * (j & 1)], cur.w[m][j >> 1][2 * (j & 1) + 1]), cur.x[j], acc[m]);
+#pragma unroll
+        for (int m = 0; m < NM; m++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) yacc[m][i] = __builtin_fmaf(acc[m][i], cur.s[m], yacc[m][i]);
+        cur = nxt;
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int m = 0; m < NM; m++) red[wave - 1][m][lane] = yacc[m];
+    }
+    __syncthreads();
+    if (wave > 0) return;
+#pragma unroll
+    for (int m = 0; m < NM; m++) yacc[m] = (yacc[m] + red[0][m][lane]) + (red[1][m][lane] + red[2][m][lane]);
+    if (r >= rows) return;
+    // lane: token column r, weight rows r0 + 4 kb + j
+    const int64_t at = kivi_moe_w8_plan_dst_elem(first + r, R, r0, kb);
+    if constexpr (GATEUP) {
+        uint16_t h[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const float g = yacc[0][j];
+            h[j] = to_bits<BF>(g / (1.0f + expf(-g)) * yacc[NM - 1][j]);
+        }
+        u32x2 out = {(uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16)};
+        *reinterpret_cast<u32x2*>((uint16_t*)dst + at) = out;
+    } else {
+        *reinterpret_cast<f32x4*>((float*)dst + at) = yacc[0];
+    }
+}
+
 template <bool BF>
 __global__ __launch_bounds__(kThreads) void moe_combine_kernel(const float* __restrict__ y, const float* __restrict__ w,
                                                                const int* __restrict__ pos, uint16_t* __restrict__ out,
@@ -374,4 +493,58 @@ extern "C" int kivi_moe_experts(const void* x, int64_t x_stride, int dtype, int 
                     out_stride, N, H, top_k, (int)nk);
     }
     return kivi_launch_status("kivi_moe_experts");
+}
+
+extern "C" int kivi_moe_experts_w8(const void* x, int64_t x_stride, int dtype, int N, int H, int I, int E, int top_k, const void* w,
+                                   const void* pairs, const void* pos, const void* tiles, const void* n_tiles, const void* gate_up,
+                                   const void* gate_up_scale, const void* down, const void* down_scale, void* out, int64_t out_stride,
+                                   void* workspace, int64_t workspace_bytes, kivi_stream_t stream) {
+    static_assert(kWaves == KIVI_MOE_W8_WAVES, "the stretches of kivi_moe_w8_plan.h are dealt over the block's waves");
+    KIVI_REQUIRE(kivi_moe_plan_dtype_ok(dtype), KIVI_EINVAL, "kivi_moe_experts_w8: dtype=%d (16: fp16, 0x110: bf16)", dtype);
+    const int64_t nk = kivi_moe_plan_pairs(N, E, top_k);
+    KIVI_REQUIRE(nk >= 0, KIVI_EINVAL, "kivi_moe_experts_w8: N=%d E=%d top_k=%d (N >= 1, E in [1, 256], top_k in [1, min(E, 16)], "
+                 "N * top_k < 2^31)", N, E, top_k);
+    KIVI_REQUIRE(kivi_moe_w8_plan_dims_ok(H, I) && kivi_moe_plan_grids_ok(N, H, I), KIVI_EINVAL,
+                 "kivi_moe_experts_w8: H=%d I=%d (positive multiples of 128, at most 16 * 65535; N * H / 1024 < 2^31)", H, I);
+    KIVI_REQUIRE(x_stride >= H && out_stride >= H, KIVI_EINVAL, "kivi_moe_experts_w8: x_stride=%lld or out_stride=%lld < H=%d",
+                 (long long)x_stride, (long long)out_stride, H);
+    KIVI_REQUIRE(x && w && pairs && pos && tiles && n_tiles && gate_up && gate_up_scale && down && down_scale && out && workspace,
+                 KIVI_EINVAL, "kivi_moe_experts_w8: null x, w, pairs, pos, tiles, n_tiles, gate_up, gate_up_scale, down, down_scale, out "
+                 "or workspace");
+    const int64_t need = kivi_moe_plan_workspace_bytes((int64_t)N, H, I, E, top_k);
+    KIVI_REQUIRE(need >= 0 && workspace_bytes >= need, KIVI_EINVAL, "kivi_moe_experts_w8: workspace_bytes=%lld < %lld",
+                 (long long)workspace_bytes, (long long)need);
+    for (const void* p : {x, gate_up, down, (const void*)workspace})
+        KIVI_REQUIRE((uintptr_t)p % 16 == 0, KIVI_EALIGN, "kivi_moe_experts_w8: x, gate_up, down or workspace off 16 bytes");
+    KIVI_REQUIRE((uintptr_t)out % 8 == 0 && x_stride % 8 == 0 && out_stride % 4 == 0, KIVI_EALIGN,
+                 "kivi_moe_experts_w8: out off 8 bytes, x_stride=%lld not a multiple of 8 or out_stride=%lld not of 4", (long long)x_stride,
+                 (long long)out_stride);
+    for (const void* p : {w, pairs, pos, tiles, n_tiles, gate_up_scale, down_scale})
+        KIVI_REQUIRE((uintptr_t)p % 4 == 0, KIVI_EALIGN, "kivi_moe_experts_w8: a 4-byte plan member or a scale grid off 4 bytes");
+    const int max_tiles = (int)kivi_moe_plan_max_tiles((int64_t)N, E, top_k);
+    hipStream_t s = (hipStream_t)stream;
+    uint16_t* act = (uint16_t*)workspace;
+    float* y = (float*)((char*)workspace + kivi_moe_w8_plan_y_offset(nk, I));
+    const dim3 g1((unsigned)max_tiles, (unsigned)kivi_moe_plan_row_blocks(I)), g2((unsigned)max_tiles, (unsigned)kivi_moe_plan_row_blocks(H));
+    const dim3 g3((unsigned)kivi_moe_plan_combine_blocks(N, H));
+    if (dtype == KIVI_MOE_BF16) {
+        KIVI_LAUNCH((moe_gemm_w8_kernel<true, true>), g1, dim3(kThreads), s, (const uint16_t*)x, x_stride, (const uint8_t*)gate_up,
+                    (const float*)gate_up_scale, (const int*)pairs, (const int*)tiles, (const int*)n_tiles, max_tiles, (void*)act, (int)nk,
+                    I, H, E, top_k);
+        KIVI_LAUNCH((moe_gemm_w8_kernel<true, false>), g2, dim3(kThreads), s, (const uint16_t*)act, (int64_t)I, (const uint8_t*)down,
+                    (const float*)down_scale, (const int*)pairs, (const int*)tiles, (const int*)n_tiles, max_tiles, (void*)y, (int)nk, H,
+                    I, E, top_k);
+        KIVI_LAUNCH(moe_combine_kernel<true>, g3, dim3(kThreads), s, (const float*)y, (const float*)w, (const int*)pos, (uint16_t*)out,
+                    out_stride, N, H, top_k, (int)nk);
+    } else {
+        KIVI_LAUNCH((moe_gemm_w8_kernel<false, true>), g1, dim3(kThreads), s, (const uint16_t*)x, x_stride, (const uint8_t*)gate_up,
+                    (const float*)gate_up_scale, (const int*)pairs, (const int*)tiles, (const int*)n_tiles, max_tiles, (void*)act, (int)nk,
+                    I, H, E, top_k);
+        KIVI_LAUNCH((moe_gemm_w8_kernel<false, false>), g2, dim3(kThreads), s, (const uint16_t*)act, (int64_t)I, (const uint8_t*)down,
+                    (const float*)down_scale, (const int*)pairs, (const int*)tiles, (const int*)n_tiles, max_tiles, (void*)y, (int)nk, H,
+                    I, E, top_k);
+        KIVI_LAUNCH(moe_combine_kernel<false>, g3, dim3(kThreads), s, (const float*)y, (const float*)w, (const int*)pos, (uint16_t*)out,
+                    out_stride, N, H, top_k, (int)nk);
+    }
+    return kivi_launch_status("kivi_moe_experts_w8");
 }

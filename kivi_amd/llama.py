@@ -42,7 +42,8 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
                 qk_kernel: bool = False, moe_kernel: bool = True, moe_kernel_max_tokens: Optional[int] = None,
                 weight_bits: Optional[int] = None, weight_group: int = 128,
                 weight_kernel_max_tokens: Optional[int] = None, expert_bits: Optional[int] = None,
-                expert_group: int = 128, fp8_weights: bool = False, fp8_skip_modules=None) -> SimpleNamespace:
+                expert_group: int = 128, fp8_weights: bool = False, fp8_skip_modules=None,
+                fp8_experts: bool = False) -> SimpleNamespace:
     """HF config.json fields (+ the four KIVI fields) -> the namespace the modules read.  `prefill_kernel`: the prompt pass's
     attention runs kivi_prefill_attention, and every attention class serves left-padded prompts.
     `decode_lead`: the decode steps of a padded batch hand the kernels every row's leading pads, and the row kernels skip the packed
@@ -64,7 +65,10 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
     DESIGN.md section 35); `weight_kernel_max_tokens` bounds its kernel as it does the 4-bit one (None:
     kivi_amd.wfp8.KERNEL_MAX_TOKENS).  `fp8_skip_modules`: a checkpoint's `modules_to_not_convert`, patterns of module names that
     stay dense.  Embeddings, lm_head and the experts of a sparse block keep the model dtype.  Together with `weight_bits=4` it
-    raises: the two are formats of the same weights; together with `expert_bits=4` it raises as well."""
+    raises: the two are formats of the same weights; together with `expert_bits=4` it raises as well.
+    `fp8_experts`: the experts of the sparse blocks hold the same FP8 format (kivi_amd.moe.Fp8Experts) and run
+    kivi_moe_experts_w8, which a captured decode step may hold; H and the experts' intermediate size must be multiples of 128.  Given
+    alone or with `fp8_weights`; with `expert_bits=4` or `weight_bits=4` it raises, and a config without experts refuses it."""
     if weight_bits not in (None, 4):
         raise ValueError(f"weight_bits has to be None or 4, got {weight_bits!r}")
     if weight_bits is not None and weight_group not in wquant.GROUPS:
@@ -77,6 +81,10 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
         raise ValueError("fp8_weights and weight_bits=4 are two formats of the same weights: choose one")
     if fp8_weights and expert_bits is not None:
         raise ValueError("fp8_weights together with expert_bits=4 is not served: save_quantized has no format that holds both")
+    if fp8_experts and expert_bits is not None:
+        raise ValueError("fp8_experts and expert_bits=4 are two formats of the same experts: choose one")
+    if fp8_experts and weight_bits is not None:
+        raise ValueError("fp8_experts together with weight_bits=4 is not served: save_quantized has no format that holds both")
     extra = {}
     if fp8_weights:                         # (absent otherwise: the default namespace is what it was)
         extra = dict(kivi_fp8_weights=True, kivi_fp8_skip=None if fp8_skip_modules is None else list(fp8_skip_modules),
@@ -88,6 +96,10 @@ def make_config(d: dict, k_bits: int = 2, v_bits: int = 2, group_size: int = 32,
         if not int(d.get("num_local_experts", d.get("num_experts", 0)) or 0):
             raise ValueError("expert_bits: the config has no experts (num_local_experts / num_experts)")
         extra.update(kivi_expert_bits=expert_bits, kivi_expert_group=expert_group, kivi_hf_config=dict(d))
+    if fp8_experts:                         # (absent otherwise)
+        if not int(d.get("num_local_experts", d.get("num_experts", 0)) or 0):
+            raise ValueError("fp8_experts: the config has no experts (num_local_experts / num_experts)")
+        extra.update(kivi_fp8_experts=True, kivi_hf_config=dict(d))
     hidden, heads = d["hidden_size"], d["num_attention_heads"]
     for field in _SHARED_EXPERT_FIELDS:
         if d.get(field):
@@ -151,7 +163,8 @@ def make_mlp(cfg, layer_idx: int) -> nn.Module:
                           norm_topk=cfg.norm_topk_prob, round_weights=getattr(cfg, "kivi_moe_round_weights", False),
                           kernel=getattr(cfg, "kivi_moe_kernel", True),
                           kernel_max_tokens=getattr(cfg, "kivi_moe_kernel_max_tokens", None),
-                          expert_bits=getattr(cfg, "kivi_expert_bits", None), expert_group=getattr(cfg, "kivi_expert_group", 128))
+                          expert_bits=getattr(cfg, "kivi_expert_bits", None), expert_group=getattr(cfg, "kivi_expert_group", 128),
+                          expert_fp8=bool(getattr(cfg, "kivi_fp8_experts", False)))
 
 
 class DecoderLayer_KIVI(nn.Module):
@@ -682,7 +695,7 @@ class LlamaForCausalLM_KIVI(nn.Module):
         """`path`: a local HF checkpoint directory (config.json + *.safetensors).  `kivi`: k_bits, v_bits, group_size,
         residual_length, max_cache_len, prefill_kernel, decode_lead, qk_kernel (default: the class's, on for the Qwen classes),
         moe_kernel, moe_kernel_max_tokens, weight_bits, weight_group, weight_kernel_max_tokens, expert_bits, expert_group,
-        fp8_weights, fp8_skip_modules (an FP8 checkpoint's `modules_to_not_convert` is added to a list given here).
+        fp8_weights, fp8_skip_modules (an FP8 checkpoint's `modules_to_not_convert` is added to a list given here), fp8_experts.
         Called on LlamaForCausalLM_KIVI, a config.json whose `model_type` is qwen2 / qwen3 / mixtral / qwen3_moe builds that
         family's class.  The class, the config and the empty model are made here; reading config.json and filling the model are
         kivi_amd/loading.py: the files are read one at a time, and a checkpoint that leaves any tensor of
@@ -696,8 +709,11 @@ class LlamaForCausalLM_KIVI(nn.Module):
         or null, float scales) is served as it lies on disk: its `weight` bytes and `weight_scale_inv` go into
         Fp8Linear modules unchanged, `modules_to_not_convert` stay dense, and an FP8 weight whose module the kernels do not serve is
         dequantised in torch.  `activation_scheme: "dynamic"` is accepted and NOT applied: activations stay 16-bit, the more exact
-        arithmetic.  "static", `input_scale` / `activation_scale` tensors, ue8m0 scales, another block size and FP8 experts raise.
-        With `fp8_weights=True` a 16-bit checkpoint is quantised to that format on the device as its files are read."""
+        arithmetic.  "static", `input_scale` / `activation_scale` tensors, ue8m0 scales, another block size and -- without
+        `fp8_experts=True` -- FP8 experts raise.
+        With `fp8_weights=True` a 16-bit checkpoint is quantised to that format on the device as its files are read.
+        With `fp8_experts=True` the FP8 expert tensors of such a checkpoint -- per expert or fused, from any
+        file in any order -- go into the sparse blocks' Fp8Experts unchanged, and 16-bit expert weights are quantised into them."""
         d = loading.read_config(path, kivi)     # (a directory of save_quantized: its tags become keywords of make_config)
         if cls is LlamaForCausalLM_KIVI:
             cls = {"qwen2": Qwen2ForCausalLM_KIVI, "qwen3": Qwen3ForCausalLM_KIVI, "mixtral": MixtralForCausalLM_KIVI,
@@ -721,7 +737,8 @@ class LlamaForCausalLM_KIVI(nn.Module):
         layout tag kivi_weight_layout -- and model.safetensors with the 4-bit modules' `qweight` / `scales` / `mins` under their
         module names.  A model built with `fp8_weights` is written in transformers' format instead: `weight` as float8_e4m3fn and
         `weight_scale_inv` as float32 under the module names, and a `quantization_config` block (fp8, e4m3, dynamic, [128, 128],
-        float scales, `modules_to_not_convert`: the linears that stayed dense) in place of the tags.  from_pretrained reads either
+        float scales, `modules_to_not_convert`: the linears that stayed dense) in place of the tags; so is one built with
+        `fp8_experts`, its experts under the per-expert names (read back with `fp8_experts=True`).  from_pretrained reads either
         back without quantising anything."""
         loading.save_quantized(self, path)
 

@@ -17,14 +17,18 @@ import torch
 import torch.nn as nn
 
 from . import wfp8, wquant
-from .moe import QuantExperts, SparseMoeBlock
+from .moe import Fp8Experts, QuantExperts, SparseMoeBlock
 
 _TAGS = ("kivi_weight_layout", "kivi_weight_bits", "kivi_weight_group", "kivi_expert_bits", "kivi_expert_group")
-_EXPERT_NAME = re.compile(r"^(.*\.)(?:block_sparse_moe|mlp)\.experts\.(\d+)\.(w1|w2|w3|gate_proj|up_proj|down_proj)\.weight$")
+_EXPERT_NAME = re.compile(r"^(.*\.)(?:block_sparse_moe|mlp)\.experts\.(\d+)\.(w1|w2|w3|gate_proj|up_proj|down_proj)"
+                          r"\.(weight|weight_scale_inv)$")
 _EXPERT_PART = {"w1": "gate", "gate_proj": "gate", "w3": "up", "up_proj": "up", "w2": "down", "down_proj": "down"}
 _STACK_PARTS = {"gate_up_proj": ("gate", "up"), "down_proj": ("down",)}
 _TRIPLE = ("qweight", "scales", "mins")
 _FP8_PAIR = ("weight", "weight_scale_inv")
+_FP8_STACKS = {"gate_up_proj": ("gate_up_proj", "gate_up", "weight"), "gate_up_proj_scale_inv": ("gate_up_proj", "gate_up", "scale"),
+               "down_proj": ("down_proj", "down", "weight"), "down_proj_scale_inv": ("down_proj", "down", "scale")}
+_FP8_EXPERT_LEAVES = {"gate": "gate_proj", "up": "up_proj", "down": "down_proj"}   # the per-expert names save_quantized writes
 _FP8_ACTIVATION = ("input_scale", "activation_scale")      # tensors of a static activation scheme: never served
 
 
@@ -76,6 +80,11 @@ class CheckpointLoader:
       a fused expert stack  quantised expert by expert where the block holds a QuantExperts (a dense block takes it as any tensor);
       a QuantLinear weight  cast to `dtype` on the module's device and packed into its buffers (section 30), as
                             QuantLinear.from_linear on the loaded model would;
+      an FP8 expert tensor  (section 36; the block holds an Fp8Experts, `fp8_experts=True`) per expert -- `...experts.{e}.<proj>.weight`
+                            as float8_e4m3fn, `.weight_scale_inv` as fp32 -- or fused (`experts.gate_up_proj`, `.down_proj`, and
+                            their `_scale_inv`): checked and copied into the expert's slab as it is, each half filling its own
+                            key's slots, from any file in any order; a 16-bit expert weight is quantised and fills both halves.
+                            Without the flag such a tensor is refused;
       an Fp8Linear's pair   (section 35) a float8_e4m3fn `weight` is checked for NaN bytes and copied as bytes, a `weight_scale_inv`
                             copied as bits (a per-tensor scalar expanded), each filling its own key, in any order and from any
                             file; a 16-bit `weight` is quantised on the module's device and fills both;
@@ -86,7 +95,7 @@ class CheckpointLoader:
                             a shape that does not fit raises there, a name nothing takes ends in `unexpected`, a tensor that comes
                             again is written again.
     The ledger `owed`: state_dict key -> the slots nothing has filled yet.  A key is one slot; the key of an expert stack -- the
-    dense parameter, or each of a 4-bit stack's three buffers -- is one slot per (expert, part), part in gate / up / down, since
+    dense parameter, each of a 4-bit stack's three buffers, or each of an FP8 stack's two -- is one slot per (expert, part), part in gate / up / down, since
     only a set can tell a repeated piece from a missing one.  The tied lm_head.weight owes nothing.  But for that
     waiting half of an FP8 pair nothing here keeps a tensor of a file: it dies with the caller's dict."""
 
@@ -110,6 +119,8 @@ class CheckpointLoader:
         """The state_dict keys behind the stack `stack` (gate_up_proj / down_proj) of the experts module `owner`."""
         if isinstance(self.experts[owner], QuantExperts):
             return [f"{owner}.{stack}.{b}" for b in _TRIPLE]
+        if isinstance(self.experts[owner], Fp8Experts):
+            return [f"{owner}.{stack}", f"{owner}.{stack}_scale_inv"]
         return [f"{owner}.{stack}"]
 
     def _fill(self, keys, slots=None) -> None:
@@ -124,13 +135,18 @@ class CheckpointLoader:
             m = _EXPERT_NAME.match(name)
             if m is not None:
                 owner = f"{m.group(1)}mlp.experts"
-                if owner in self.experts:
+                if isinstance(self.experts.get(owner), Fp8Experts):
+                    self._take_fp8_piece(name, owner, int(m.group(2)), _EXPERT_PART[m.group(3)], m.group(4), t)
+                elif owner in self.experts and m.group(4) == "weight":
                     self._take_piece(name, owner, int(m.group(2)), _EXPERT_PART[m.group(3)], t)
                 else:
                     rest[name] = t                          # load_state_dict reports the name as unexpected
                 continue
             new = name.replace(".block_sparse_moe.", ".mlp.")
             owner, _, leaf = new.rpartition(".")
+            if leaf in _FP8_STACKS and isinstance(self.experts.get(owner), Fp8Experts):
+                self._take_fp8_fused(name, owner, leaf, t)
+                continue
             if self._take_fp8(new, owner, leaf, t):
                 continue
             if leaf in _STACK_PARTS and isinstance(self.experts.get(owner), QuantExperts):
@@ -146,12 +162,21 @@ class CheckpointLoader:
             self.unexpected += unexpected
             self._fill(rest.keys() - set(unexpected))
 
-    @staticmethod
-    def _refuse_unserved_fp8(name: str, t: torch.Tensor) -> None:
-        """ValueError, by name, for what of the FP8 format nothing here serves: experts, static activation scales, e5m2."""
+    def _fp8_experts_of(self, name: str):
+        """The Fp8Experts module the tensor `name` belongs to, or None."""
+        m = _EXPERT_NAME.match(name)
+        owner = f"{m.group(1)}mlp.experts" if m is not None else name.replace(".block_sparse_moe.", ".mlp.").rpartition(".")[0]
+        ex = self.experts.get(owner)
+        return ex if isinstance(ex, Fp8Experts) else None
+
+    def _refuse_unserved_fp8(self, name: str, t: torch.Tensor) -> None:
+        """ValueError, by name, for what of the FP8 format nothing here serves: experts of a model built without `fp8_experts`,
+        static activation scales, e5m2."""
         leaf = name.rpartition(".")[2]
-        if ".experts." in name and (t.dtype in (torch.float8_e4m3fn, torch.float8_e5m2) or leaf.endswith("_scale_inv")):
-            raise ValueError(f"{name}: FP8 experts are not served (the attention projections and the dense MLP layers are)")
+        if ".experts." in name and (t.dtype in (torch.float8_e4m3fn, torch.float8_e5m2) or leaf.endswith("_scale_inv")) \
+                and self._fp8_experts_of(name) is None:
+            raise ValueError(f"{name}: FP8 experts are not served (the attention projections and the dense MLP layers are) unless the "
+                             f"model is built with fp8_experts=True (from_pretrained(path, fp8_experts=True))")
         if leaf in _FP8_ACTIVATION or leaf.endswith(tuple("_" + a for a in _FP8_ACTIVATION)):
             raise ValueError(f"{name}: a static activation scale (input_scale / activation_scale); activations are not quantised "
                              f"here and the tensor is not served")
@@ -206,6 +231,52 @@ class CheckpointLoader:
             rows.copy_(t)
         self._fill(self._keys(owner, stack), {(e, part)})
 
+    def _take_fp8_piece(self, name: str, owner: str, e: int, part: str, leaf: str, t: torch.Tensor) -> None:
+        """One per-expert tensor of a block of FP8 experts: `weight` as float8_e4m3fn or `weight_scale_inv`
+        goes into the expert's slab as it is and fills its own key's slot (e, part); a 16-bit `weight` is quantised and fills both."""
+        ex, stack = self.experts[owner], "down_proj" if part == "down" else "gate_up_proj"
+        t = t.to(ex.down_proj.device)
+        if leaf == "weight_scale_inv":
+            ex.load_expert_(e, part, scale=t, name=name)
+            self._fill([f"{owner}.{stack}_scale_inv"], {(e, part)})
+        elif t.dtype == torch.float8_e4m3fn:
+            ex.load_expert_(e, part, weight_fp8=t, name=name)
+            self._fill([f"{owner}.{stack}"], {(e, part)})
+        elif t.is_floating_point():
+            ex.quantize_expert_(e, part, t, name)
+            self._fill(self._keys(owner, stack), {(e, part)})
+        else:
+            raise ValueError(f"{name}: {t.dtype} for an expert weight; FP8 bytes have to come as float8_e4m3fn with their "
+                             f"weight_scale_inv")
+
+    def _take_fp8_fused(self, name: str, owner: str, leaf: str, t: torch.Tensor) -> None:
+        """A fused stack of a block of FP8 experts: `gate_up_proj` / `down_proj` (E, rows, cols) as float8_e4m3fn, their `_scale_inv`
+        (E, rows / 128, cols / 128) as fp32 (or one per-tensor scalar), or a 16-bit stack, which is quantised expert by expert."""
+        ex = self.experts[owner]
+        stack, part, half = _FP8_STACKS[leaf]
+        t = t.to(ex.down_proj.device)
+        O, K = ex.shape_of(part)
+        if half == "scale":
+            if t.numel() != 1 and (t.dim() != 3 or t.shape[0] != ex.num_experts):
+                raise ValueError(f"{name}: shape {tuple(t.shape)} does not fit the block grids "
+                                 f"{(ex.num_experts, O // wfp8.BLOCK, K // wfp8.BLOCK)}")
+            for e in range(ex.num_experts):
+                ex.load_expert_(e, part, scale=t if t.numel() == 1 else t[e], name=name)
+            self._fill([f"{owner}.{stack}_scale_inv"])
+            return
+        if tuple(t.shape) != (ex.num_experts, O, K):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} does not fit {(ex.num_experts, O, K)}")
+        if t.dtype == torch.float8_e4m3fn:
+            for e in range(ex.num_experts):
+                ex.load_expert_(e, part, weight_fp8=t[e], name=name)
+            self._fill([f"{owner}.{stack}"])
+        elif t.is_floating_point():
+            for e in range(ex.num_experts):
+                ex.quantize_expert_(e, part, t[e], f"{name}[{e}]")
+            self._fill(self._keys(owner, stack))
+        else:
+            raise ValueError(f"{name}: {t.dtype} for an expert stack; FP8 bytes have to come as float8_e4m3fn with their _scale_inv")
+
     def _take_fused(self, name: str, owner: str, stack: str, t: torch.Tensor) -> None:
         q, part = self.experts[owner], "down" if stack == "down_proj" else "gate_up"
         if tuple(t.shape) != (q.num_experts, *q.shape_of(part)):
@@ -240,7 +311,7 @@ def save_quantized(model: nn.Module, path: str) -> None:
     """The body of the models' save_quantized: config.json with the tags read_config strips, and model.safetensors."""
     from safetensors.torch import save_file
     cfg = model.config
-    if getattr(cfg, "kivi_fp8_weights", False):
+    if getattr(cfg, "kivi_fp8_weights", False) or getattr(cfg, "kivi_fp8_experts", False):
         return _save_fp8(model, path)
     wbits, ebits = getattr(cfg, "kivi_weight_bits", None), getattr(cfg, "kivi_expert_bits", None)
     if wbits is None and ebits is None:
@@ -259,13 +330,15 @@ def save_quantized(model: nn.Module, path: str) -> None:
 
 
 def _save_fp8(model: nn.Module, path: str) -> None:
-    """save_quantized of a model built with fp8_weights: transformers' fine-grained FP8 format -- `weight` as
-    float8_e4m3fn and `weight_scale_inv` as float32 under the module names, and the `quantization_config` block read_config reads;
+    """save_quantized of a model built with fp8_weights or fp8_experts: transformers' fine-grained FP8 format (DESIGN.md sections 35
+    and 36) -- `weight` as float8_e4m3fn and `weight_scale_inv` as float32 under the module names, FP8 experts under the per-expert
+    names `mlp.experts.{e}.gate_proj / up_proj / down_proj`, and the `quantization_config` block read_config reads;
     `modules_to_not_convert` lists the linears that stayed dense, lm_head among them.  No tag of this project's."""
     from safetensors.torch import save_file
     cfg = model.config
     os.makedirs(path, exist_ok=True)
     fp8 = {n for n, m in model.named_modules() if isinstance(m, wfp8.Fp8Linear)}
+    stacks = {n: m for n, m in model.named_modules() if isinstance(m, Fp8Experts)}
     dense = [n for n, m in model.named_modules() if isinstance(m, nn.Linear)]
     d = dict(cfg.kivi_hf_config, quantization_config=dict(
         quant_method="fp8", fmt="e4m3", activation_scheme="dynamic", weight_block_size=[wfp8.BLOCK, wfp8.BLOCK], scale_fmt="float",
@@ -277,6 +350,16 @@ def _save_fp8(model: nn.Module, path: str) -> None:
         if cfg.tie_word_embeddings and k == "lm_head.weight":
             continue
         owner, _, leaf = k.rpartition(".")
+        if owner in stacks:
+            if leaf in ("gate_up_proj", "down_proj"):       # (the scales travel with their bytes)
+                ex = stacks[owner]
+                for e in range(ex.num_experts):
+                    for part in ("gate", "up") if leaf == "gate_up_proj" else ("down",):
+                        codes, bits = ex.slab(e, part)
+                        base = f"{owner}.{e}.{_FP8_EXPERT_LEAVES[part]}"
+                        state[f"{base}.weight"] = codes.detach().cpu().contiguous().view(torch.float8_e4m3fn)
+                        state[f"{base}.weight_scale_inv"] = bits.detach().cpu().contiguous().view(torch.float32)
+            continue
         v = v.detach().cpu().contiguous()
         if owner in fp8 and leaf in _FP8_PAIR:
             v = v.view(torch.float8_e4m3fn if leaf == "weight" else torch.float32)

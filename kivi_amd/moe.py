@@ -5,6 +5,8 @@ per token, each a SwiGLU MLP.  `route` / `experts` are the two HIP entries kivi_
 synchronise with the host -- for tensors off the GPU, shapes the kernels refuse and passes of many tokens.  `SparseMoeBlock` is the
 module the decoder layers carry as `mlp`; with `expert_bits=4` its experts are a `QuantExperts` -- the stacked matrices packed by
 kivi_w4_pack -- and every call takes `experts_w4_torch`, the loop with each hit expert dequantised first.
+With `expert_fp8=True` they are an `Fp8Experts` -- a checkpoint's own e4m3fn bytes and fp32 block scales -- served
+by `experts_w8`, the HIP entry kivi_moe_experts_w8 (launches only, capturable), and by `experts_w8_torch`, the dequantising loop.
 
 The contract: token n's experts are the K largest router LOGITS, descending, equal logits to the lower expert (a choice that is
 decidable from the inputs; HF's top-k over the fp32 probabilities picks the same experts wherever two probabilities differ); its
@@ -19,7 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, wquant
+from . import _lib, wfp8, wquant
 
 TOKEN_TILE = _lib.MOE_TOKEN_TILE        # pairs per tile of the grouped plan: include/kivi_hip.h, KIVI_MOE_TOKEN_TILE
 MAX_EXPERTS, MAX_TOP_K = _lib.MOE_MAX_E, _lib.MOE_MAX_K
@@ -29,6 +31,12 @@ MAX_EXPERTS, MAX_TOP_K = _lib.MOE_MAX_E, _lib.MOE_MAX_K
 # next measured size, 256, Mixtral's bf16 run is behind (0.84x; fp16 1.02x) while Qwen3's stay 38-44x ahead: a Qwen3-MoE user
 # may raise it.
 KERNEL_MAX_TOKENS = 64
+# The same rule for a block of FP8 experts, whose loop dequantises every hit expert before its GEMMs.  From
+# tools/moe_w8_time.py (profiles/moe_w8_time.log, MI355X): "crossover: w8 is no slower than the dequantising loop at both geometries
+# (every dtype run) at N in [1, 8, 32, 64, 256]; the largest such N below the first N at which it loses somewhere (None): 256; worst
+# loop / w8 per N: 1: 5.56, 8: 7.18, 32: 6.71, 64: 3.43, 256: 1.54" -- 256 is the largest size measured: at it the kernel is
+# 1.54-1.58x (Mixtral-8x7B) and 72-74x (Qwen3-30B-A3B) ahead; nothing above it has been timed.
+FP8_KERNEL_MAX_TOKENS = 256
 _DTYPES = {torch.float16: 16, torch.bfloat16: _lib.LOGITS_BF16}
 
 
@@ -308,6 +316,181 @@ def experts_w4_torch(x: torch.Tensor, plan: MoePlan, qexperts: QuantExperts) -> 
     return out
 
 
+class Fp8Experts(nn.Module):
+    """The stacked experts in FP8 in `_Experts`' place: the four buffers of transformers' FP8Experts under its
+    names, holding a checkpoint's own bytes -- gate_up_proj (E, 2 I, H) and down_proj (E, H, I) uint8 (e4m3fn, gate rows first), and
+    gate_up_proj_scale_inv (E, 2 I / 128, H / 128), down_proj_scale_inv (E, H / 128, I / 128) int32: the bit patterns of the fp32
+    block scales, which .half() / .bfloat16() cannot re-round (Fp8Linear's reason).  H and I are positive multiples of 128, so the
+    block grid of the stacked (2 I, H) matrix is the gate's followed by the up's.  No dense expert parameter exists."""
+
+    def __init__(self, num_experts: int, hidden: int, intermediate: int):
+        super().__init__()
+        if hidden < wfp8.BLOCK or hidden % wfp8.BLOCK:
+            raise ValueError(f"FP8 experts need hidden_size to be a positive multiple of {wfp8.BLOCK}, got {hidden}")
+        if intermediate < wfp8.BLOCK or intermediate % wfp8.BLOCK:
+            raise ValueError(f"FP8 experts need the experts' intermediate_size to be a positive multiple of {wfp8.BLOCK}, got "
+                             f"{intermediate}")
+        if not 1 <= num_experts <= MAX_EXPERTS:
+            raise ValueError(f"FP8 experts need num_experts in [1, {MAX_EXPERTS}], got {num_experts}")
+        self.num_experts, self.hidden, self.intermediate = num_experts, hidden, intermediate
+        E, H, I, B = num_experts, hidden, intermediate, wfp8.BLOCK
+        self.register_buffer("gate_up_proj", torch.zeros((E, 2 * I, H), dtype=torch.uint8))
+        self.register_buffer("gate_up_proj_scale_inv", torch.zeros((E, 2 * I // B, H // B), dtype=torch.int32))
+        self.register_buffer("down_proj", torch.zeros((E, H, I), dtype=torch.uint8))
+        self.register_buffer("down_proj_scale_inv", torch.zeros((E, H // B, I // B), dtype=torch.int32))
+
+    def extra_repr(self) -> str:
+        return f"num_experts={self.num_experts}, hidden={self.hidden}, intermediate={self.intermediate}, fp8=e4m3fn [128, 128]"
+
+    def shape_of(self, part: str):
+        I, H = self.intermediate, self.hidden
+        return {"gate": (I, H), "up": (I, H), "gate_up": (2 * I, H), "down": (H, I)}[part]
+
+    def slab(self, e: int, part: str):
+        """The views (bytes uint8, scale bits int32) that hold `part` (gate, up, gate_up or down) of expert e: contiguous."""
+        if part not in ("gate", "up", "gate_up", "down"):
+            raise ValueError(f"part has to be gate, up, gate_up or down, got {part!r}")
+        if not 0 <= e < self.num_experts:
+            raise ValueError(f"expert {e} outside [0, {self.num_experts})")
+        if part == "down":
+            return self.down_proj[e], self.down_proj_scale_inv[e]
+        I = self.intermediate
+        a, b = {"gate": (0, I), "up": (I, 2 * I), "gate_up": (0, 2 * I)}[part]
+        return self.gate_up_proj[e, a:b], self.gate_up_proj_scale_inv[e, a // wfp8.BLOCK:b // wfp8.BLOCK]
+
+    def load_expert_(self, e: int, part: str, weight_fp8: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                     name: str = "weight") -> "Fp8Experts":
+        """Take a checkpoint's tensors of `part` of expert e as they are, either or both: `weight_fp8` float8_e4m3fn is checked for
+        NaN bytes and copied as bytes; `scale`, fp32, is checked to be finite and copied as bits, a per-tensor scalar expanded to
+        the grid.  Refusals are ValueErrors by `name`."""
+        try:
+            wv, sv = self.slab(e, part)
+        except ValueError as err:
+            raise ValueError(f"{name}: {err}") from None
+        O, K = self.shape_of(part)
+        if weight_fp8 is not None:
+            if tuple(weight_fp8.shape) != (O, K):
+                raise ValueError(f"{name}: shape {tuple(weight_fp8.shape)} does not fit the {part} matrix {(O, K)}")
+            wv.copy_(wfp8.as_bytes(weight_fp8, name))
+        if scale is not None:
+            sv.copy_(wfp8.as_scale(scale, O, K, name).view(torch.int32))
+        return self
+
+    def quantize_expert_(self, e: int, part: str, weight16: torch.Tensor, name: str = "weight") -> "Fp8Experts":
+        """Quantise `weight16` -- the gate, up (I, H), gate_up (2 I, H) or down (H, I) matrix of expert e -- on its device into the
+        expert's slab (wfp8.quantize).  I is a multiple of 128: the stacked matrix quantises as gate and up apart."""
+        try:
+            wv, sv = self.slab(e, part)
+        except ValueError as err:
+            raise ValueError(f"{name}: {err}") from None
+        if tuple(weight16.shape) != self.shape_of(part):
+            raise ValueError(f"{name}: shape {tuple(weight16.shape)} does not fit the {part} matrix {self.shape_of(part)}")
+        codes, inv = wfp8.quantize(weight16, name)
+        if codes.device != wv.device:
+            raise ValueError(f"{name}: the weight is on {codes.device}, the module on {wv.device}")
+        wv.copy_(codes)
+        sv.copy_(inv.view(torch.int32))
+        return self
+
+    def dequant_expert(self, e: int, dtype=torch.float16, out=None):
+        """-> (gate_up (2 I, H), down (H, I)) of expert e in `dtype`: kivi_w8_dequant on the GPU, wfp8.dequant_torch (the same bits)
+        elsewhere.  `out`: a pair of contiguous buffers of those shapes to write into."""
+        res = []
+        for i, part in enumerate(("gate_up", "down")):
+            wv, sv = self.slab(e, part)
+            buf = None if out is None else out[i]
+            if wv.is_cuda:
+                if dtype not in _DTYPES:
+                    raise ValueError(f"FP8 experts on the GPU serve torch.float16 and torch.bfloat16, got {dtype}")
+                res.append(wfp8.dequant(wv, sv, dtype=dtype, out=buf))
+            else:
+                t = wfp8.dequant_torch(wv, sv.view(torch.float32), dtype)
+                res.append(t if buf is None else buf.copy_(t))
+        return tuple(res)
+
+    def dequant(self, dtype=torch.float16):
+        """-> the dense stacks gate_up (E, 2 I, H), down (E, H, I) in `dtype` (what a dense twin of the block holds)."""
+        pairs = [self.dequant_expert(e, dtype) for e in range(self.num_experts)]
+        return torch.stack([p[0] for p in pairs]), torch.stack([p[1] for p in pairs])
+
+    @classmethod
+    def from_dense(cls, gate_up: torch.Tensor, down: torch.Tensor) -> "Fp8Experts":
+        """Quantise stacked dense experts gate_up (E, 2 I, H), down (E, H, I) on their device (wfp8.quantize per matrix)."""
+        E, H, I = down.shape
+        if tuple(gate_up.shape) != (E, 2 * I, H):
+            raise ValueError(f"from_dense: gate_up {tuple(gate_up.shape)} and down {tuple(down.shape)} do not go together")
+        with torch.device(down.device):
+            m = cls(E, H, I)
+        for e in range(E):
+            m.quantize_expert_(e, "gate_up", gate_up[e].detach(), f"experts.gate_up[{e}]")
+            m.quantize_expert_(e, "down", down[e].detach(), f"experts.down[{e}]")
+        return m
+
+
+def usable_w8(x: torch.Tensor, num_experts: int, top_k: int, hidden: int, intermediate: int) -> bool:
+    """True where kivi_moe_experts_w8 serves: `usable`, with H and I multiples of 128."""
+    return usable(x, num_experts, top_k, hidden, intermediate) and hidden % wfp8.BLOCK == 0 and intermediate % wfp8.BLOCK == 0
+
+
+def experts_w8(x: torch.Tensor, plan: MoePlan, fp8experts: Fp8Experts, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One kivi_moe_experts_w8 call (three launches) over the four buffers of `fp8experts`.  x (N, H) fp16 or bf16 with unit channel
+    stride on the GPU; `plan`: route's for the same N.  -> (N, H) in the dtype; `out`: a contiguous buffer of that shape to write
+    into.  The workspace is kivi_moe_experts': allocated per call, under capture it belongs to the graph's pool."""
+    _lib.require_gpu(x, "x")
+    _lib.require_gpu(fp8experts.gate_up_proj, "gate_up_proj")
+    E, H, I = fp8experts.num_experts, fp8experts.hidden, fp8experts.intermediate
+    if x.dim() != 2 or x.shape[1] != H or E != plan.num_experts:
+        raise ValueError(f"kivi_moe_experts_w8: x {tuple(x.shape)}, experts (E = {E}, H = {H}, I = {I}) and a plan over "
+                         f"{plan.num_experts} experts do not go together")
+    if x.dtype not in _DTYPES or x.stride(1) != 1:
+        raise ValueError(f"kivi_moe_experts_w8: x must be fp16 or bf16 of unit channel stride, got {x.dtype}, strides {x.stride()}")
+    bufs = (fp8experts.gate_up_proj, fp8experts.gate_up_proj_scale_inv, fp8experts.down_proj, fp8experts.down_proj_scale_inv)
+    if [b.dtype for b in bufs] != [torch.uint8, torch.int32, torch.uint8, torch.int32] or not all(b.is_contiguous() for b in bufs):
+        raise ValueError("kivi_moe_experts_w8: the experts' buffers must be contiguous uint8 bytes and int32 scale bits")
+    N = x.shape[0]
+    if plan.tiles is None or tuple(plan.idx.shape) != (N, plan.top_k) or not plan.idx.is_cuda:
+        raise ValueError(f"kivi_moe_experts_w8: the plan must be route()'s for these {N} tokens")
+    if x.stride(0) % 8 or x.data_ptr() % 16:
+        x = x.contiguous()
+    if out is None:
+        out = torch.empty((N, H), dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (N, H) or out.dtype != x.dtype or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"kivi_moe_experts_w8: out must be contiguous {x.dtype} {(N, H)} on the GPU")
+    lib = _lib.load()
+    K = plan.top_k
+    nbytes = lib.kivi_moe_workspace_bytes(N, H, I, E, K)
+    if nbytes < 0:
+        _lib.check(-1, "kivi_moe_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    rc = lib.kivi_moe_experts_w8(
+        x.data_ptr(), x.stride(0), _DTYPES[x.dtype], N, H, I, E, K, plan.w.data_ptr(), plan.pairs.data_ptr(), plan.pos.data_ptr(),
+        plan.tiles.data_ptr(), plan.n_tiles.data_ptr(), *(b.data_ptr() for b in bufs), out.data_ptr(), out.stride(0), ws.data_ptr(),
+        nbytes, _lib.stream_ptr(x))
+    _lib.check(rc, "kivi_moe_experts_w8")
+    return out
+
+
+def experts_w8_torch(x: torch.Tensor, plan: MoePlan, fp8experts: Fp8Experts) -> torch.Tensor:
+    """experts_torch over FP8 experts, on any device: every expert that received a pair is dequantised to x's dtype into wquant's
+    shared scratch before its two F.linear's.  Synchronises."""
+    E, H, I = fp8experts.num_experts, fp8experts.hidden, fp8experts.intermediate
+    out = torch.zeros_like(x)
+    idx, w = plan.idx.long(), plan.w
+    mask = F.one_hot(idx, num_classes=E).permute(2, 1, 0)
+    hit = torch.greater(mask.sum(dim=(-1, -2)), 0).nonzero()
+    buf = wquant._scratch(x.device, x.dtype, 3 * I, H)
+    bufs = (buf[: 2 * I], buf[2 * I:].view(H, I))
+    for e in hit:
+        e = e[0]
+        k_pos, tok = torch.where(mask[e])
+        gate_up, down = fp8experts.dequant_expert(int(e), x.dtype, bufs)
+        g, u = F.linear(x[tok], gate_up).chunk(2, dim=-1)
+        y = F.linear(F.silu(g) * u, down)
+        y = y * w[tok, k_pos, None]
+        out.index_add_(0, tok, y.to(out.dtype))
+    return out
+
+
 class _Router(nn.Module):
     def __init__(self, num_experts: int, hidden: int):
         super().__init__()
@@ -329,23 +512,32 @@ class SparseMoeBlock(nn.Module):
     cannot run, and for at most `kernel_max_tokens` tokens otherwise; what the kernels do not serve (usable) takes the torch loop.
     `expert_bits=4`: the experts are a QuantExperts in groups of `expert_group` and every call takes the
     loop, with each hit expert dequantised into wquant's shared scratch first.  That loop synchronises, and there is no expert
-    kernel over the packed buffers yet: under stream capture such a block raises."""
+    kernel over the packed buffers yet: under stream capture such a block raises.
+    `expert_fp8`: the experts are an Fp8Experts, exclusive with `expert_bits`.  kivi_moe_experts_w8 runs under
+    stream capture and for at most `kernel_max_tokens` tokens otherwise (None: FP8_KERNEL_MAX_TOKENS); above that, off the GPU and
+    with `kernel=False` the dequantising loop runs, which under capture raises as the 4-bit block does."""
 
     def __init__(self, hidden: int, intermediate: int, num_experts: int, top_k: int, norm_topk: bool = True,
                  round_weights: bool = False, kernel: bool = True, kernel_max_tokens: Optional[int] = None,
-                 expert_bits: Optional[int] = None, expert_group: int = 128):
+                 expert_bits: Optional[int] = None, expert_group: int = 128, expert_fp8: bool = False):
         super().__init__()
         if not 1 <= top_k <= num_experts:
             raise ValueError(f"num_experts_per_tok = {top_k} outside [1, num_experts = {num_experts}]")
         if expert_bits not in (None, 4):
             raise ValueError(f"expert_bits has to be None or 4, got {expert_bits!r}")
+        if expert_fp8 and expert_bits is not None:
+            raise ValueError("expert_fp8 and expert_bits=4 are two formats of the same experts: choose one")
         self.hidden, self.intermediate, self.num_experts, self.top_k = hidden, intermediate, num_experts, top_k
         self.norm_topk, self.round_weights = bool(norm_topk), bool(round_weights)
         self.kernel = bool(kernel)
         self.expert_bits = expert_bits
-        self.kernel_max_tokens = KERNEL_MAX_TOKENS if kernel_max_tokens is None else int(kernel_max_tokens)
+        self.expert_fp8 = bool(expert_fp8)
+        default = FP8_KERNEL_MAX_TOKENS if self.expert_fp8 else KERNEL_MAX_TOKENS
+        self.kernel_max_tokens = default if kernel_max_tokens is None else int(kernel_max_tokens)
         self.gate = _Router(num_experts, hidden)
-        if expert_bits is None:
+        if self.expert_fp8:
+            self.experts = Fp8Experts(num_experts, hidden, intermediate)
+        elif expert_bits is None:
             self.experts = _Experts(num_experts, hidden, intermediate)
         else:
             self.experts = QuantExperts(num_experts, hidden, intermediate, expert_group)
@@ -363,11 +555,17 @@ class SparseMoeBlock(nn.Module):
         logits = F.linear(x2, self.gate.weight)
         if self.uses_kernel(x2):
             plan = route(logits, self.top_k, self.norm_topk, self.round_weights)
+            if self.expert_fp8:
+                return experts_w8(x2, plan, self.experts).view(B, Q, H)
             return experts(x2, plan, self.experts.gate_up_proj, self.experts.down_proj).view(B, Q, H)
-        if self.expert_bits is not None and x2.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise _lib.KiviHipError("a sparse block with expert_bits=4 cannot run under stream capture: its experts go through the "
-                                    "dequantising loop, which synchronises, and no kernel over the packed experts exists")
+        if (self.expert_bits is not None or self.expert_fp8) and x2.is_cuda and torch.cuda.is_current_stream_capturing():
+            what = "expert_fp8 and kernel=False" if self.expert_fp8 else "expert_bits=4"
+            why = "the kernel over them is switched off" if self.expert_fp8 else "no kernel over the packed experts exists"
+            raise _lib.KiviHipError(f"a sparse block with {what} cannot run under stream capture: its experts go through the "
+                                    f"dequantising loop, which synchronises, and {why}")
         plan = route_torch(logits, self.top_k, self.norm_topk, self.round_weights)
+        if self.expert_fp8:
+            return experts_w8_torch(x2, plan, self.experts).view(B, Q, H)
         if self.expert_bits is not None:
             return experts_w4_torch(x2, plan, self.experts).view(B, Q, H)
         return experts_torch(x2, plan, self.experts.gate_up_proj, self.experts.down_proj).view(B, Q, H)
